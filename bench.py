@@ -12,7 +12,14 @@ Descriptor extraction shards over GPUs with no data-path collective (clouds are 
 -> weak scaling; value = clouds all ranks processed / max-over-ranks time.
 
 --steps K: the timed region is K steps between fences (barrier + synchronize, max over ranks); it is repeated --regions
-times (default 7) and `value` / `ms_per_step` are the MEDIAN region's, `regions` holds min / max.
+times (default 1; 7 with --full) and `value` / `ms_per_step` are the MEDIAN region's, `regions` holds min / max.
+
+A plain run (no --full) does only what the headline needs: set up, warm up (--warmup W steps, then --settle-ms of untimed
+steps), time the K steps of the f32-equivalent arithmetic with no stage events, write --dump-outputs, print the line.  --full
+adds everything below: stage events and `roofline` / `stage_ms` / `stage_floor`, `overlapped`, `fast`, `configs`,
+`pipeline_hbm`, `cpu_baseline`, and the RCCL process group at N = 1.
+--dump-outputs DIR: after the timed region, the descriptors of its last step -> DIR/descriptors.npy (float32, (batch, 256);
+DIR/descriptors_rank<r>.npy per rank at N > 1).  Clouds and weights are seeded: the same arguments give the same inputs.
 
 `value` / `dtype` / `roofline` belong to EPC_PRECISION_F32 (include/epcnet.h): the f32-equivalent arithmetic (conv layers:
 both MFMA operands scaled by a per-row / per-column power of two and split into fp16 hi + lo, three products, f32 accumulate
@@ -22,7 +29,7 @@ float32 on the ill-conditioned cases).  The same timed region is then repeated i
 activation, weights fp16 hi + MX-fp6 lo; right-or-refuses outside fp16's range) and reported in the `fast` object with its
 own roofline -- never as `value`.
 
-Objects on the JSON line:
+Objects on the JSON line with --full:
   roofline     dominant kernel = conv5 + L2 norm + soft-assignment (conv5_kernel<256,VLAD>), bound = MFMA, priced against
                the dense bf16 peak (2.5 PFLOP/s): achieved = ALGORITHMIC FLOPs per launch (2.684 GFLOP per cloud)
                / its average duration from HIP events the library records on the launch stream inside the timed region
@@ -260,6 +267,21 @@ def median(xs):
     return xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2])
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, name, t, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: a result of the timed path as DIRECTORY/<name>.npy (float32), for comparing two builds output for
+    output.  Past `max_bytes` a fixed, seeded sample of its rows (sorted) is written instead."""
+    import numpy as np
+    a = t.detach().float().cpu().numpy()
+    max_rows = max(1, max_bytes // max(1, a[:1].nbytes))
+    if a.shape[0] > max_rows:
+        a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], max_rows, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def lib_sha256():
     """SHA-256 of the libepcnet_hip.so this process loaded (stamped into profiles/pmc_*_current.json at collection time)."""
     import hashlib
@@ -302,9 +324,11 @@ def kernel_entry(summary, prefix):
     return None
 
 
-def extraction_leg(H, E, store, arch, precision, batch, steps, warmup, settle_ms, every, lanes, regions=1):
+def extraction_leg(H, E, store, arch, precision, batch, steps, warmup, settle_ms, every, lanes, regions=1, full=True):
     """The timed region of one (arch, precision): K steps on ONE stream (stage-boundary HIP events on every `every`-th
-    step), then -- separately reported -- the same K steps with `lanes` of them in flight."""
+    step), then -- separately reported -- the same K steps with `lanes` of them in flight.  ``full`` False (a plain run):
+    the K steps alone, no stage events, no in-flight region, no roofline.  Returns (result, median region seconds, the
+    descriptors of the last timed step)."""
     import torch
     device = H.device
     eng = E.InferenceEngine(arch, PARAMS, store, outer=OUTER, micro_batch=batch, in_flight=max(1, lanes), precision=precision)
@@ -313,13 +337,14 @@ def extraction_leg(H, E, store, arch, precision, batch, steps, warmup, settle_ms
     xyz = (torch.rand((batch, N_POINTS, 3), generator=g) * 2.0 - 1.0).to(device)
     outs = [torch.empty((batch, 256), dtype=torch.float32, device=device) for _ in range(max(1, lanes))]
     out = outs[0]
-    profiles = {(r, k): E.StageProfile() for r in range(regions) for k in range(0, steps, every)}
-    scratch = E.StageProfile()
+    profiles = {(r, k): E.StageProfile() for r in range(regions) for k in range(0, steps, every)} if full else {}
+    scratch = E.StageProfile() if full else None
     for k in range(max(warmup, 0)):
-        eng.forward(xyz, out=out, profile=scratch if k % every == 0 else None, check=False)   # the entry point the timed steps use
+        eng.forward(xyz, out=out, profile=scratch if full and k % every == 0 else None, check=False)   # the entry point the timed steps use
     if warmup > 0:
         torch.cuda.synchronize()
-        scratch.elapsed_ms()                                   # first event query happens outside the timed region
+        if scratch is not None:
+            scratch.elapsed_ms()                               # first event query happens outside the timed region
         # Settle: a process that starts right after another GPU process has exited (pytest, then this) can see one
         # 70-80 ms dispatch stall while the driver tears the old process down -- observed as a single slow kNN launch.
         # Keep issuing UNTIMED steps until the device has been busy for --settle-ms since the first launch.
@@ -329,9 +354,19 @@ def extraction_leg(H, E, store, arch, precision, batch, steps, warmup, settle_ms
             torch.cuda.synchronize()
     region_s = H.timed_regions(lambda r, k: eng.forward(xyz, out=out, profile=profiles.get((r, k)), check=False), steps, regions)
     elapsed = median(region_s)
+    last = out.clone()                                         # (the in-flight region below writes `out` again)
     norms = out.norm(dim=1)
     if not bool(torch.isfinite(out).all()) or float((norms - 1).abs().max()) > 1e-3:
         raise SystemExit("descriptors are not unit-norm / finite: refusing to report a number")
+    key = (arch, precision)
+    res = {"value": round(H.world * batch * steps / elapsed, 2), "unit": "clouds/s", "dtype": DTYPE[key],
+           "ms_per_step": round(elapsed / steps * 1e3, 4),
+           "regions": {"count": regions, "steps_each": steps, "statistic": "median",
+                       "ms_per_step_min": round(region_s[0] / steps * 1e3, 4), "ms_per_step_max": round(region_s[-1] / steps * 1e3, 4),
+                       "value_min": round(H.world * batch * steps / region_s[-1], 2),
+                       "value_max": round(H.world * batch * steps / region_s[0], 2)}}
+    if not full:
+        return res, elapsed, last
 
     # second, separately reported region: the same K steps with `lanes` of them in flight (InferenceEngine.submit deals
     # successive steps over the engine's own HIP streams, own workspace and output buffer each: step k+1's kNN (VALU-bound)
@@ -354,7 +389,6 @@ def extraction_leg(H, E, store, arch, precision, batch, steps, warmup, settle_ms
     conv5_ms = stage["conv5"]
     conv5_flops = (CONV5_ASSIGN_FLOPS if arch == "epc-net" else CONV5_L_FLOPS) * batch
     achieved = conv5_flops / (conv5_ms * 1e-3) / 1e12
-    key = (arch, precision)
     # HBM bytes / MFMA-busy fraction per launch of the dominant kernel from the committed rocprofv3 PMC summaries of this
     # same command (profiles/; collected by scripts/collect_profiles.sh at batch 64 / 256)
     std_batch = batch == (64 if arch == "epc-net" else 256)
@@ -374,15 +408,9 @@ def extraction_leg(H, E, store, arch, precision, batch, steps, warmup, settle_ms
     if hbm is None or comp is None:
         roofline["counters_unavailable"] = ("batch differs from the profiled configuration" if not std_batch else
                                             "; ".join(sorted(set(_PMC_WHY.values()))))
-    res = {"value": round(H.world * batch * steps / elapsed, 2), "unit": "clouds/s", "dtype": DTYPE[key],
-           "ms_per_step": round(elapsed / steps * 1e3, 4),
-           "regions": {"count": regions, "steps_each": steps, "statistic": "median",
-                       "ms_per_step_min": round(region_s[0] / steps * 1e3, 4), "ms_per_step_max": round(region_s[-1] / steps * 1e3, 4),
-                       "value_min": round(H.world * batch * steps / region_s[-1], 2),
-                       "value_max": round(H.world * batch * steps / region_s[0], 2)},
-           "roofline": roofline,
-           "stage_ms": {k: round(v, 4) for k, v in stage.items()},
-           "pipeline_tflops": round(batch * steps / elapsed * FLOPS_PER_CLOUD[arch] / 1e12, 3)}
+    res.update({"roofline": roofline,
+                "stage_ms": {k: round(v, 4) for k, v in stage.items()},
+                "pipeline_tflops": round(batch * steps / elapsed * FLOPS_PER_CLOUD[arch] / 1e12, 3)})
     if arch == "epc-net" and precision == "f32" and batch == 64:
         fl = stage_floors_epc_net_f32_b64()
         res["stage_floor_ms"] = fl
@@ -393,7 +421,7 @@ def extraction_leg(H, E, store, arch, precision, batch, steps, warmup, settle_ms
                                        "bytes / 6.3 TB/s (DESIGN.md 4, Floor models)" % (MFMA_GHZ, VALU_GHZ)}
     if overlapped is not None:
         res["overlapped"] = overlapped
-    return res, elapsed
+    return res, elapsed, last
 
 
 def train_counters(precision, n_clouds):
@@ -610,9 +638,18 @@ def main():
                     help="process-group backend: nccl = RCCL (the product's); gloo = the dry run of the N > 1 code on a box with fewer GPUs")
     ap.add_argument("--same-device", action="store_true",
                     help="every rank on cuda:0 (with --backend gloo: RCCL refuses two ranks on one GPU); numbers from it are not credit")
-    ap.add_argument("--regions", type=int, default=7,
-                    help="fenced regions of --steps steps each; value / ms_per_step = the median region (min / max reported)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="fenced regions of --steps steps each; value / ms_per_step = the median region (min / max reported); "
+                         "default 1, 7 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: stage events and roofline, the in-flight region, the fast "
+                         "arithmetic, the configs legs, pipeline_hbm, cpu_baseline, the world-of-one RCCL group")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the descriptors of the headline's last timed step to DIR/descriptors.npy (float32; "
+                         "DIR/descriptors_rank<r>.npy per rank at N > 1)")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 7 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])                        # does not return
@@ -655,7 +692,7 @@ def main():
             sk.bind(("127.0.0.1", 0))
             os.environ["MASTER_PORT"] = str(sk.getsockname()[1])
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    if world > 1 or not args.no_rccl:
+    if world > 1 or (args.full and not args.no_rccl):
         try:
             if args.backend == "nccl":
                 tdist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
@@ -675,16 +712,24 @@ def main():
     lanes = max(1, args.in_flight)
 
     store = build_store(args.arch, device, seed=0)             # same weights on every rank
-    precisions = ["f32"] if args.arch == "epc-net-l" else (["f32", "fast"] if args.precision == "both" else [args.precision])
-    legs = {}
+    if args.arch == "epc-net-l":
+        precisions = ["f32"]
+    elif args.precision == "both":
+        precisions = ["f32", "fast"] if args.full else ["f32"]
+    else:
+        precisions = [args.precision]
+    legs, last = {}, {}
     for prec in precisions:
-        legs[prec], _ = extraction_leg(H, E, store, args.arch, prec, args.batch, args.steps, args.warmup, args.settle_ms,
-                                       every, lanes, regions=max(1, args.regions))
+        legs[prec], _, last[prec] = extraction_leg(H, E, store, args.arch, prec, args.batch, args.steps, args.warmup, args.settle_ms,
+                                                   every, lanes, regions=max(1, args.regions), full=args.full)
     head_prec = precisions[0]
     head = legs[head_prec]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "descriptors" if world == 1 else "descriptors_rank%d" % rank, last[head_prec],
+                     DUMP_MAX_BYTES // world)
 
     configs = {}
-    if not args.no_configs and args.arch == "epc-net":
+    if args.full and not args.no_configs and args.arch == "epc-net":
         # The bounded legs may not take the headline down with them: a leg that raises is reported as {"error": ...} (on every rank the
         # same way: the legs' collectives raise on all ranks or on none).
         # A leg that raises is reported as {"error": ...} and the process exits non-zero AFTER the line is printed.  The
@@ -715,8 +760,8 @@ def main():
 
         def l_leg():
             stl = build_store("epc-net-l", device, seed=0)
-            leg, _ = extraction_leg(H, E, stl, "epc-net-l", "f32", 256, max(10, min(50, args.steps)), min(args.warmup, 10), 0.0,
-                                    every, 1)
+            leg, _, _ = extraction_leg(H, E, stl, "epc-net-l", "f32", 256, max(10, min(50, args.steps)), min(args.warmup, 10), 0.0,
+                                       every, 1)
             leg["workload"] = "EPC-Net-L inference, batch 256x4096x3 fp32 per GPU (BASELINE.json configs[3]; models/epc-net-l.py:29-102)"
             # `roofline` above is conv5 + max-pool's (the MFMA kernel); by TIME the leg is kNN + the two ProxyConv blocks (two thirds of
             # it), neither of which is MFMA- or HBM-bound: kNN saturates VALU issue (286.6 M vector instructions per launch = 0.98 of
@@ -764,7 +809,7 @@ def main():
     # by scripts/collect_profiles.sh on this configuration) x their launches per step: the figure behind "fraction of the
     # HBM roofline" (north_star); the path is MFMA / VALU-bound, so it is a secondary number.
     hbm_step = None
-    pm = pmc_summary("pmc_hbm_current.json")
+    pm = pmc_summary("pmc_hbm_current.json") if args.full else None
     if pm and args.arch == "epc-net" and args.batch == 64 and head_prec in pm.get("launches_per_step", {}):
         try:
             hbm_step = sum(v["hbm_bytes_per_launch_corrected"] * m for k, v in pm["kernels"].items()
@@ -783,11 +828,12 @@ def main():
                        "clouds_per_step_per_gpu": args.batch, "num_points": N_POINTS,
                        "precision": "EPC_PRECISION_%s (include/epcnet.h)" % head_prec.upper(),
                        "weights": "seeded random init of the architecture (no checkpoint payloads exist)",
-                       "parallelism": "independent clouds sharded over %d GPU(s), no data-path collective" % world,
-                       "stage_events_on_every_nth_step": every},
-            "regions": head["regions"],
-            "roofline": head["roofline"], "stage_ms": head["stage_ms"], "pipeline_tflops": head["pipeline_tflops"],
+                       "parallelism": "independent clouds sharded over %d GPU(s), no data-path collective" % world},
+            "regions": head["regions"], "full": bool(args.full),
         }
+        if args.full:
+            line["config"]["stage_events_on_every_nth_step"] = every
+            line["roofline"], line["stage_ms"], line["pipeline_tflops"] = head["roofline"], head["stage_ms"], head["pipeline_tflops"]
         if "stage_floor_ms" in head:
             line["stage_floor_ms"], line["stage_floor"] = head["stage_floor_ms"], head["stage_floor"]
         if args.requested_gpus and args.requested_gpus != world:
@@ -805,7 +851,7 @@ def main():
                                     "model_bytes": int(18.2e6 * args.batch), "ratio": round(hbm_step / (18.2e6 * args.batch), 3),
                                     "ratio_is": "the 3-byte feature map's round trip (conv5 writes it, the aggregate reads it): a design limit",
                                     "how": "PMC bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, profiles/) x launches per step / ms_per_step"}
-        elif args.arch == "epc-net" and args.batch == 64:
+        elif args.full and args.arch == "epc-net" and args.batch == 64:
             line["pipeline_hbm"] = None
             line["pipeline_hbm_unavailable"] = _PMC_WHY.get("pmc_hbm_current.json", "no launch table for this arithmetic")
         line["lib_sha256"] = lib_sha256()
@@ -815,7 +861,7 @@ def main():
             line["fast"] = legs["fast"]
         if configs:
             line["configs"] = configs
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.arch, store if args.arch != "epc-net" or not configs else build_store(args.arch, device, 0),
                                                 args.cpu_budget_s, args.cpu_clouds)
         line["backend"] = {"name": args.backend if group_up else None, "rccl": bool(rccl), "ranks": world,

@@ -66,7 +66,7 @@ for k in sorted(set(fetch) | set(write)):
     kernels[k] = {"FETCH_SIZE_KB_mean": round(f_kb, 1), "WRITE_SIZE_KB_mean": round(w_kb, 1),
                   "hbm_bytes_per_launch_corrected": int(round((2.0 * f_kb + w_kb) * 1024)), "launches": max(n, n2)}
 if kernels:
-    doc = {"command": "rocprofv3 --kernel-trace --pmc <C> --output-format csv -- python3 bench.py --steps 5 --warmup 2 "
+    doc = {"command": "rocprofv3 --kernel-trace --pmc <C> --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 "
                       "--no-cpu-baseline (separate passes for FETCH_SIZE and WRITE_SIZE; scripts/collect_profiles.sh)",
            "tag": tag, "lib_sha256": LIB_SHA, "correction": "bytes = 2 x FETCH_SIZE + WRITE_SIZE (KB x 1024)", "kernels": kernels}
     for name in (tag + "_pmc_hbm.json",) + (() if SIDE else ("pmc_hbm_current.json",)):
@@ -137,7 +137,7 @@ if comp:
         sets = open(os.path.join(src, "pmc_compute_sets.txt")).read()
     except Exception:
         pass
-    doc = {"command": "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python3 bench.py --steps 5 --warmup 2 "
+    doc = {"command": "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 "
                       "--no-cpu-baseline --in-flight 1 --no-configs (two passes; scripts/collect_profiles.sh)",
            "tag": tag, "lib_sha256": LIB_SHA, "counter_sets": sets,
            "derived": "mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs); valu_active_lane_fraction = "
