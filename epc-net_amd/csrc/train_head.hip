@@ -787,9 +787,11 @@ extern "C" int epc_group_sum_bwd(const float* dy, int rows_out, int G, int O, fl
 // ONE workgroup of 1024 threads.  The column-wise parts: thread (column c = tid % O, slice q = tid / O), every reduction over rows on
 // the slices in parallel, meeting in LDS in slice order (bit-reproducible).  The (B, O) x (O, O) products on the matrix pipe: the B <= 32
 // rows are ONE 32-row tile in LDS (rows beyond B zero), a wave takes 32-column tiles, operands split into bf16 pieces exactly as the
-// per-op GEMMs split them (forward three pieces / six products, backward two / three) -- f32-accurate in BOTH arithmetics of the step:
-// products with at most 32 rows stay float32 under "bf16" too (oracle/epcnet_oracle_torch.py: bf16_product_rule; the per-op path ran
-// them on plain FMAs).  A first version on scalar FMAs with v broadcast from LDS took 106 / 146 us: one CU's LDS pipe.
+// per-op GEMMs split them (forward three pieces / six products, backward two / three).  Which products round to one bf16 piece under
+// "bf16" follows oracle/epcnet_oracle_torch.py: bf16_product_rule (all sides >= 64, K >= 32).  The two products with B <= 32 rows -- gl
+// and dv -- stay f32-accurate in BOTH arithmetics (the per-op path ran them on plain FMAs).  The weight gradient dWg = v^T dgl has K = B:
+// under "bf16" at B = 32 the rule rounds its operands, as the per-op GEMM does for every B > 32, and so does this kernel (one piece each).
+// A first version on scalar FMAs with v broadcast from LDS took 106 / 146 us: one CU's LDS pipe.
 // O in {64, 128, 256}; B <= 32.
 // ----------------------------------------------------------------------------------------------------------------
 #include "train_chain_common.h"
@@ -899,6 +901,30 @@ __global__ __launch_bounds__(HT_THREADS) void hidden_tail_fwd_kernel(const float
     }
 }
 
+// dWg (O, O) = v^T dgl over the 32-row tiles vs / dgls (LDS, row stride O): 32 x 32 output tiles over the waves, the 32 rows two k-steps;
+// P bf16 pieces per operand (P = 1: each operand rounded to bf16, one product)
+template <int P>
+__device__ __forceinline__ void ht_dwg(const float* vs, const float* dgls, int O, float* __restrict__ dWg) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6, i = lane & 31, hh = lane >> 5, T = O / 32;
+    for (int t = wave; t < T * T; t += nwaves) {
+        const int mt = t / T, nt = t % T;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            float a8[8], b8[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) a8[j] = vs[(16 * s + 8 * hh + j) * O + 32 * mt + i], b8[j] = dgls[(16 * s + 8 * hh + j) * O + 32 * nt + i];
+            bf16x8 ap[P], bp[P];
+            ch_split<P>(a8, ap), ch_split<P>(b8, bp);
+            acc = ch_prod<P>(ap, bp, acc);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dWg[(size_t)(32 * mt + mfma_row(r, hh)) * O + 32 * nt + i] = acc[r];
+    }
+}
+
 // Backward: from dout (B, O) and the forward's h, mean1, var1, v, gl, mean2, var2:
 //   s = sigmoid(bn2(gl));  dv = dout s;  dgt = dout v s (1 - s);  bn2': dgl = gamma2 rstd2 (dgt - dbeta2 / B - gt^ dgamma2 / B);
 //   dWg = v^T dgl;  dv += dgl Wg^T;  dy[b G + g] = dv[b];  bn1': dh = gamma1 rstd1 (dy - dbeta1 / R - z^ dgamma1 / R)
@@ -909,7 +935,7 @@ __global__ __launch_bounds__(HT_THREADS) void hidden_tail_bwd_kernel(const float
                                                                     const float* __restrict__ gl, const float* __restrict__ Wg,
                                                                     const float* __restrict__ gamma2, const float* __restrict__ beta2,
                                                                     const float* __restrict__ mean2, const float* __restrict__ var2, float eps,
-                                                                    float* __restrict__ dh, float* __restrict__ dgamma1,
+                                                                    int dw_rounded, float* __restrict__ dh, float* __restrict__ dgamma1,
                                                                     float* __restrict__ dbeta1, float* __restrict__ dWg, float* __restrict__ dgamma2,
                                                                     float* __restrict__ dbeta2) {
     extern __shared__ __attribute__((aligned(16))) float lds[];   // vs[32][O] | dgl[32][O] | dv[32][O] | red[slices][O]
@@ -942,26 +968,8 @@ __global__ __launch_bounds__(HT_THREADS) void hidden_tail_bwd_kernel(const float
     }
     __syncthreads();
     // ---- dWg = v^T dgl: 32 x 32 output tiles over the waves, the 32 rows are two k-steps ----
-    {
-        const int lane = tid & 63, wave = tid >> 6, nwaves = HT_THREADS / 64, i = lane & 31, hh = lane >> 5, T = O / 32;
-        for (int t = wave; t < T * T; t += nwaves) {
-            const int mt = t / T, nt = t % T;
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                float a8[8], b8[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) a8[j] = vs[(16 * s + 8 * hh + j) * O + 32 * mt + i], b8[j] = dgls[(16 * s + 8 * hh + j) * O + 32 * nt + i];
-                bf16x8 ap[P], bp[P];
-                ch_split<P>(a8, ap), ch_split<P>(b8, bp);
-                acc = ch_prod<P>(ap, bp, acc);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dWg[(size_t)(32 * mt + mfma_row(r, hh)) * O + 32 * nt + i] = acc[r];
-        }
-    }
+    if (dw_rounded) ht_dwg<1>(vs, dgls, O, dWg);
+    else ht_dwg<P>(vs, dgls, O, dWg);
     ht_product<P, true, true>(dgls, Wg, O, dvs);   // dv += dgl Wg^T
     __syncthreads();
     // ---- the group sum's transpose and bn1's backward over the R rows ----
@@ -1004,20 +1012,24 @@ extern "C" int epc_hidden_tail_fwd(const float* h, int B, int G, int O, const fl
 
 extern "C" int epc_hidden_tail_bwd(const float* dout, const float* h, int B, int G, int O, const float* gamma1, const float* mean1, const float* var1,
                                    const float* v, const float* gl, const float* Wg, const float* gamma2, const float* beta2, const float* mean2,
-                                   const float* var2, float eps, float* dh, float* dgamma1, float* dbeta1, float* dWg,
+                                   const float* var2, float eps, int pieces, float* dh, float* dgamma1, float* dbeta1, float* dWg,
                                    float* dgamma2, float* dbeta2, void* stream) {
     EPC_CHECK_ARG(dout && h && gamma1 && mean1 && var1 && v && gl && Wg && gamma2 && beta2 && mean2 && var2 && dh && dgamma1 && dbeta1 && dWg &&
                       dgamma2 && dbeta2,
                   "null pointer");
     EPC_CHECK_ARG(ht_shape_ok(B, G, O), "shape not covered (epc_hidden_tail_ok)");
     EPC_CHECK_ARG((reinterpret_cast<size_t>(Wg) & 15) == 0, "Wg must be 16-byte aligned");
+    EPC_CHECK_ARG(pieces == 1 || pieces == 2, "pieces must be 1 (bf16) or 2 (f32-accurate)");
+    // "bf16" (pieces 1): dWg = v^T dgl is (O x B)(B x O) with O >= 64, so its operands round to bf16 once K = B reaches 32 -- the rule of
+    // oracle/epcnet_oracle_torch.py (bf16_product_rule) and of the per-op GEMM that takes B > 32; the two products with B rows stay f32-accurate
+    const int dw_rounded = pieces == 1 && B >= 32;
     const size_t lds = ((size_t)3 * HT_ROWS * O + (size_t)(HT_THREADS / O) * O) * sizeof(float);
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(hidden_tail_bwd_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         epc_set_error("%s: hipFuncSetAttribute failed", __func__);
         return EPC_EHIP;
     }
     hipLaunchKernelGGL(hidden_tail_bwd_kernel<2>, dim3(1), dim3(HT_THREADS), lds, (hipStream_t)stream, dout, h, B, G, O, gamma1, mean1, var1, v, gl, Wg,
-                       gamma2, beta2, mean2, var2, eps, dh, dgamma1, dbeta1, dWg, dgamma2, dbeta2);
+                       gamma2, beta2, mean2, var2, eps, dw_rounded, dh, dgamma1, dbeta1, dWg, dgamma2, dbeta2);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
 }

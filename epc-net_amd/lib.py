@@ -182,7 +182,7 @@ _lib.epc_gate_fwd.argtypes = [_P, _P, ctypes.c_long, _P, _P]
 _lib.epc_gate_bwd.argtypes = [_P, _P, _P, ctypes.c_long, _P, _P, _P]
 _lib.epc_hidden_tail_ok.argtypes = [c_int, c_int, c_int]
 _lib.epc_hidden_tail_fwd.argtypes = [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, c_float, c_float] + [_P] * 9 + [_P]
-_lib.epc_hidden_tail_bwd.argtypes = [_P, _P, c_int, c_int, c_int] + [_P] * 10 + [c_float] + [_P] * 7
+_lib.epc_hidden_tail_bwd.argtypes = [_P, _P, c_int, c_int, c_int] + [_P] * 10 + [c_float, c_int] + [_P] * 7
 _lib.epc_chain_parts.argtypes = [c_int]
 _lib.epc_chain_stats.argtypes = [_P, c_int, _P, _P]
 _lib.epc_chain_fwd_linear.argtypes = [_P] * 7 + [c_float, _P, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P]

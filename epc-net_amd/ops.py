@@ -1363,7 +1363,8 @@ class HiddenTail(torch.autograd.Function):
         y = slim.batch_norm(h);  v = reduce_sum over the G group rows;  out = v * sigmoid(slim.batch_norm(v @ gating_weights))
     Returns (out (B, O), mean1, var1u, mean2, var2u): the batch means and the Bessel-corrected batch variances -- what the fused slim
     op feeds its moving averages (the population variances normalise).  The gating product is f32-accurate in both arithmetics of the
-    step (at most 32 rows: oracle/epcnet_oracle_torch.py, bf16_product_rule)."""
+    step (at most 32 rows: oracle/epcnet_oracle_torch.py, bf16_product_rule), and so is dv; its weight gradient dWg = v^T dgl has K = B and
+    follows the same rule: under "bf16" at B = 32 its operands round to bf16, as the per-op GEMM rounds them for every B > 32."""
 
     @staticmethod
     def forward(ctx, h, gamma1, beta1, G, Wg, gamma2, beta2, eps):
@@ -1381,7 +1382,7 @@ class HiddenTail(torch.autograd.Function):
                                         var1u.data_ptr(), v.data_ptr(), gl.data_ptr(), mean2.data_ptr(), var2.data_ptr(), var2u.data_ptr(),
                                         out.data_ptr(), _st()))
         ctx.save_for_backward(h, gamma1, mean1, var1, v, gl, Wg, gamma2, beta2, mean2, var2)
-        ctx.G, ctx.eps = G, float(eps)
+        ctx.G, ctx.eps, ctx.pieces = G, float(eps), 1 if _GEMM_PRECISION == "bf16" else 2
         ctx.mark_non_differentiable(mean1, var1u, mean2, var2u)
         ctx.set_materialize_grads(False)
         return out, mean1, var1u, mean2, var2u
@@ -1401,7 +1402,7 @@ class HiddenTail(torch.autograd.Function):
         dg1, db1, dg2, db2 = vec(), vec(), vec(), vec()
         L.check(lib.epc_hidden_tail_bwd(dout.data_ptr(), h.data_ptr(), B, ctx.G, O, gamma1.data_ptr(), mean1.data_ptr(), var1.data_ptr(),
                                         v.data_ptr(), gl.data_ptr(), Wg.data_ptr(), gamma2.data_ptr(), beta2.data_ptr(), mean2.data_ptr(),
-                                        var2.data_ptr(), ctx.eps, dh.data_ptr(), dg1.data_ptr(), db1.data_ptr(), dWg.data_ptr(),
+                                        var2.data_ptr(), ctx.eps, ctx.pieces, dh.data_ptr(), dg1.data_ptr(), db1.data_ptr(), dWg.data_ptr(),
                                         dg2.data_ptr(), db2.data_ptr(), _st()))
         return dh, dg1, db1, None, dWg, dg2, db2, None
 

@@ -513,14 +513,16 @@ int epc_gate_bwd(const float* dout, const float* y, const float* g, long n, floa
  * One workgroup; reductions meet in a fixed order (bit-reproducible); the (B, O) x (O, O) products on the matrix pipe with the per-op
  * GEMMs' f32-accurate arithmetic (forward three bf16 pieces per operand: six products; backward two: three) in both arithmetics of the
  * step: products with at most 32 rows stay float32 under "bf16" as well.  Shapes: epc_hidden_tail_ok(B, G, O): B <= 32, O in {64, 128, 256}.
- * The backward takes the forward's h, mean1, var1, v, gl, mean2, var2 and returns dh, dgamma1, dbeta1, dWg, dgamma2, dbeta2. */
+ * The backward takes the forward's h, mean1, var1, v, gl, mean2, var2 and returns dh, dgamma1, dbeta1, dWg, dgamma2, dbeta2; `pieces`: the
+ * step's arithmetic, 1 = "bf16", 2 = f32-accurate.  Under "bf16" the weight gradient dWg = v^T dgl (K = B) takes one bf16 value per
+ * operand at B = 32, as every product with all sides >= 64 and K >= 32 does (the per-op GEMM for B > 32). */
 int epc_hidden_tail_ok(int B, int G, int O);
 int epc_hidden_tail_fwd(const float* h, int B, int G, int O, const float* gamma1, const float* beta1, const float* Wg,
                         const float* gamma2, const float* beta2, float eps, float bessel1, float bessel2, float* mean1,
                         float* var1, float* var1u, float* v, float* gl, float* mean2, float* var2, float* var2u, float* out, void* stream);
 int epc_hidden_tail_bwd(const float* dout, const float* h, int B, int G, int O, const float* gamma1, const float* mean1, const float* var1,
                         const float* v, const float* gl, const float* Wg, const float* gamma2, const float* beta2, const float* mean2,
-                        const float* var2, float eps, float* dh, float* dgamma1, float* dbeta1, float* dWg,
+                        const float* var2, float eps, int pieces, float* dh, float* dgamma1, float* dbeta1, float* dWg,
                         float* dgamma2, float* dbeta2, void* stream);
 
 /* The grouped hidden projection itself in the training step (loupe.py:302-322; csrc/train_hidden.hip): Y (M, 256) = X (M, K) W (K, 256)

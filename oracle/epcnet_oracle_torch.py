@@ -357,28 +357,37 @@ def train_step(weights: Dict[str, np.ndarray], query, positives, negatives, othe
                adam_m: Optional[Dict[str, np.ndarray]] = None, adam_v: Optional[Dict[str, np.ndarray]] = None,
                arch="epc-net", params=None, m1=0.5, m2=0.2, base_lr=5e-5, batch_num_queries=1, dtype=torch.float64,
                relu_masks: Optional[Dict[str, np.ndarray]] = None, gemm_rounding: Optional[str] = None,
-               value_pins: Optional[Dict[str, np.ndarray]] = None):
+               value_pins: Optional[Dict[str, np.ndarray]] = None, decay_step: float = 200000):
     """One reference training step (train.py:251-277, 484-495): returns dict(loss, grads, new_weights, adam_m, adam_v).
 
     ``step`` = value of the global-step variable BEFORE the step (``batch``, train.py:246): bn_decay is evaluated with
-    it; Adam's bias correction uses t = step + 1 (TensorFlow's beta*_power are multiplied after each apply)."""
+    it, ``batch_num_queries`` and ``decay_step`` (DECAY_STEP); Adam's bias correction uses t = step + 1 (TensorFlow's beta*_power are
+    multiplied after each apply)."""
     orc = TorchOracle(weights, arch, params, dtype)
     orc.relu_masks = relu_masks        # None = the reference's relu; a dict pins the masks (see TorchOracle.__init__)
     orc.gemm_rounding = gemm_rounding  # None = exact products; "bf16" = the configs[2] arithmetic (TorchOracle.__init__)
     orc.value_pins = value_pins        # None, or the stored pre-activations of the implementation under test (TorchOracle.__init__)
     vecs = np.concatenate([query, positives, negatives, other_neg], axis=1)          # train.py:252
-    bn_decay = O.get_bn_decay(step, batch_num_queries)
+    bn_decay = O.get_bn_decay(step, batch_num_queries, decay_step=decay_step)
     out = orc.forward(vecs, True, bn_decay)
     npos, nneg = positives.shape[1], negatives.shape[1]
     q, pos, neg, oth = torch.split(out, [1, npos, nneg, 1], dim=1)                    # train.py:255
     select_on = None
     if value_pins is not None and "descriptors" in value_pins:
-        # the descriptors of the implementation under test: the loss SELECTS on them (lazy_quadruplet_loss), the values stay this
-        # oracle's own
+        # the descriptors of the implementation under test, a value pin like the layers' (TorchOracle._pin): the loss SELECTS on them
+        # (lazy_quadruplet_loss) and its gradient is formed at their values.  That gradient is made of DIFFERENCES of nearly equal
+        # descriptors (q - pos, q - neg, neg - other), so a descriptor's last-bit difference between two arithmetics comes out of it
+        # amplified, and the same error then flows into every tensor of the backward alike -- systematic, not averaged by a projection.
+        # The returned "loss" stays this oracle's own (its descriptors, the pinned selection); value_pin_gap["descriptors"] holds the gap.
         pin = torch.as_tensor(np.asarray(value_pins["descriptors"], dtype=np.float64).reshape(tuple(out.shape)), dtype=out.dtype)
         orc.value_pin_gap["descriptors"] = float((pin - out.detach()).abs().max() / out.detach().abs().max())
         select_on = torch.split(pin, [1, npos, nneg, 1], dim=1)
+        with torch.no_grad():
+            own_loss = float(lazy_quadruplet_loss(q, pos, neg, oth, m1, m2, select_on))
+        q, pos, neg, oth = torch.split(out + (pin - out).detach(), [1, npos, nneg, 1], dim=1)
     loss = lazy_quadruplet_loss(q, pos, neg, oth, m1, m2, select_on)
+    if select_on is None:
+        own_loss = float(loss.detach())
     grads = torch.autograd.grad(loss, [orc.w[k] for k in orc.trainable], allow_unused=True)
     lr = O.get_learning_rate(epoch, base_lr)
     b1, b2, eps = 0.9, 0.999, 1e-8                                                    # tf.train.AdamOptimizer defaults
@@ -396,7 +405,7 @@ def train_step(weights: Dict[str, np.ndarray], query, positives, negatives, othe
         g_out[k] = g
     for k, v in orc.new_stats.items():
         new_w[k] = v.numpy().copy()
-    return {"loss": float(loss.detach()), "grads": g_out, "new_weights": new_w, "adam_m": am, "adam_v": av,
+    return {"loss": own_loss, "grads": g_out, "new_weights": new_w, "adam_m": am, "adam_v": av,
             "lr": lr, "bn_decay": bn_decay, "descriptors": out.detach().numpy(),
             "relu_mask_disagreement": dict(orc.relu_mask_disagreement), "value_pin_gap": dict(orc.value_pin_gap)}
 

@@ -24,7 +24,7 @@ fwd = lambda: L.check(lib.epc_hidden_tail_fwd(h.data_ptr(), B, G, O, g1.data_ptr
                                               1.0, 1.0, m1.data_ptr(), v1.data_ptr(), v1u.data_ptr(), v.data_ptr(), gl.data_ptr(), m2.data_ptr(), v2.data_ptr(),
                                               v2u.data_ptr(), out.data_ptr(), st))
 bwd = lambda: L.check(lib.epc_hidden_tail_bwd(dout.data_ptr(), h.data_ptr(), B, G, O, g1.data_ptr(), m1.data_ptr(), v1.data_ptr(), v.data_ptr(), gl.data_ptr(),
-                                              Wg.data_ptr(), g2.data_ptr(), b2.data_ptr(), m2.data_ptr(), v2.data_ptr(), 1e-3, dh.data_ptr(), dg1.data_ptr(),
+                                              Wg.data_ptr(), g2.data_ptr(), b2.data_ptr(), m2.data_ptr(), v2.data_ptr(), 1e-3, 2, dh.data_ptr(), dg1.data_ptr(),
                                               db1.data_ptr(), dWg.data_ptr(), dg2.data_ptr(), db2.data_ptr(), st))
 for name, fn in (("epc_hidden_tail_fwd", fwd), ("epc_hidden_tail_bwd", bwd)):
     for _ in range(10):

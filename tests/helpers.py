@@ -2,6 +2,7 @@
 import ctypes
 import importlib
 import os
+import re
 import sys
 
 import numpy as np
@@ -134,3 +135,41 @@ def run_stages(eng, xyz):
     out["status"] = status
     torch.cuda.synchronize()
     return out
+
+
+# ---- which launch form a call reached -------------------------------------------------------------------------------------------------
+# The training step's kernels choose their form from the row count and the CU count (rows_tile_waves, epc_chain_parts, ...).  A test that
+# exists for one form asserts that it reached it, so that a later change to a heuristic cannot quietly turn it into a duplicate.
+
+def launched_kernels(fn):
+    """Run fn() under torch.profiler; returns (fn's result, {device kernel name: launches})."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        out = fn()
+        torch.cuda.synchronize()
+    names = {}
+    for e in prof.events():
+        if str(getattr(e, "device_type", "")).endswith("CUDA"):
+            names[e.name] = names.get(e.name, 0) + 1
+    return out, names
+
+
+_ROWGEMM = (re.compile(r"hx_rowgemm_kernel<(\d+),(true|false),(unsignedshort|float),(\d+),(\d+),(true|false),(\d+)>"),
+            re.compile(r"hx_rowgemm_kernelILi(\d+)ELb([01])E([tf])Li(\d+)ELi(\d+)ELb([01])ELi(\d+)E"))
+
+
+def rowgemm_forms(names):
+    """{(NT, XFORM, 'u16' | 'f32', P, KSC, BNB, NW): launches} of hx_rowgemm_kernel (csrc/train_head_common.h) among `names`, demangled or
+    mangled; NW = 3 is the 96-row workgroup, 4 the 128-row one."""
+    forms = {}
+    for name, count in names.items():
+        flat = name.replace(" ", "")
+        for rx in _ROWGEMM:
+            m = rx.search(flat)
+            if m:
+                nt, xf, ta, p, ksc, bnb, nw = m.groups()
+                key = (int(nt), xf in ("true", "1"), "f32" if ta in ("float", "f") else "u16", int(p), int(ksc), bnb in ("true", "1"), int(nw))
+                forms[key] = forms.get(key, 0) + count
+                break
+    return forms

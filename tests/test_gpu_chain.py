@@ -46,7 +46,10 @@ def _backbone(arch, w, pc, dev, use_chain, precision="bf16x6", upstream_seed=3):
 
 
 @pytest.mark.parametrize("arch,ncl,n,kind", [("epc-net", 3, 256, "uniform"), ("epc-net-l", 5, 96, "uniform"),
-                                            ("epc-net", 18, 4096, "uniform"), ("epc-net", 2, 256, "ties")])
+                                            ("epc-net", 18, 4096, "uniform"), ("epc-net", 2, 256, "ties"),
+                                            # beyond the persistent form (14 tiles per workgroup on 256 CUs), and 288 workgroups of the
+                                            # sixteen tiles that are the most one takes: more workgroups than CUs
+                                            ("epc-net", 28, 4096, "uniform"), ("epc-net", 36, 4096, "uniform")])
 def test_chain_equals_the_per_layer_operators(dev, arch, ncl, n, kind):
     """The fused chain against the per-layer operators (LinearBatchNormTrain / ProxyConvTail: the round-3 step) on the same weights,
     clouds and upstream gradient: the same products in the same arithmetic, only the pooling order of the batch statistics differs --
@@ -59,8 +62,19 @@ def test_chain_equals_the_per_layer_operators(dev, arch, ncl, n, kind):
     if kind == "ties":
         pc[0, 40:120] = pc[0, 7]                      # 81 copies of one point: every one of them selects all the others
         pc[1] = 0.0                                   # evaluate.py:425-430 / train.py:834-844 padding cloud
+    if ncl * n > 24 * 4096:
+        rows, lib = ncl * n, H.pkg("lib").lib()
+        parts, cus = lib.epc_chain_parts(rows), torch.cuda.get_device_properties(0).multi_processor_count
+        tiles = -(-rows // parts) // 32
+        print("%dx%d rows: %d chain workgroups of %d tiles on %d CUs" % (ncl, n, parts, tiles, cus))
+        assert lib.epc_chain_persist_ok(rows) == 0 and (parts, tiles) == {28: (256, 14), 36: (288, 16)}[ncl], (parts, tiles, cus)
     a = _backbone(arch, w, pc, dev, True)
     b = _backbone(arch, w, pc, dev, False)
+    hold_to_the_per_layer_operators(a, b, arch, ncl, n, kind)
+
+
+def hold_to_the_per_layer_operators(a, b, arch, ncl, n, kind):
+    """_backbone's result through the chain (a) against the per-layer operators' (b)."""
     assert np.isfinite(a[0]).all()
     # (bars: full size -- 16 x the activations -- sees ReLU-mask flips between the two float32 implementations, each moving a few
     # gradient elements by per cents of a tensor's maximum (test_gpu_train_step.py holds both to float64 with the masks pinned); the

@@ -12,7 +12,7 @@ import torch
 
 import helpers as H
 from helpers import O
-from test_gpu_chain import _backbone
+from test_gpu_chain import _backbone, hold_to_the_per_layer_operators
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,11 +65,16 @@ print("CHILD OK")
 @pytest.mark.parametrize("arch,ncl,n,kind,precision", [("epc-net", 3, 256, "uniform", "bf16x6"), ("epc-net-l", 5, 96, "uniform", "bf16x6"),
                                                       ("epc-net", 2, 32, "uniform", "bf16x6"),          # two workgroups of one wave: two groups of one
                                                       ("epc-net", 2, 256, "ties", "bf16x6"), ("epc-net", 18, 4096, "uniform", "bf16x6"),
-                                                      ("epc-net", 22, 4096, "uniform", "bf16"), ("epc-net", 7, 1000, "uniform", "bf16")])
+                                                      ("epc-net", 22, 4096, "uniform", "bf16"), ("epc-net", 7, 1000, "uniform", "bf16"),
+                                                      ("epc-net", 24, 4096, "uniform", "bf16x6")])      # twelve waves: the largest form
 def test_persistent_chain_equals_the_launch_chain(dev, arch, ncl, n, kind, precision):
     """Outputs to 1e-5 of their scale, moving statistics to 2e-6, gradients to 1e-4 relative L2 (small sizes; at full size ReLU-mask
     flips between two float32 summation orders move single gradient elements: the bars of test_gpu_chain)."""
-    assert H.pkg("lib").lib().epc_chain_persist_ok(ncl * n) == 1
+    lib = H.pkg("lib").lib()
+    assert lib.epc_chain_persist_ok(ncl * n) == 1
+    if ncl * n == 24 * 4096:       # 256 workgroups of twelve 32-row tiles (waves) on 256 CUs: the persistent kernel's largest LDS
+        parts = lib.epc_chain_parts(ncl * n)
+        assert (parts, -(-ncl * n // parts) // 32) == (256, 12), (parts, torch.cuda.get_device_properties(0).multi_processor_count)
     w = O.seeded_weights(arch, 4)
     pc = O.synthetic_clouds(ncl, n, 11)
     if kind == "ties":
@@ -172,3 +177,7 @@ def test_rows_beyond_the_persistent_form_take_the_launch_chain(dev):
     a = _with_persist(True, lambda: _backbone("epc-net-l", w, pc, dev, True))
     b = _with_persist(False, lambda: _backbone("epc-net-l", w, pc, dev, True))
     assert np.array_equal(a[0], b[0])
+    # (both settings took the launch chain, so the comparison above only shows that no persistent launch happened: the result is also
+    # held to the per-layer operators with test_gpu_chain's bars)
+    c = _backbone("epc-net-l", w, pc, dev, False)
+    hold_to_the_per_layer_operators(a, c, "epc-net-l", 25, 4096, "uniform")

@@ -31,7 +31,31 @@ def _bf16(t):
     return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)
 
 
-@pytest.mark.parametrize("B,N", [(3, 96), (5, 32), (18, 256), (2, 1024), (4, 4096)])
+# Launch forms the larger cases are there for (256 CUs; on another CU count the assertion fails on purpose): the assignment product of the
+# forward -- 3: 96-row workgroups over all rows; 4: the per-cloud grid of 128-row tiles whose batch moments are finalised per cloud
+# (epc_moments_finalize_launch with n_points: partial tiles when n_points % 128 != 0) -- and the dcat product with the BatchNorm backward
+# formed inside (rows_tile_waves on two workgroups per CU: 96 or 128 rows).
+HEAD16_FORMS = {(14, 4096): dict(dx=4), (28, 4096): dict(assign=4, dx=4), (100, 1120): dict(assign=4, dx=4)}
+HEAD32_FORMS = {(22, 4096): dict(assign=4, dx=3), (28, 4096): dict(assign=3, dx=4)}
+
+
+def _run(fn, want):
+    return H.launched_kernels(fn) if want else (fn(), {})
+
+
+def _assert_forms(want, head, fwd_kernels, bwd_kernels):
+    if not want:
+        return
+    fwd, bwd = H.rowgemm_forms(fwd_kernels), H.rowgemm_forms(bwd_kernels)
+    print("%s row-GEMM forms: forward %s, backward %s" % (head, sorted(fwd), sorted(bwd)))
+    assign = {k[6] for k in fwd if k[0] == 2 and k[1] and k[2] == head}
+    dx = {k[6] for k in bwd if k[0] == 8 and k[5] and k[2] == head}
+    if "assign" in want:
+        assert assign == {want["assign"]}, fwd
+    assert dx == {want["dx"]}, bwd
+
+
+@pytest.mark.parametrize("B,N", [(3, 96), (5, 32), (18, 256), (2, 1024), (4, 4096), (14, 4096), (28, 4096), (100, 1120)])
 def test_head16_node_matches_the_rounded_restatement(dev, B, N):
     import epcnet_oracle_torch as T
     ops = H.pkg("ops")
@@ -40,10 +64,12 @@ def test_head16_node_matches_the_rounded_restatement(dev, B, N):
     prev = ops.set_gemm_precision("bf16")
     try:
         xs = [leaves[k].float().to(dev).requires_grad_(True) for k in names]
-        vlad, a_sum, mean5, var5, mean_c, var_c, z5, rn = ops.Conv5VladHead.apply(xs[0], xs[1], xs[2], xs[3], xs[4], EPS, xs[5], xs[6],
-                                                                                  xs[7], EPS, N, "bf16")
+        want = HEAD16_FORMS.get((B, N))
+        (vlad, a_sum, mean5, var5, mean_c, var_c, z5, rn), kf = _run(
+            lambda: ops.Conv5VladHead.apply(xs[0], xs[1], xs[2], xs[3], xs[4], EPS, xs[5], xs[6], xs[7], EPS, N, "bf16"), want)
         loss = (vlad * wv.float().to(dev)).sum() + (a_sum * wa.float().to(dev)).sum()
-        grads = torch.autograd.grad(loss, xs, allow_unused=True)
+        grads, kb = _run(lambda: torch.autograd.grad(loss, xs, allow_unused=True), want)
+        _assert_forms(want, "u16", kf, kb)
         z5f = ops.expand16(z5).double().cpu()
         mask = (ops.expand16(z5, (mean5, var5, xs[3].detach(), xs[4].detach(), EPS), None) > 0).cpu()
         # the same call again: bit-identical results (fixed summation orders, no atomics)
@@ -93,7 +119,7 @@ def test_head16_node_matches_the_rounded_restatement(dev, B, N):
     assert worst[0] <= 3e-3, worst
 
 
-@pytest.mark.parametrize("B,N", [(3, 96), (18, 256), (4, 4096)])
+@pytest.mark.parametrize("B,N", [(3, 96), (18, 256), (4, 4096), (22, 4096), (28, 4096)])
 def test_head32_node_matches_the_exact_graph(dev, B, N):
     """The same node in the default f32-accurate arithmetic (csrc/train_head32.hip: f32 tensors, split products) against the EXACT
     function -- _Head16 with the rounding off, i.e. the plain graph in float64 -- with the ReLU mask of the HIP forward pinned: outputs to
@@ -103,10 +129,12 @@ def test_head32_node_matches_the_exact_graph(dev, B, N):
     leaves, (wv, wa) = _inputs(B, N, 31 + N, dev)
     names = list(leaves)
     xs = [leaves[k].float().to(dev).requires_grad_(True) for k in names]
-    vlad, a_sum, mean5, var5, mean_c, var_c, z5, rn = ops.Conv5VladHead.apply(xs[0], xs[1], xs[2], xs[3], xs[4], EPS, xs[5], xs[6],
-                                                                              xs[7], EPS, N, "f32")
+    want = HEAD32_FORMS.get((B, N))
+    (vlad, a_sum, mean5, var5, mean_c, var_c, z5, rn), kf = _run(
+        lambda: ops.Conv5VladHead.apply(xs[0], xs[1], xs[2], xs[3], xs[4], EPS, xs[5], xs[6], xs[7], EPS, N, "f32"), want)
     loss = (vlad * wv.float().to(dev)).sum() + (a_sum * wa.float().to(dev)).sum()
-    grads = torch.autograd.grad(loss, xs, allow_unused=True)
+    grads, kb = _run(lambda: torch.autograd.grad(loss, xs, allow_unused=True), want)
+    _assert_forms(want, "f32", kf, kb)
     assert z5.dtype == torch.float32
     mask = (ops.bn_apply_train(z5, mean5, var5, xs[3].detach(), xs[4].detach(), EPS, True) > 0).cpu()
     d_ = [x.detach() for x in xs]

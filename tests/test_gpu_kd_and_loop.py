@@ -208,13 +208,14 @@ def _dataset(T, n, seed=0):
     return queries, data
 
 
-@pytest.mark.parametrize("arch", ["epc-net-l"])
-def test_training_loop_with_mining_and_resume(dev, tmp_path, arch):
+@pytest.mark.parametrize("arch,nq", [pytest.param("epc-net-l", 1, id="epc-net-l"), pytest.param("epc-net-l", 2, id="epc-net-l-2q")])
+def test_training_loop_with_mining_and_resume(dev, tmp_path, arch, nq):
+    """nq = BATCH_NUM_QUERIES: the loop's batches of nq tuples (train.py:330-617), eager and replayed, and the resumed continuation."""
     V = H.pkg("variables")
     TR = H.pkg("training")
     TL = H.pkg("train_loop")
     tb = H.pkg("tf_bundle")
-    params = dict(H.PARAMS, ARCH=arch, BATCH_NUM_QUERIES=1, POSITIVES_PER_QUERY=2, NEGATIVES_PER_QUERY=6,
+    params = dict(H.PARAMS, ARCH=arch, BATCH_NUM_QUERIES=nq, POSITIVES_PER_QUERY=2, NEGATIVES_PER_QUERY=6,
                   NUM_POINTS=N, BASE_LEARNING_RATE=1e-3, MAX_EPOCH=8)
     queries, data = _dataset(40, N)
     st = V.reset_default_store(device=dev, seed=0)
@@ -246,8 +247,9 @@ def test_training_loop_with_mining_and_resume(dev, tmp_path, arch):
     ent = tb.read_index(prefix + ".index")
     assert "Variable" in ent and "beta1_power" in ent
     assert "query_triplets/fastdgcnn/conv1/weights/Adam_1" in ent and "query_triplets/VLAD/fc1/weights" in ent
-    q = [torch.from_numpy(data[i][None, None]).to(dev) for i in range(4)]
-    batch = (q[0], torch.cat([q[1], q[2]], 1), torch.cat([q[3]] * 6, 1), q[1])
+    q = [torch.from_numpy(data[i][None, None]).to(dev) for i in range(3 + nq)]
+    tuples = [(q[j], torch.cat([q[j + 1], q[j + 2]], 1), torch.cat([q[j + 3]] * 6, 1), q[j + 1]) for j in range(nq)]
+    batch = tuple(torch.cat([t[k] for t in tuples], 0) for k in range(4))
     l_a, _, _ = ts.step(*batch, epoch=6)
     w_a = st.vars["query_triplets/VLAD/fc1/weights"].detach().clone()
     st2 = V.reset_default_store(device=dev, seed=123)

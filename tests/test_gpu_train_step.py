@@ -18,7 +18,11 @@ pytestmark = pytest.mark.gpu
 # operand elements that round the other way.  Before the pins the same comparison measured 8.2e-2 and the bars were 8e-2 / 1e-1.
 BF16_STEP_BAR_ALL = 3e-2
 BF16_STEP_BAR_LARGE = {256: 1e-1, 4096: 3e-2}
-BF16_STEP_ALPHA_BAR = 2.5e-3    # |alpha - 1| of the large tensors: measured 3e-5 .. 1.0e-3 over the four sizes (conv5's weights 3e-5 .. 3e-4)
+# |alpha - 1| of the large tensors: measured 3e-5 .. 1.0e-3 over the four one-query sizes (conv5's weights 3e-5 .. 3e-4) when the oracle's
+# loss gradient was formed at its own descriptors, up to 1.5e-3 with the descriptors' values pinned.  The first layer's small tensors
+# (conv1/weights: 192 elements, conv1/bn/beta: 64) are the noisiest: at 2 x 16 x 4096 their alpha moved between 1.2e-3 and 2.5e-3 when only
+# the summation order behind the descriptors changed (scripts/bf16_step_alpha.py: the fused hidden projection and tail on or off).
+BF16_STEP_ALPHA_BAR = 2.5e-3
 
 
 @pytest.fixture(scope="module")
@@ -31,22 +35,78 @@ def _rel(a, b):
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
 
 
-@pytest.mark.parametrize("arch,nneg,n", [("epc-net", 14, 256), ("epc-net", 18, 256), ("epc-net-l", 14, 256),
-                                         # BASELINE.json configs[2] at FULL size: 18 x 4096 (the reference's tuple,
-                                         # configs/epc-net.yaml:28-34) and 22 x 4096 (BASELINE.json's "18 neg")
-                                         ("epc-net", 14, 4096), ("epc-net", 18, 4096)])
-def test_train_step_matches_gradient_oracle(dev, arch, nneg, n):
+def _step_forms(st, nq, ncl, n):
+    """What the step at nq x ncl clouds of n points reaches, by the exported predicates:
+    (hidden projection fused, hidden tail fused, persistent chain, chain workgroups, chain tiles per workgroup)."""
+    ops, lib = H.pkg("ops"), H.pkg("lib").lib()
+    rows, B, G = nq * ncl * n, nq * ncl, H.PARAMS["GROUPS"]
+    K = int(st.vars[H.OUTER + "/VLAD/hidden1_weights"].shape[0])
+    parts = lib.epc_chain_parts(rows)
+    return (ops.hidden_proj_ok(B * G, K, 256), ops.hidden_tail_ok(B * G, G, 256), bool(lib.epc_chain_persist_ok(rows)), parts,
+            -(-rows // parts) // 32)
+
+
+def _assert_reaches(case, st, nq, ncl, n, head, kernels):
+    """The launch forms a new case of the step is there for (the shapes assume 256 CUs: on another CU count this fails on purpose)."""
+    if case is None:
+        return
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    proj, tail, persist, parts, tiles = _step_forms(st, nq, ncl, n)
+    forms = H.rowgemm_forms(kernels)
+    xf = {k: v for k, v in forms.items() if k[1] and k[2] == head}      # the assignment product: (forward with moments, da) per step
+    dx = {k[6] for k in forms if k[0] == 8 and k[5] and k[2] == head}  # the dcat product with the BatchNorm backward formed inside
+    print("step %s %dx%dx%d: hidden projection fused %s, hidden tail fused %s, persistent chain %s, %d chain workgroups of %d tiles on %d CUs; "
+          "row-GEMM forms %s" % (head, nq, ncl, n, proj, tail, persist, parts, tiles, cus, sorted(forms.items())))
+    want = dict(case)
+    assert (proj, tail) == (want.pop("proj"), want.pop("tail")), (proj, tail)
+    if "persist" in want:
+        assert persist == want.pop("persist")
+    if "parts" in want:
+        assert parts == want["parts"] and tiles == want.pop("tiles") and (parts > cus) == want.pop("parts_over_cus"), (parts, tiles, cus)
+        want.pop("parts")
+    if "dx" in want:
+        assert dx == {want.pop("dx")}, forms
+    if "assign" in want:
+        nw = want.pop("assign")                 # 4: the per-cloud 128-row grid with its moments (n_points finalise); 3: the 96-row one
+        assert xf.get((2, True, head, 1 if head == "u16" else 2, 4, False, nw), 0) >= (2 if nw == 4 else 1), forms
+    assert not want, want
+
+
+# The cases of more than one query (BATCH_NUM_QUERIES > 1: the reference pools BatchNorm over B x P clouds, models/epc-net.py:34-57) are
+# there for the launch forms the step only takes at 25+ clouds on 256 CUs; each asserts that it reaches them (_assert_reaches).
+_FALLBACKS = dict(proj=False, tail=False)          # M = 4 B > 128 rows: ops.Linear for the hidden projection; B > 32: the per-op tail
+STEP_CASES = [pytest.param("epc-net", 1, 14, 256, None, id="epc-net-14-256"), pytest.param("epc-net", 1, 18, 256, None, id="epc-net-18-256"),
+              pytest.param("epc-net-l", 1, 14, 256, None, id="epc-net-l-14-256"),
+              # BASELINE.json configs[2] at FULL size: 18 x 4096 (the reference's tuple, configs/epc-net.yaml:28-34) and 22 x 4096
+              # (BASELINE.json's "18 neg")
+              pytest.param("epc-net", 1, 14, 4096, None, id="epc-net-14-4096"), pytest.param("epc-net", 1, 18, 4096, None, id="epc-net-18-4096"),
+              pytest.param("epc-net", 2, 14, 256, _FALLBACKS, id="epc-net-2x18-256"),
+              pytest.param("epc-net-l", 2, 14, 256, None, id="epc-net-l-2x18-256"),      # (no VLAD tail: its fc1 head pools 36 clouds)
+              # 32 clouds: every fused path at its edge -- hidden projection M = 128, hidden tail B = 32, the launch chain at 16 tiles per
+              # workgroup, the 128-row fused-BatchNorm dcat product
+              pytest.param("epc-net", 2, 12, 4096, dict(proj=True, tail=True, persist=False, parts=256, tiles=16, parts_over_cus=False, dx=4),
+                           id="epc-net-2x16-4096"),
+              # 36 clouds: 288 chain workgroups of 16 tiles (more than CUs), both fallbacks
+              pytest.param("epc-net", 2, 14, 4096, dict(_FALLBACKS, persist=False, parts=288, tiles=16, parts_over_cus=True),
+                           id="epc-net-2x18-4096")]
+
+
+@pytest.mark.parametrize("arch,nq,nneg,n,case", STEP_CASES)
+def test_train_step_matches_gradient_oracle(dev, arch, nq, nneg, n, case):
     import epcnet_oracle_torch as T
-    ncl = 1 + 2 + nneg + 1                                   # 18 (reference config) or 22 (BASELINE.json "18 neg")
+    ncl = 1 + 2 + nneg + 1                                   # 18 (reference config) or 22 (BASELINE.json "18 neg") clouds per query
     w0 = O.seeded_weights(arch, 4)
-    pcs = O.synthetic_clouds(ncl, n, 9)
-    q, pos, neg, oth = pcs[None, :1], pcs[None, 1:3], pcs[None, 3:3 + nneg], pcs[None, 3 + nneg:]
+    pcs = O.synthetic_clouds(nq * ncl, n, 9).reshape(nq, ncl, n, 3)
+    q, pos, neg, oth = pcs[:, :1], pcs[:, 1:3], pcs[:, 3:3 + nneg], pcs[:, 3 + nneg:]
     step0, epoch = 3, 7                                      # non-trivial bias correction and LR decay
-    ref = T.train_step(w0, q, pos, neg, oth, step=step0, epoch=epoch, arch=arch)
+    # (one query: the reference's DECAY_STEP, bn_decay 0.5; two: floor(step0 B / 4) = 1 -- bn_decay 0.75, where B = 1 would give 0.5)
+    decay_step = 200000 if nq == 1 else 4
+    ref = T.train_step(w0, q, pos, neg, oth, step=step0, epoch=epoch, arch=arch, batch_num_queries=nq, decay_step=decay_step)
+    assert ref["bn_decay"] == (0.5 if nq == 1 else 0.75)
 
     st = H.make_store(arch, w0, dev)
     TR = H.pkg("training")
-    params = dict(H.PARAMS, ARCH=arch, BATCH_NUM_QUERIES=1, DECAY_STEP=200000, BASE_LEARNING_RATE=5e-5,
+    params = dict(H.PARAMS, ARCH=arch, BATCH_NUM_QUERIES=nq, DECAY_STEP=decay_step, BASE_LEARNING_RATE=5e-5,
                   MARGIN_1=0.5, MARGIN_2=0.2)
     ts = TR.TrainStep(params, st, outer=H.OUTER)
     ts.global_step = step0
@@ -67,7 +127,11 @@ def test_train_step_matches_gradient_oracle(dev, arch, nneg, n):
     TFU.RELU_MASK_TAPS = {}                                  # the ReLU masks of THIS forward, for the mask-pinned comparison below
     try:
         to = lambda a: torch.from_numpy(a).to(dev)
-        loss, lr, bn_decay = ts.step(to(q), to(pos), to(neg), to(oth), epoch=epoch)
+        first_step = lambda: ts.step(to(q), to(pos), to(neg), to(oth), epoch=epoch)
+        if case is None:
+            loss, lr, bn_decay = first_step()
+        else:
+            (loss, lr, bn_decay), kernels = H.launched_kernels(first_step)
     finally:
         H.pkg("ops").adam_multi = orig
         TR.ops.adam_multi = orig
@@ -76,6 +140,7 @@ def test_train_step_matches_gradient_oracle(dev, arch, nneg, n):
     masks = {k[len(H.OUTER) + 1:]: v.cpu().numpy() for k, v in masks.items()}
     assert len(masks) == (13 if arch == "epc-net" else 8), sorted(masks)     # 12 + conv5 / 6 + conv5 + fc1 ReLU'd layers
 
+    _assert_reaches(case, st, nq, ncl, n, "f32", kernels if case is not None else {})
     assert lr == pytest.approx(ref["lr"]) and bn_decay == pytest.approx(ref["bn_decay"])
     assert float(loss) == pytest.approx(ref["loss"], rel=2e-5, abs=1e-6)
     assert ts.global_step == step0 + 1
@@ -89,7 +154,8 @@ def test_train_step_matches_gradient_oracle(dev, arch, nneg, n):
     # float64 gradients as that (and never needs to be closer than the small-size bars).
     noise = {}
     if n == 4096:
-        ref32 = T.train_step(w0, q, pos, neg, oth, step=step0, epoch=epoch, arch=arch, dtype=torch.float32)
+        ref32 = T.train_step(w0, q, pos, neg, oth, step=step0, epoch=epoch, arch=arch, dtype=torch.float32, batch_num_queries=nq,
+                             decay_step=decay_step)
         for k, g_ref in ref["grads"].items():
             d = ref32["grads"][k].astype(np.float64) - g_ref
             noise[k] = (np.abs(d).max() / max(np.abs(g_ref).max(), 1e-30), np.linalg.norm(d) / max(np.linalg.norm(g_ref), 1e-30))
@@ -120,10 +186,12 @@ def test_train_step_matches_gradient_oracle(dev, arch, nneg, n):
     # one of the 62 (30) gradients is held to a relative L2 error of 1e-3 -- a 1 % gradient bug cannot hide behind the flips.
     # (the training forward Morton-sorts every cloud's points -- the network is permutation-invariant -- so the masks' rows are in
     # that order: the pinned oracle run gets the same sorted clouds; its gradients do not depend on the order)
-    srt = H.pkg("ops").morton_sort(torch.from_numpy(np.concatenate([q, pos, neg, oth], axis=1)[0]).to(dev)).cpu().numpy()[None]
-    assert np.array_equal(np.sort(srt.reshape(ncl, n * 3), axis=1), np.sort(pcs.reshape(ncl, n * 3), axis=1))
+    # (the step's rows are query-major: the nq x ncl clouds in the order of the (nq, ncl, n, 3) concatenation)
+    cat = np.concatenate([q, pos, neg, oth], axis=1).reshape(nq * ncl, n, 3)
+    srt = H.pkg("ops").morton_sort(torch.from_numpy(cat).to(dev)).cpu().numpy().reshape(nq, ncl, n, 3)
+    assert np.array_equal(np.sort(srt.reshape(nq * ncl, n * 3), axis=1), np.sort(pcs.reshape(nq * ncl, n * 3), axis=1))
     pin = T.train_step(w0, srt[:, :1], srt[:, 1:3], srt[:, 3:3 + nneg], srt[:, 3 + nneg:], step=step0, epoch=epoch, arch=arch,
-                       relu_masks=masks)
+                       relu_masks=masks, batch_num_queries=nq, decay_step=decay_step)
     flips = sum(pin["relu_mask_disagreement"].values())
     total = sum(int(np.prod(m.shape)) for m in masks.values())
     assert flips <= 2e-5 * total, "the HIP forward's ReLU masks differ from the float64 forward's in %d of %d elements" % (flips, total)
@@ -135,10 +203,10 @@ def test_train_step_matches_gradient_oracle(dev, arch, nneg, n):
         rel_l2 = np.linalg.norm(g - g_ref) / np.linalg.norm(g_ref)
         worst_pin = max(worst_pin, (rel_l2, k))
         assert rel_l2 <= 1e-3, "mask-pinned gradient of %s: relative L2 error %.3e" % (k, rel_l2)
-    print("train step %s %dx%d, ReLU masks pinned (%d of %d elements differ from the float64 forward's): worst gradient "
-          "relative L2 error %.2e (%s)" % (arch, ncl, n, flips, total, worst_pin[0], worst_pin[1]))
-    print("train step %s %dx%d: worst gradient relative L2 error %.2e (%s)%s" % (
-        arch, ncl, n, worst[0], worst[1],
+    print("train step %s %dx%dx%d, ReLU masks pinned (%d of %d elements differ from the float64 forward's): worst gradient "
+          "relative L2 error %.2e (%s)" % (arch, nq, ncl, n, flips, total, worst_pin[0], worst_pin[1]))
+    print("train step %s %dx%dx%d: worst gradient relative L2 error %.2e (%s)%s" % (
+        arch, nq, ncl, n, worst[0], worst[1],
         "; float32 torch on the same tensor: %.2e" % noise[worst[1]][1] if noise else ""))
     # Moving averages are updated by the same run and must match tightly.  Adam-updated weights: the first steps of
     # Adam are sign-like (update ~ 3.2 lr sign(g)), so an element whose gradient sits at the f32 noise floor may move by
@@ -230,34 +298,54 @@ def test_op_level_conv1d_and_g_vlad_api(dev):
 
 def test_graphed_step_equals_eager_step(dev):
     """step(graph=True) replays one captured HIP graph per step; schedule values are device-resident, so several replays
-    (different learning rates / bias corrections / BN decays / inputs) track the eager steps."""
+    (different learning rates / bias corrections / BN decays / inputs) track the eager steps.  One query, and two (BATCH_NUM_QUERIES = 2:
+    BatchNorm over 2 x 10 clouds, bn_decay from floor(step B / DECAY_STEP)) with the four inputs as slices of ONE (2, 10, n, 3) tensor --
+    the replay copies the joined buffer once (training._joined_along_dim1) -- and as four separate tensors."""
     TR = H.pkg("training")
     arch, n = "epc-net-l", 256
     w0 = O.seeded_weights(arch, 4)
-    params = dict(H.PARAMS, ARCH=arch, BATCH_NUM_QUERIES=1, DECAY_STEP=4, BASE_LEARNING_RATE=1e-3, MARGIN_1=0.5, MARGIN_2=0.2)
-    to = lambda a: torch.from_numpy(a).to(dev)
-    out = []
-    for use_graph in (False, True):
-        st = H.make_store(arch, w0, dev)
-        ts = TR.TrainStep(params, st, outer=H.OUTER)
-        losses = []
-        for i in range(4):
-            pcs = O.synthetic_clouds(10, n, 30 + i)
-            q, pos, neg, oth = to(pcs[None, :1]), to(pcs[None, 1:3]), to(pcs[None, 3:9]), to(pcs[None, 9:])
-            loss, lr, bd = ts.step(q, pos, neg, oth, epoch=5 * i, graph=use_graph)      # lr and bn_decay change every step
-            losses.append(float(loss))
-        out.append((losses, {k: v.detach().cpu().numpy().copy() for k, v in st.vars.items()}, ts.global_step))
-    (l0, w_e, s0), (l1, w_g, s1) = out
-    assert s0 == s1 == 4
-    # The step is deterministic since round 3 (ordered split-K, sorted transposed lists, ordered reductions) and a replayed HIP graph
-    # launches the same kernels on the same buffers as the eager step: losses and every variable are the same BITS.
-    assert l0 == l1, (l0, l1)
-    for k in w_e:
-        assert np.array_equal(w_e[k], w_g[k]), k
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    for nq, joined in ((1, False), (2, True), (2, False)):
+        params = dict(H.PARAMS, ARCH=arch, BATCH_NUM_QUERIES=nq, DECAY_STEP=4, BASE_LEARNING_RATE=1e-3, MARGIN_1=0.5, MARGIN_2=0.2)
+        out = []
+        for use_graph in (False, True):
+            st = H.make_store(arch, w0, dev)
+            ts = TR.TrainStep(params, st, outer=H.OUTER)
+            losses, decays = [], []
+            for i in range(4):
+                pcs = O.synthetic_clouds(nq * 10, n, 30 + i).reshape(nq, 10, n, 3)
+                if joined:
+                    t = to(pcs)
+                    q, pos, neg, oth = t[:, :1], t[:, 1:3], t[:, 3:9], t[:, 9:]
+                    assert TR._joined_along_dim1([q, pos, neg, oth]) is not None
+                else:
+                    q, pos, neg, oth = to(pcs[:, :1]), to(pcs[:, 1:3]), to(pcs[:, 3:9]), to(pcs[:, 9:])
+                    assert nq == 1 or TR._joined_along_dim1([q, pos, neg, oth]) is None
+                loss, lr, bd = ts.step(q, pos, neg, oth, epoch=5 * i, graph=use_graph)      # lr and bn_decay change every step
+                losses.append(float(loss))
+                decays.append(bd)
+            out.append((losses, {k: v.detach().cpu().numpy().copy() for k, v in st.vars.items()}, ts.global_step, decays))
+        (l0, w_e, s0, d0), (l1, w_g, s1, d1) = out
+        assert s0 == s1 == 4
+        assert d0 == d1 == [min(0.99, 1 - 0.5 * 0.5 ** (i * nq // 4)) for i in range(4)], d0
+        # The step is deterministic since round 3 (ordered split-K, sorted transposed lists, ordered reductions) and a replayed HIP graph
+        # launches the same kernels on the same buffers as the eager step: losses and every variable are the same BITS.
+        assert l0 == l1, (nq, joined, l0, l1)
+        for k in w_e:
+            assert np.array_equal(w_e[k], w_g[k]), (nq, joined, k)
 
 
-@pytest.mark.parametrize("n,nneg", [(256, 14), (256, 18), (4096, 14), (4096, 18)])
-def test_bf16_precision_step_matches_the_operand_rounded_oracle(dev, n, nneg):
+@pytest.mark.parametrize("n,nneg,nq,case", [pytest.param(256, 14, 1, None, id="256-14"), pytest.param(256, 18, 1, None, id="256-18"),
+                                            pytest.param(4096, 14, 1, None, id="4096-14"), pytest.param(4096, 18, 1, None, id="4096-18"),
+                                            # 32 clouds: the per-cloud 128-row assignment product with its moments, the 128-row dcat
+                                            # product, the fused hidden projection at M = 128, the fused tail at B = 32 (its gating weight
+                                            # gradient rounds: bf16_product_rule)
+                                            pytest.param(4096, 12, 2, dict(proj=True, tail=True, assign=4, dx=4), id="4096-2x16"),
+                                            # 44 clouds: 352 chain workgroups; the per-op tail, whose 256 x 256 weight gradients (K = 44)
+                                            # take the bf16 matrix-pipe GEMM; ops.Linear for the hidden projection; the 128-row dcat product
+                                            pytest.param(4096, 18, 2, dict(proj=False, tail=False, persist=False, parts=352, tiles=16,
+                                                                           parts_over_cus=True, assign=3, dx=4), id="4096-2x22")])
+def test_bf16_precision_step_matches_the_operand_rounded_oracle(dev, n, nneg, nq, case):
     """params["TRAIN_PRECISION"] = "bf16" (BASELINE.json configs[2]: bf16 activations of the (rows, 1024) head, one bf16 value per GEMM
     operand, f32 accumulation, statistics and master weights) at 18 clouds (the reference's tuple, configs/epc-net.yaml:28-34) and 22
     (BASELINE.json's "18 neg"), against the float64 oracle with the SAME rounding points (epcnet_oracle_torch._RoundedMatmul for the
@@ -268,10 +356,11 @@ def test_bf16_precision_step_matches_the_operand_rounded_oracle(dev, n, nneg):
     TR, ops, TFU = H.pkg("training"), H.pkg("ops"), H.pkg("utils.tf_util")
     ncl = 1 + 2 + nneg + 1
     w0 = O.seeded_weights("epc-net", 4)
-    pcs = O.synthetic_clouds(ncl, n, 9)
-    tup = [torch.from_numpy(a).to(dev) for a in (pcs[None, :1], pcs[None, 1:3], pcs[None, 3:3 + nneg], pcs[None, 3 + nneg:])]
+    pcs = O.synthetic_clouds(nq * ncl, n, 9).reshape(nq, ncl, n, 3)
+    tup = [torch.from_numpy(a).to(dev) for a in (pcs[:, :1], pcs[:, 1:3], pcs[:, 3:3 + nneg], pcs[:, 3 + nneg:])]
     st = H.make_store("epc-net", w0, dev)
-    params = dict(H.PARAMS, ARCH="epc-net", BATCH_NUM_QUERIES=1, TRAIN_PRECISION="bf16")
+    decay_step = 200000 if nq == 1 else 4                   # (two queries: bn_decay 0.75 at step 3, where one query gives 0.5)
+    params = dict(H.PARAMS, ARCH="epc-net", BATCH_NUM_QUERIES=nq, TRAIN_PRECISION="bf16", DECAY_STEP=decay_step)
     ts = TR.TrainStep(params, st, outer=H.OUTER)
     ts.global_step = 3
     grads = {}
@@ -287,22 +376,31 @@ def test_bf16_precision_step_matches_the_operand_rounded_oracle(dev, n, nneg):
     ops.adam_multi = spy
     TFU.RELU_MASK_TAPS, TFU.VALUE_TAPS = {}, {}
     try:
-        loss, _, _ = ts.step(*tup, epoch=7)
+        if case is None:
+            loss, _, bn_decay = ts.step(*tup, epoch=7)
+        else:
+            (loss, _, bn_decay), kernels = H.launched_kernels(lambda: ts.step(*tup, epoch=7))
     finally:
         ops.adam_multi = orig
         masks, TFU.RELU_MASK_TAPS = TFU.RELU_MASK_TAPS, None
         pins, TFU.VALUE_TAPS = TFU.VALUE_TAPS, None
     assert ops._GEMM_PRECISION == "bf16x6", "the step must restore the process-wide setting"
+    assert bn_decay == (0.5 if nq == 1 else 0.75)
+    _assert_reaches(case, st, nq, ncl, n, "u16", kernels if case is not None else {})
     masks = {k[len(H.OUTER) + 1:]: v.cpu().numpy() for k, v in masks.items()}
     pins = {k[len(H.OUTER) + 1:]: v.cpu().numpy() for k, v in pins.items()}
     assert len(masks) == 13 and len(pins) == 13, (sorted(masks), sorted(pins))
-    # the loss's selections (closest positive, hardest negatives: argmin / argmax over descriptors of random clouds, a rounding apart
-    # from each other) are made on the HIP step's descriptors: one more value pin
+    # one more value pin: the HIP step's descriptors.  The loss's selections (closest positive, hardest negatives: argmin / argmax over
+    # descriptors of random clouds, a rounding apart from each other) are made on them, and its gradient is formed at their values: it
+    # is made of differences of nearly equal descriptors, which amplify the last layers' arithmetic and carry it into every tensor alike
+    # (the descriptors' own gap is value_pin_gap["descriptors"], held below with the layers')
     aux = ts.last_aux
     pins["descriptors"] = torch.cat([aux["q_vec"], aux["pos_vecs"], aux["neg_vecs"], aux["other_neg_vec"]], 1).double().cpu().numpy()
-    srt = ops.morton_sort(torch.from_numpy(pcs).to(dev)).cpu().numpy()[None]
+    srt = ops.morton_sort(torch.from_numpy(pcs.reshape(nq * ncl, n, 3)).to(dev)).cpu().numpy().reshape(nq, ncl, n, 3)
     sp = (srt[:, :1], srt[:, 1:3], srt[:, 3:3 + nneg], srt[:, 3 + nneg:])
-    ref = T.train_step(w0, *sp, step=3, epoch=7, arch="epc-net", relu_masks=masks, gemm_rounding="bf16", value_pins=pins)
+    ref = T.train_step(w0, *sp, step=3, epoch=7, arch="epc-net", relu_masks=masks, gemm_rounding="bf16", value_pins=pins, batch_num_queries=nq,
+                       decay_step=decay_step)
+    assert ref["bn_decay"] == bn_decay
     flips = sum(ref["relu_mask_disagreement"].values())
     total = sum(int(np.prod(m.shape)) for m in masks.values())
     gap = max(ref["value_pin_gap"].values())
@@ -338,10 +436,10 @@ def test_bf16_precision_step_matches_the_operand_rounded_oracle(dev, n, nneg):
             alpha = float(np.vdot(g_ref, g) / np.vdot(g_ref, g_ref))
             alphas.append((abs(alpha - 1.0), k))
     total_rel = np.sqrt(num / den)
-    print("bf16 step %dx%d: loss %.6f vs oracle %.6f, all gradients relative L2 error %.2e, worst large tensor %.2e (%s), worst tensor %.2e "
-          "(%s), %d of %d mask elements differ, largest value-pin gap %.2e" % (ncl, n, float(loss), ref["loss"], total_rel, max(big)[0],
+    print("bf16 step %dx%dx%d: loss %.6f vs oracle %.6f, all gradients relative L2 error %.2e, worst large tensor %.2e (%s), worst tensor %.2e "
+          "(%s), %d of %d mask elements differ, largest value-pin gap %.2e" % (nq, ncl, n, float(loss), ref["loss"], total_rel, max(big)[0],
                                                                                  max(big)[1], worst[0], worst[1], flips, total, gap))
-    print("bf16 step %dx%d: |alpha - 1| of the %d large tensors: %s" % (ncl, n, len(alphas), ", ".join("%s %.1e" % (k, a) for a, k in sorted(alphas, reverse=True))))
+    print("bf16 step %dx%dx%d: |alpha - 1| of the %d large tensors: %s" % (nq, ncl, n, len(alphas), ", ".join("%s %.2e" % (k, a) for a, k in sorted(alphas, reverse=True))))
     assert max(alphas)[0] <= BF16_STEP_ALPHA_BAR, "bf16 step: the gradient of %s is systematically off (alpha - 1 = %.3e)" % (max(alphas)[1], max(alphas)[0])
     assert total_rel <= BF16_STEP_BAR_ALL, "bf16 step, all gradients: relative L2 error %.3e" % total_rel
     assert max(big)[0] <= BF16_STEP_BAR_LARGE[n], "bf16 step, gradient of %s: relative L2 error %.3e against the oracle with the same rounding points" % (max(big)[1], max(big)[0])
