@@ -18,13 +18,9 @@
 // switch between the row layout and the MFMA layout.
 #include "common.h"
 
-#ifndef BLK_WAVES
 #define BLK_WAVES 12  // f32 kernel: 12 x 8.7 KB staging tiles + the 49-KB weight pack = 154 KB (3 waves per SIMD)
-#endif
 #define BLK_THREADS (64 * BLK_WAVES)
-#ifndef BLK_PERSIST_MAX_ROUNDS
 #define BLK_PERSIST_MAX_ROUNDS 4096   // grids of up to this many rounds of short workgroups run as one persistent workgroup per CU (i.e. always)
-#endif
 #define ST_STRIDE 68  // floats per staged row: 64 + 4 pad -> conflict-free b128 reads in both layouts
 #define BLK_PACK EPC_BLOCK_PACK_FLOATS
 #define BLK_PACK_S EPC_BLOCK_PACK_FLOATS_S   // f32 kernel: the three layers' inverse column scales follow the layer packs
@@ -241,31 +237,16 @@ __global__ __launch_bounds__(BLK_THREADS) void proxyconv_block_kernel(
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const int g = g0 + 4 * s + p;
-#ifdef BLK_ABL_NOIDX   // timing only
-        const int c = 20;
-#else
         const int c = cnt[g];
-#endif
         const bool ovf = c > cap;
         // every row holds >= 20 valid entries (cnt >= 20 by construction); ties beyond 20 are the rare tail
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         if (!ovf) {
             int nb[EPC_KNN_SELECT];
-#ifdef BLK_ABL_NOIDX
-#pragma unroll
-            for (int m = 0; m < EPC_KNN_SELECT; ++m) nb[m] = 0;
-#else
             load_nb20(reinterpret_cast<const char*>(idx), (unsigned)(wg0 + 4 * s + p), cap, u16, nb);
-#endif
             float4 v[EPC_KNN_SELECT];
 #pragma unroll
-#ifdef BLK_ABL_LDSGATHER   // timing only: every neighbour row read from LDS (the weight pack's bytes stand in for a row cache)
-            for (int m = 0; m < EPC_KNN_SELECT; ++m) v[m] = ld4(lds + (((unsigned)nb[m] % 180u) * 64 + q * 4));
-#elif defined(BLK_ABL_NOGATHER)   // timing only: every neighbour row = the point's own row (L1-resident after the first)
-            for (int m = 0; m < EPC_KNN_SELECT; ++m) v[m] = row32(g - cloud_base + 0 * nb[m]);
-#else
             for (int m = 0; m < EPC_KNN_SELECT; ++m) v[m] = row32(nb[m]);
-#endif
 #pragma unroll
             for (int m = 0; m < EPC_KNN_SELECT; ++m) {  // ascending j, one rounding per add
                 acc.x += v[m].x;
@@ -317,17 +298,10 @@ __global__ __launch_bounds__(BLK_THREADS) void proxyconv_block_kernel(
     f16x8 bh[4], bl[4];
     f32x16 a1[2], a2[2];
     float inv_row = stage_to_bop(st, bh, bl, lane);
-#ifdef BLK_ABL_NOLAYERS   // timing only
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a2[t][r] = inv_row + (float)r;
-#else
     layer_s64(wa, ba, tia, bh, bl, inv_row, a1, lane);
     relu16(a1[0]);
     relu16(a1[1]);
     layer_acc64(wb, bb, tib, a1, a2, lane);
-#endif
     relu16(a2[0]);
     relu16(a2[1]);
 
@@ -424,10 +398,8 @@ __device__ __forceinline__ void stage16_to_bop(const unsigned short* st, f16x8 (
 }
 
 // waves per workgroup of the fp16 kernel (its staging tile is 4.5 KB per wave, so more waves fit beside the 49-KB
-// weight pack than in the f32 kernel): tuned on MI355X, scripts/tune_lib.sh
-#ifndef BLK16_WAVES
+// weight pack than in the f32 kernel): tuned on MI355X
 #define BLK16_WAVES 16
-#endif
 #define BLK16_THREADS (64 * BLK16_WAVES)
 #define BLK16_LDS_BYTES (BLK_PACK * 4 + BLK16_WAVES * 32 * ST16 * 2)
 

@@ -20,7 +20,7 @@
 // through a double-buffered LDS chunk (32 output channels, 128*CIN bytes) shared by the 8 waves: LDS-DMA, ONE barrier per
 // chunk, the next chunk's pieces in flight under this chunk's MFMAs.
 //
-// Schedule.  In-kernel stamps (-DC5_STAMPS, scripts/c5_stamps.py) of the lock-step form -- every wave: chain(c), epilogue(c),
+// Schedule.  In-kernel cycle stamps (since removed; a66c05d) of the lock-step form -- every wave: chain(c), epilogue(c),
 // barrier -- showed the two waves of a SIMD serialising: the older wave wins the matrix pipe and runs its 96-MFMA chain, the
 // younger one runs its chain afterwards (beside the older one's epilogue), then its own epilogue beside NOTHING while the older
 // wave idles at the barrier (per wave: barrier wait 11 %, the un-overlapped epilogue 23 % of the cycles; matrix pipe busy 59 %
@@ -79,27 +79,6 @@ __device__ __forceinline__ f32x4v mfma16_bf16(bf16x8 a, bf16x8 b, f32x4v c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-#ifdef C5_STAMPS
-// Diagnostic build only (scripts/c5_stamps.py): per wave the shader cycles spent in each phase of the kernel, summed over the
-// 32 chunks -- [prologue, DMA issue, MFMA chain, epilogue VALU + stores, vmcnt / lgkmcnt wait, barrier, final epilogue, total].
-// The values go to a buffer of their own that nothing else reads; the product build contains no stamp.
-__device__ unsigned int c5_stamp_buf[16384][8];
-extern "C" int epc_debug_c5_stamps(void* host, size_t bytes) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(c5_stamp_buf), bytes < sizeof(c5_stamp_buf) ? bytes : sizeof(c5_stamp_buf)) == hipSuccess ? 0 : -3;
-}
-#define C5_T(var) __builtin_amdgcn_sched_barrier(0); const unsigned long long var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
-#define C5_ADD(dst, a, b) dst += (unsigned)((b) - (a))
-#else
-#define C5_T(var)
-#define C5_ADD(dst, a, b)
-#endif
-#ifndef C5_START_STAGGER
-#define C5_START_STAGGER 0   // shader cycles between the start phases of first-round workgroups (0 = none)
-#endif
-#ifndef C5_ASYM
-#define C5_ASYM 1   // 0: the lock-step schedule (every wave chain, epilogue, barrier), kept for the A/B measurement
-#endif
-
 template <int CIN>
 struct C5fLds {  // VLAD kernel; offsets in floats (4 B)
     static constexpr int W5_CHUNK = 32 * CIN;              // hi + lo fragments of 32 output channels: 128 * CIN bytes
@@ -157,10 +136,6 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
                                                                     float* __restrict__ assign_frag, float* __restrict__ apart) {
     using L = C5fLds<CIN>;
     constexpr int STEPS = CIN / 32;
-#ifdef C5_STAMPS
-    unsigned int st_dma = 0, st_mfma = 0, st_epi = 0, st_wait = 0, st_bar = 0;
-#endif
-    C5_T(t_begin);
     static_assert(C5_WAVES * L::T_WAVE <= 2 * L::W5_CHUNK, "the transpose tiles must fit in the W5 buffers");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -190,16 +165,6 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
                    lds_base + 4u * (L::OFF_WC + (c & (L::WC_SLOTS - 1)) * L::WC_CHUNK + wave_u * 256));
     };
 
-#if C5_START_STAGGER
-    // First-round workgroups start a quarter-phase apart: every workgroup's prologue is a 256-KB burst from HBM, all tiles take
-    // the same time, so without this the 256 CUs load together (4.5 TB/s bursts with the matrix pipes idle) and then compute
-    // together; a CU's later workgroups inherit its phase.
-    if (blockIdx.x < 256 && (blockIdx.x & 3)) {
-        const unsigned long long t0s = __builtin_amdgcn_s_memtime();
-        const unsigned long long d = (unsigned long long)(blockIdx.x & 3) * C5_START_STAGGER;
-        while (__builtin_amdgcn_s_memtime() - t0s < d) __builtin_amdgcn_s_sleep(32);
-    }
-#endif
     stage_chunk(0, std::integral_constant<int, 0>{});
     for (int o = tid; o < 1024; o += C5_THREADS) {
         lds[L::OFF_B5 + o] = gb5[o];
@@ -218,7 +183,6 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
     float ss[2] = {0.f, 0.f};
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    C5_T(t_pro);
 
     f32x4v acc[2][2];
     // ---- the chunk's MFMA chain: 2 x 2 accumulator tiles, STEPS k-steps, three products: 12 * STEPS MFMAs ----
@@ -332,18 +296,13 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
     };
     // One interval = everything between two chunk barriers.  `late` waves (4-7) run the epilogue of the PREVIOUS chunk before this
     // chunk's chain (see Schedule at the top of the file).
-    const bool late = C5_ASYM && wave_u >= 4;
+    const bool late = wave_u >= 4;
     auto interval = [&](int c, auto bufc) {
         constexpr int buf = decltype(bufc)::value;
-        C5_T(t0);
         if (c + 1 < 32) stage_chunk(c + 1, std::integral_constant<int, buf ^ 1>{});
-        C5_T(t1);
         if (late && c > 0) epilogue(c - 1);
-        C5_T(t2);
         chain(bufc);
-        C5_T(t3);
         if (!late) epilogue(c);
-        C5_T(t4);
         // the next chunk's LDS-DMA pieces are the OLDEST outstanding vector-memory operations of this wave; the 3 feat stores
         // issued after them may stay in flight (vmcnt counts in issue order).  Waves without stores drain everything.
         if (active && (!late || c > 0))
@@ -351,22 +310,13 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        C5_T(t5);
         __builtin_amdgcn_s_barrier();
-        C5_T(t6);
-        C5_ADD(st_dma, t0, t1);
-        C5_ADD(st_epi, t1, t2);
-        C5_ADD(st_mfma, t2, t3);
-        C5_ADD(st_epi, t3, t4);
-        C5_ADD(st_wait, t4, t5);
-        C5_ADD(st_bar, t5, t6);
     };
     for (int c = 0; c < 32; c += 2) {
         interval(c, std::integral_constant<int, 0>{});
         interval(c + 1, std::integral_constant<int, 1>{});
     }
     if (late) epilogue(31);
-    C5_T(t_loop);
 
     if (active) {
         // per-point inverse norm (models/epc-net.py:148): the point's 1024 squares sit in its four q lanes
@@ -458,18 +408,6 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
             apart[(size_t)(g0 >> 5) * 64 + 32 + j] = asum[1];
         }
     }
-#ifdef C5_STAMPS
-    {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        C5_T(t_end);
-        const unsigned wv = blockIdx.x * C5_WAVES + wave;
-        if (lane == 0 && wv < 16384) {
-            unsigned int* o = c5_stamp_buf[wv];
-            o[0] = (unsigned)(t_pro - t_begin), o[1] = st_dma, o[2] = st_mfma, o[3] = st_epi, o[4] = st_wait, o[5] = st_bar;
-            o[6] = (unsigned)(t_end - t_loop), o[7] = (unsigned)(t_end - t_begin);
-        }
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

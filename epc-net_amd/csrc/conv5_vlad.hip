@@ -185,7 +185,6 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_kernel(const float* __restri
         // instruction takes 8 as well) -- the lo term is a 2^-11 correction, so 4 significant bits on each side keep it
         // to 2^-15 of the product.  Block scales: byte ks of the lanes' scale dwords (op_sel).
         const float* wl = w5 + L::W5_LO8;
-#ifndef CONV5_ABL_NO_LO
         const int wsc = __float_as_int(w5[L::W5_LOSC + lane]);
         auto lo_step = [&](auto ksc) {
             constexpr int ks = decltype(ksc)::value;
@@ -202,14 +201,12 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_kernel(const float* __restri
         lo_step(std::integral_constant<int, 2>{});
         lo_step(std::integral_constant<int, 3>{});
         static_assert(CIN / 64 <= 4, "one scale dword holds four block scales");
-#endif
-        // fragment reads run C5_PF k-steps ahead of the MFMAs that consume them: eight waves share the LDS port, so a
+        // fragment reads run PF k-steps ahead of the MFMAs that consume them: eight waves share the LDS port, so a
         // read returns after ~8 other 1-KB reads (64+ cycles) while a k-step's MFMA takes 32 -- with one read in flight
-        // per wave the port idles
-#ifndef C5_PF
-#define C5_PF 1   // measured 1, 2, 3, 4, 6: 0.258-0.260 ms alike, so the shallowest (fewest registers) stays
-#endif
-        constexpr int PF = C5_PF < STEPS ? C5_PF : STEPS - 1;
+        // per wave the port idles.  Depths 1, 2, 3, 4, 6 measured 0.258-0.260 ms alike, so the shallowest (fewest
+        // registers) stays.
+        constexpr int PF = 1;
+        static_assert(PF < STEPS, "the ring holds PF + 1 k-steps");
         constexpr int RING = PF + 1;
         f16x8 fa[RING];
 #pragma unroll
@@ -230,63 +227,45 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_kernel(const float* __restri
             const int vb = __float_as_int(a);
             acc[r] = __int_as_float(vb > 0 ? vb : 0) * kDescale;
         }
-#ifdef C5_ABL_NOEPI
-        constexpr bool kEpi = false;
-        asm volatile("" :: "v"(acc));
-#else
-        constexpr bool kEpi = true;
-#endif
-        if constexpr (kEpi) {
-            const float* wc = lds + L::OFF_WC + (c & (L::WC_SLOTS - 1)) * L::WC_CHUNK;
-            // The cluster weights are ONE fp16 value each (x 2^8): the soft assignment only enters through a softmax whose
-            // logits tolerate a 2^-12 weight rounding -- emulated descriptor effect 5e-9 on top of the 9.4e-7 of the
-            // two-product conv5 -- so the lo product of the hi+lo form is not spent here.
-            auto wfrag = [&](int sp, int t) { return ldfrag16(wc + ((sp * 2 + t) * 64 + lane) * 4); };
-            // cluster-weight fragments of k-step 0: issued now, they land under the VALU work below
-            f16x8 wf[2];
-            wf[0] = wfrag(0, 0), wf[1] = wfrag(0, 1);
+        const float* wc = lds + L::OFF_WC + (c & (L::WC_SLOTS - 1)) * L::WC_CHUNK;
+        // The cluster weights are ONE fp16 value each (x 2^8): the soft assignment only enters through a softmax whose
+        // logits tolerate a 2^-12 weight rounding -- emulated descriptor effect 5e-9 on top of the 9.4e-7 of the
+        // two-product conv5 -- so the lo product of the hi+lo form is not spent here.
+        auto wfrag = [&](int sp, int t) { return ldfrag16(wc + ((sp * 2 + t) * 64 + lane) * 4); };
+        // cluster-weight fragments of k-step 0: issued now, they land under the VALU work below
+        f16x8 wf[2];
+        wf[0] = wfrag(0, 0), wf[1] = wfrag(0, 1);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) ss += acc[r] * acc[r];
-            // accumulators -> fp16 B fragments: k-step s' = registers 8s' .. 8s'+7 (k order: common.h, Wcp).  The same
-            // fragment is the assignment GEMM's operand and what is stored.
+        for (int r = 0; r < 16; ++r) ss += acc[r] * acc[r];
+        // accumulators -> fp16 B fragments: k-step s' = registers 8s' .. 8s'+7 (k order: common.h, Wcp).  The same
+        // fragment is the assignment GEMM's operand and what is stored.
 #pragma unroll
-            for (int sp = 0; sp < 2; ++sp) {
-                f16x8 fs;
+        for (int sp = 0; sp < 2; ++sp) {
+            f16x8 fs;
 #pragma unroll
-                for (int q = 0; q < 8; ++q) fs[q] = (_Float16)acc[8 * sp + q];
-#ifndef C5_ABL_NOSTORE
-                // feat leaves the kernel as ONE fp16 fragment per accumulator half (accumulator order: lane = point,
-                // element q = channel 32c + 16sp + 8(q>>2) + 4h + (q&3)): 1 KB per wave-instruction, 2 B per value; the
-                // aggregate kernel scales by rnorm and transposes.  (fp16 keeps 11 significant bits of a value that is
-                // then averaged over the cloud's points: measured descriptor effect 7e-7)
-                if (active) {
-                    float* fdst = feat + ((size_t)(g0 >> 5) * 32 + c) * 512 + lane * 4;
-                    *reinterpret_cast<u32x4*>(fdst + sp * 256) = __builtin_bit_cast(u32x4, fs);
-                }
-#endif
-                f16x8 wn[2];
-                if (sp == 0) wn[0] = wfrag(1, 0), wn[1] = wfrag(1, 1);
-#ifndef C5_ABL_NOASSIGN
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    P[t] = mfma_f16(wf[t], fs, P[t]);
-                }
-#else
-                asm volatile("" :: "v"(fs), "v"(wf[0]), "v"(wf[1]));
-#endif
-                if (sp == 0) wf[0] = wn[0], wf[1] = wn[1];
+            for (int q = 0; q < 8; ++q) fs[q] = (_Float16)acc[8 * sp + q];
+            // feat leaves the kernel as ONE fp16 fragment per accumulator half (accumulator order: lane = point,
+            // element q = channel 32c + 16sp + 8(q>>2) + 4h + (q&3)): 1 KB per wave-instruction, 2 B per value; the
+            // aggregate kernel scales by rnorm and transposes.  (fp16 keeps 11 significant bits of a value that is
+            // then averaged over the cloud's points: measured descriptor effect 7e-7)
+            if (active) {
+                float* fdst = feat + ((size_t)(g0 >> 5) * 32 + c) * 512 + lane * 4;
+                *reinterpret_cast<u32x4*>(fdst + sp * 256) = __builtin_bit_cast(u32x4, fs);
             }
+            f16x8 wn[2];
+            if (sp == 0) wn[0] = wfrag(1, 0), wn[1] = wfrag(1, 1);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                P[t] = mfma_f16(wf[t], fs, P[t]);
+            }
+            if (sp == 0) wf[0] = wn[0], wf[1] = wn[1];
         }
     };
     // the next chunk's LDS-DMA pieces are the OLDEST outstanding vector-memory operations of this wave; the 2 feat stores
     // issued after them may stay in flight (vmcnt counts in issue order).  Waves without stores (tail of the grid) drain
     // everything.
     auto chunk_wait = [&]() {
-#ifdef C5_ABL_NOSTORE
-        if (false)
-#else
         if (active)
-#endif
             asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -296,15 +275,11 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_kernel(const float* __restri
     // 0.32 vs 0.31 ms; a one-wave-per-SIMD, two-tiles-per-wave form with a software-pipelined epilogue, 0.50-0.52 vs 0.48 ms)
     auto do_chunk = [&](int c, auto bufc) {
         constexpr int buf = decltype(bufc)::value;
-#ifndef C5_ABL_NODMA
         if (c + 1 < 32) stage_chunk(c + 1, std::integral_constant<int, buf ^ 1>{});
-#endif
         chunk_mfma(c, bufc);
         chunk_epi(c);
         chunk_wait();
-#ifndef C5_ABL_NOBARRIER
         __builtin_amdgcn_s_barrier();
-#endif
     };
     for (int c = 0; c < 32; c += 2) {
         do_chunk(c, std::integral_constant<int, 0>{});

@@ -49,9 +49,7 @@ __global__ __launch_bounds__(256) void vlad_fold_kernel(const float* __restrict_
 // ---- H2: Yp[slice][row][256] = U[row][slice*HSL .. +HSL] @ H[slice*HSL .. +HSL][256]  (split-K, f32 MFMA) --------
 // HSL = 128 k per slice: a wave's serial work is 128 f32 MFMAs (4 us) and 2 rounds of 8 k-steps of loads; with 64 rows
 // (clouds) there are only two row tiles per column tile, so the K split is what fills the chip (1024 waves).
-#ifndef HSL
 #define HSL 128
-#endif
 // One wave per (32-column tile, K slice, 64-row group).  A (row on lane) is read as float4 along K: k-step (q,c) takes
 // k = 8q + c from lane-half 0 and k = 8q + 4 + c from lane-half 1; B rows are read to match.
 __global__ __launch_bounds__(64) void hidden_gemm_kernel(const float* __restrict__ U, const float* __restrict__ H,

@@ -109,12 +109,8 @@ __device__ __forceinline__ ChBnRegs ch_bn_begin(const ChBn& bn, int rows, double
         for (int u = 0; u < CH_POOL_CHUNK; ++u) {
             const int t = min(t0 + nslices * u, bn.parts - 1);
             const float* p = bn.stats + (size_t)t * 192 + 4 * cq;
-#ifdef CH_ABL_NOLOAD
-            v1[u] = v2[u] = vp[u] = make_float4((float)t, 1.f, 2.f, (float)cq);
-#else
             v1[u] = *reinterpret_cast<const float4*>(p), v2[u] = *reinterpret_cast<const float4*>(p + 64);
             vp[u] = *reinterpret_cast<const float4*>(p + 128);
-#endif
         }
 #pragma unroll
         for (int u = 0; u < CH_POOL_CHUNK; ++u) {
@@ -125,15 +121,11 @@ __device__ __forceinline__ ChBnRegs ch_bn_begin(const ChBn& bn, int rows, double
                             pv[4] = {vp[u].x, vp[u].y, vp[u].z, vp[u].w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-#ifdef CH_ABL_NOMATH
-                    N[q] += nt, A[q] += (double)(s1[q] + s2[q] + pv[q]);
-#else
                     if (first) PL[q] = (double)pv[q];
                     const double d = (double)pv[q] - PL[q];
                     N[q] += nt;
                     A[q] += (double)s1[q] + nt * d;
                     B[q] += (double)s2[q] + 2.0 * d * (double)s1[q] + nt * d * d;
-#endif
                 }
                 first = false;
             }

@@ -9,29 +9,38 @@
 // kernel boundary per dependency: 33 launches whose 14-20 us are mostly launch gap (4.2 us), the pooling of 256 moment partials
 // by every workgroup (5 us) and the re-read of a (rows, 64) tensor the previous launch has just written.  Here ONE workgroup per CU
 // keeps its rows for the whole pass: a wave owns one 32-row tile, the tile handed to the next layer stays in the wave's LDS tile,
-// and a dependency costs a barrier (2.3 us) with the moments reduced in two levels on the way through it.
+// and a dependency costs a barrier with the moments reduced in two levels on the way through it.
 //
 // The barrier (scripts/probe/grid_barrier_probe{,2}.hip have the measurements this design follows).  The textbook form -- agent-scope
 // release fence, atomic, poll, acquire fence -- costs 6-10 us bare and 24-35 us behind 72 KB of freshly written rows per workgroup
 // on this chip: every workgroup's `buffer_wbl2` walks its XCD's whole L2, and 256 pollers of one word queue behind the arrivals at
-// the memory side.  This one needs NO cache maintenance:
-//   * whatever ANOTHER workgroup will read inside the launch (the next block's z0 rows, the backward's s rows, every partial) is
-//     stored WRITE-THROUGH (`global_store ... sc1`, agent scope): once the store has completed (s_waitcnt vmcnt(0)) it is where
-//     every XCD's L2 misses go;
+// the memory side.  This one needs NO cache maintenance and no counter: the moment partials are the barrier.
+//   * whatever ANOTHER workgroup will read inside the launch (the next block's z0 rows, every partial) is stored WRITE-THROUGH
+//     (`global_store ... sc1`, agent scope): once the store has completed (s_waitcnt vmcnt(0)) it is where every XCD's L2 misses go;
 //   * every such location is written exactly ONCE per launch, before its first read: no L1 or L2 can hold a stale copy of it (a
 //     launch starts with both invalidated), so readers use plain loads and the neighbour gathers keep their L2 hit rate;
-//   * arrival in two levels -- eight group counters (blockIdx & 7: under round-robin dispatch the workgroups of an XCD), the last
-//     arrival of a group bumps the global counter -- and release in two: only that last arrival polls the global counter and then
-//     publishes the epoch in its group's flag, the other 31 poll the flag.  Sync words are touched by atomics and sc1 accesses only.
-//   * the moments travel WITH the barrier: the last arrival of a group merges its group's partials (<= 32, ascending rows, double
-//     precision) into one group partial before it bumps the global counter; after the release every workgroup merges the eight
-//     group partials.  196 KB of partials per workgroup and boundary (50 MB through the L2s) become 6 KB for eight of them + 16 KB.
-// Nothing depends on WHICH workgroup arrives last: the merge order is by row range, so results are bit-reproducible.
+//   * posting: every workgroup stores its partial of the phase as 192 tagged granules in its own slot (pst_post_stats: every wave
+//     first waits for its own stores, then wave 0 merges the waves and stores the granules).  A granule is 32 payload bits and a
+//     32-bit tag in ONE 64-bit relaxed agent-scope store, so whoever sees the tag sees the payload and everything its poster wrote
+//     before;
+//   * polling, in two levels: the workgroups are split into eight groups by blockIdx & 7 (under round-robin dispatch the workgroups
+//     of an XCD), and the group's fixed leader, the workgroup with blockIdx.x < 8, polls its group's granules until every one carries
+//     the phase's tag (pst_poll), merges them in ascending row order in double precision and posts the group partial as 384 tagged
+//     granules (pst_group_reduce).  Every workgroup, the leaders included, polls the eight group partials (pst_gather_groups) and
+//     merges them in group order (pst_final_moments).  196 KB of partials per workgroup and boundary (50 MB through the L2s) become
+//     6 KB for eight leaders + 24 KB;
+//   * the tag: pst_tag = 64 x the launch sequence number + phase + 1.  pst_init reads the sequence word; the last workgroup to leave
+//     (pst_exit) and epc_chain_persist_reset() advance it.  Granules that an earlier launch left in the workspace, an abandoned one's
+//     included, carry an older sequence number and a zeroed workspace carries tag 0, so a poll never takes a stale granule for a
+//     fresh one and the partials need no clearing between launches.
+// Nothing depends on WHICH workgroup arrives last: the merge order is by row range, so results are bit-reproducible.  The cost the
+// profiles record is about 8 us per barrier: three memory-side round trips of ~2 us under load and the merges.
 //
 // Safety.  The grid is at most the CU count and the host checks with the occupancy query that every workgroup is co-resident; every
 // spin is bounded by a wall-clock budget (s_memrealtime), a time-out sets the sticky error word and every workgroup leaves at its next
-// poll; a launch that finds the error word set leaves at once.  Either way the launch leaves NaN in the concat (a row per workgroup), so
-// the loss is NaN; epc_chain_persist_status() reads the word, _reset() clears it.
+// poll; a launch that finds the error word set leaves at once.  Either way every workgroup writes NaN into one row of the f32 concat
+// (the first row of its slice) and nothing into cat_bf16.  epc_chain_persist_status() is the signal: it reads the word, _reset()
+// clears it.
 #include "train_chain_common.h"
 
 #define PST_WAVES 12                 // one 32-row tile per wave: at most 384 rows per workgroup (98 304 rows on 256 CUs)
@@ -42,13 +51,12 @@
 #define PST_W_ERR 2112
 #define PST_SYNC_WORDS 4096
 // the workspace: [sync words][workgroup partials: PST_MAX_PHASES x PST_MAX_PARTS x 192 granules][group partials: PST_MAX_PHASES x 8 x 384
-// granules][time stamps of a -DPST_STAMPS build: PST_MAX_PARTS x 64 long long]
+// granules]
 #define PST_MAX_PHASES 20
 #define PST_MAX_PARTS 512
 #define PST_WS_PARTIALS (PST_SYNC_WORDS * 4)
 #define PST_WS_GROUPS (PST_WS_PARTIALS + (size_t)PST_MAX_PHASES * PST_MAX_PARTS * 192 * 8)
-#define PST_WS_STAMPS (PST_WS_GROUPS + (size_t)PST_MAX_PHASES * 8 * 384 * 8)
-#define PST_WS_BYTES (PST_WS_STAMPS + (size_t)PST_MAX_PARTS * 64 * 8)
+#define PST_WS_BYTES (PST_WS_GROUPS + (size_t)PST_MAX_PHASES * 8 * 384 * 8)
 
 typedef float pst_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 pst_bf16x4 __attribute__((ext_vector_type(4)));
@@ -333,14 +341,6 @@ struct PstFwdArgs {
     long long budget;
 };
 
-// -DPST_STAMPS (scripts/time_chain_persist.py STAMPS=1): thread 0 of every workgroup leaves s_memrealtime stamps behind the group
-// partials of gstats ([workgroup][64] long long) -- where a phase's microseconds go and how far apart the workgroups arrive.
-#ifdef PST_STAMPS
-#define PST_STAMP() do { if (threadIdx.x == 0 && sidx < 64) stamps[sidx++] = wall_clock64(); } while (0)
-#else
-#define PST_STAMP() do { } while (0)
-#endif
-
 template <int PF>
 __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFwdArgs g) {
     extern __shared__ __attribute__((aligned(16))) float tiles_all[];   // one staging tile per wave
@@ -361,19 +361,14 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
         return;
     }
     PstCtx cx = pst_init(sync, g.budget);
-#ifdef PST_STAMPS
-    long long* stamps = reinterpret_cast<long long*>(ws + PST_WS_STAMPS) + (size_t)blockIdx.x * 64;
-    int sidx = 0;
-#endif
-    PST_STAMP();
     const int wg0 = cx.lb * g.wg_rows, tiles = min(g.wg_rows, rows - wg0 + 31) / 32;
     const int wg_rows_here = min(g.wg_rows, rows - wg0);
     float* tile = tiles_all + wave * CH_STG_FLOATS;
     const int base = wg0 + wave * 32;   // the wave's tile (wave < tiles)
     const bool have = wave < tiles;
     int phase = 0;
-    // an abandoned launch leaves NaN in the first row of the workgroup's slice of the concat: whatever consumes the result sees it
-    // (the loss is NaN) even when nobody asks epc_chain_persist_status
+    // an abandoned launch leaves NaN in the first row of the workgroup's slice of the f32 concat (cat_bf16 is not written);
+    // epc_chain_persist_status() is what reports it
     auto poison = [&]() {
         for (int o = threadIdx.x; o < g.width; o += blockDim.x) g.a.cat[(size_t)wg0 * g.width + o] = __int_as_float(0x7fc00000);
     };
@@ -395,9 +390,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
         const unsigned tag = pst_tag(cx, phase);
         __syncthreads();   // (wave 0 is done with the waves' merge in `scratch`: the polls land there)
         if (cx.leader && !pst_group_reduce<3>(cx, stats_of(phase), gstats_of(phase), tag, rows, g.wg_rows, scratch)) return false;
-        PST_STAMP();
         if (!pst_gather_groups<3>(cx, gstats_of(phase), tag, scratch)) return false;
-        PST_STAMP();
         pst_final_moments(cx, scratch, rows, g.wg_rows, bias, gamma, beta, g.a.eps, mean_out, var_out, s_mean, s_var, coef);
         phase += 1;
         return true;
@@ -435,7 +428,6 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
         __syncthreads();   // (red is scratch: the polls may overwrite it)
     }
     pst_stage_fwd_weights<PF>(g.a.blk[0].Wa, Wf);
-    PST_STAMP();
 
 #pragma unroll 1
     for (int b = 0; b < g.a.nblocks; ++b) {
@@ -445,7 +437,6 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
         const int p4 = lane >> 4, q = lane & 15;
         // ================= barrier: z0's moments =================
         if (!barrier_moments(B.in_bias, B.gamma0, B.beta0, B.mean0, B.var0)) { poison(); return; }
-        PST_STAMP();
         // ================= phase G =================
         float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f}, piv[2] = {0.f, 0.f};
         int my_rows = 0;
@@ -552,14 +543,11 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
             }
             my_rows = min(32, rows - base);
         }
-        PST_STAMP();
         pst_post_stats(s1, s2, piv, my_rows, sred, snrows, stats_of(phase) + (size_t)cx.lb * 192, pst_tag(cx, phase));
-        PST_STAMP();
         if (have) store_tile_rows(B.za);       // (after the post: under the barrier)
         pst_stage_fwd_weights<PF>(B.Wb, Wf);   // (every wave is past its products: pst_post_stats' barrier) -- under the wait
         // ================= barrier: za's moments =================
         if (!barrier_moments(B.ba, B.gamma_a, B.beta_a, B.mean_a, B.var_a)) { poison(); return; }
-        PST_STAMP();
         // ================= phase M =================
         s1[0] = s1[1] = s2[0] = s2[1] = piv[0] = piv[1] = 0.f;
         if (have) {
@@ -604,14 +592,11 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
                 }
             }
         }
-        PST_STAMP();
         pst_post_stats(s1, s2, piv, my_rows, sred, snrows, stats_of(phase) + (size_t)cx.lb * 192, pst_tag(cx, phase));
-        PST_STAMP();
         if (have) store_tile_rows(B.zb);
         if (B.W0_next) pst_stage_fwd_weights<PF>(B.W0_next, Wf);
         // ================= barrier: zb's moments =================
         if (!barrier_moments(B.bb, B.gamma_b, B.beta_b, B.mean_b, B.var_b)) { poison(); return; }
-        PST_STAMP();
         // ================= phase H =================
         s1[0] = s1[1] = s2[0] = s2[1] = piv[0] = piv[1] = 0.f;
         if (have) {
@@ -667,11 +652,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
                 }
             }
         }
-        PST_STAMP();
-        if (B.W0_next) {
-            pst_post_stats(s1, s2, piv, my_rows, sred, snrows, stats_of(phase) + (size_t)cx.lb * 192, pst_tag(cx, phase));
-            PST_STAMP();
-        }
+        if (B.W0_next) pst_post_stats(s1, s2, piv, my_rows, sred, snrows, stats_of(phase) + (size_t)cx.lb * 192, pst_tag(cx, phase));
         if (have) {   // the block's slice of the concat (and its bf16 copy) from the tile: after the post, under the barrier
             const int ln = pst_tid() & 63, p4_ = ln >> 4, q_ = ln & 15;
             float* cat_b = g.a.cat + 64 * b;

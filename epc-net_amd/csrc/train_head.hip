@@ -20,9 +20,7 @@
 // workgroup per cloud left 18 CUs moving a megabyte each (19 + 20 us); 8 x 18 workgroups: 8 + 9 us.
 #define VN_SLICES 8
 #define L2_EPS 1e-12f
-#ifndef VN_UNROLL
 #define VN_UNROLL 8     // rows of a column in flight per thread and round trip (16 and 32 measured in round 6: the step 2.02 -> 2.05 / 2.07 ms)
-#endif
 
 __device__ __forceinline__ float group_sum(float v, float (*red)[64], int c, int g) {  // sum over the 16 feature groups
     __syncthreads();
@@ -377,9 +375,7 @@ extern "C" int epc_sq_err_bwd(const float* a, const float* b, long n, int mean, 
 // ----------------------------------------------------------------------------------------------------------------
 #define VDF_WAVES 4
 #define VDF_CHUNK_U4 (8 * 2 * 64)    // u32x4 per 32-column chunk: [k-step 8][piece 2][lane 64] = 16 KB
-#ifndef VDF_NT
 #define VDF_NT 1                      // 32-column chunks per LDS stage (2 = a row's 64 columns leave as one 256-byte run: measured slower, 160 vs 136 us)
-#endif
 
 // Bp[b][chunk c][k-step s][piece][lane (i, h)][8 bf16]: value j = B[k = 16 s + 8 h + j][f = 32 c + i], B = [dvlad[b]^T ; Wc^T]
 __global__ __launch_bounds__(256) void vlad_df_pack_kernel(const float* __restrict__ dvlad, const float* __restrict__ Wc, int F,

@@ -333,20 +333,6 @@ __device__ __forceinline__ void store_fragments(const float (&v)[(BLOCKS * 128) 
 // quad: the epilogue is float4 stores -- a quarter of the store instructions of the lane = column layout, whose 64 dword stores
 // per wave made the wide-output products (conv5 forward, the VLAD feature gradient: 302 MB written) store-issue-bound.  Used for
 // plain outputs (no statistics epilogue, which wants a column per lane; no split-K; N, ldc multiples of 4).
-#ifdef GEMM_STAMPS
-// Diagnostic build only (scripts/gemm_stamps.py): per wave the shader cycles of each phase of the k-tile loop, summed over its
-// k-tiles -- [store (split + LDS writes), barrier 1, fetch issue, MFMA phase (LDS reads + products), barrier 2, epilogue, total].
-__device__ unsigned int gemm_stamp_buf[32768][8];
-extern "C" int epc_debug_gemm_stamps(void* host, size_t bytes) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(gemm_stamp_buf), bytes < sizeof(gemm_stamp_buf) ? bytes : sizeof(gemm_stamp_buf)) == hipSuccess ? 0 : -3;
-}
-#define GS_T(var) __builtin_amdgcn_sched_barrier(0); const unsigned long long var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
-#define GS_ADD(dst, a, b) dst += (unsigned)((b) - (a))
-#else
-#define GS_T(var)
-#define GS_ADD(dst, a, b)
-#endif
-
 // (the split-fp16 instantiation of the 128 x 128 tile sits at the edge of three waves per SIMD -- 163 registers; the range guard's
 // state pushed it to 179 = two waves and 189 -> 238 us on conv5's forward product -- so it is held there explicitly)
 template <int WM, int WN, int PIECES, bool SWAP = false, int G_PF = 1>
@@ -391,26 +377,15 @@ __global__ __launch_bounds__(256, (PIECES == 4 && WM == 2 && WN == 2) ? 3 : 1) v
             fetch_fragments<2 * WM>(A, g.sAm, g.sAk, m0, g.M, k0 + pf * S_BK, k1, va[pf], tid);
             fetch_fragments<2 * WN>(B, g.sBn, g.sBk, n0, g.N, k0 + pf * S_BK, k1, vb[pf], tid, g.b16 != 0);
         }
-#ifdef GEMM_STAMPS
-    unsigned st_store = 0, st_b1 = 0, st_fetch = 0, st_mfma = 0, st_b2 = 0;
-    GS_T(t_begin);
-#endif
     auto k_tile = [&](int kt, auto slotc) {
         constexpr int slot = decltype(slotc)::value;
-        GS_T(t0);
         store_fragments<2 * WM, PIECES>(va[slot], a_kc, As, tid, g.a_scale, &range_bad);
         store_fragments<2 * WN, PIECES>(vb[slot], b_kc, Bs, tid, g.b_scale, &range_bad);
-        GS_T(t1);
         __syncthreads();
-        GS_T(t2);
         if (kt + G_PF * S_BK < k1) {  // in flight under the MFMAs of this tile and of the G_PF - 1 after it
             fetch_fragments<2 * WM>(A, g.sAm, g.sAk, m0, g.M, kt + G_PF * S_BK, k1, va[slot], tid);
             fetch_fragments<2 * WN>(B, g.sBn, g.sBk, n0, g.N, kt + G_PF * S_BK, k1, vb[slot], tid, g.b16 != 0);
         }
-        GS_T(t3);
-        GS_ADD(st_store, t0, t1);
-        GS_ADD(st_b1, t1, t2);
-        GS_ADD(st_fetch, t2, t3);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             bf16x8 a[WM][NP], b[WN][NP];   // (fp16 pieces travel in the same 16-byte registers)
@@ -447,11 +422,7 @@ __global__ __launch_bounds__(256, (PIECES == 4 && WM == 2 && WN == 2) ? 3 : 1) v
                     acc[rb][cb] = c;
                 }
         }
-        GS_T(t4);
         __syncthreads();
-        GS_T(t5);
-        GS_ADD(st_mfma, t3, t4);
-        GS_ADD(st_b2, t4, t5);
     };
     // (the register slot is a compile-time constant: a runtime index would send va / vb to scratch memory)
     for (int kt = k0; kt < k1; kt += G_PF * S_BK) {
@@ -468,23 +439,6 @@ __global__ __launch_bounds__(256, (PIECES == 4 && WM == 2 && WN == 2) ? 3 : 1) v
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[rb][cb][r] *= g.descale;
     }
-#ifdef GEMM_STAMPS
-    GS_T(t_loop_end);
-    struct StampWriter {
-        unsigned a, b, c, d, e;
-        unsigned long long t0, t1;
-        int slot, lane;
-        __device__ ~StampWriter() {
-            const unsigned long long tend = __builtin_amdgcn_s_memtime();
-            if (lane == 0 && slot < 32768) {
-                gemm_stamp_buf[slot][0] = a, gemm_stamp_buf[slot][1] = b, gemm_stamp_buf[slot][2] = c, gemm_stamp_buf[slot][3] = d;
-                gemm_stamp_buf[slot][4] = e, gemm_stamp_buf[slot][5] = (unsigned)(tend - t1), gemm_stamp_buf[slot][6] = (unsigned)(tend - t0);
-                gemm_stamp_buf[slot][7] = (unsigned)(t1 - t0);
-            }
-        }
-    } stamp_writer{st_store, st_b1, st_fetch, st_mfma, st_b2, t_begin, t_loop_end,
-                   (int)(((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 + wave), lane};
-#endif
     // Column statistics of the product for a training-mode BatchNorm that follows (epc_gemm_f32_stats): per row tile and column
     // the PIVOT p = the product's value in the tile's first row, and the sums of (v - p) and (v - p)^2 over the tile's valid rows
     // (of the product without the bias).  Shifted by a value of the column itself the sums stay at the scale of the column's
@@ -617,12 +571,8 @@ __global__ __launch_bounds__(256, (PIECES == 4 && WM == 2 && WN == 2) ? 3 : 1) v
 template <int WM, int WN>
 static void launch_gemm_split(const GemmArgs& g, int batch, int pieces, hipStream_t st) {
     dim3 grid((g.N + 64 * WN - 1) / (64 * WN), (g.M + 64 * WM - 1) / (64 * WM), batch * g.splitk);
-#ifndef EPC_GEMM_NO_SWAP
     const bool swap = !g.stats && !g.partial && g.splitk == 1 && g.N % 4 == 0 && g.ldc % 4 == 0 && g.bC % 4 == 0 &&
                       (reinterpret_cast<size_t>(g.C) & 15) == 0 && (!g.bias || (reinterpret_cast<size_t>(g.bias) & 15) == 0);
-#else
-    const bool swap = false;
-#endif
     if (swap) {
         if (pieces == 1)
             hipLaunchKernelGGL((gemm_split_kernel<WM, WN, 1, true>), grid, dim3(256), 0, st, g);
@@ -632,7 +582,6 @@ static void launch_gemm_split(const GemmArgs& g, int batch, int pieces, hipStrea
             hipLaunchKernelGGL((gemm_split_kernel<WM, WN, 3, true>), grid, dim3(256), 0, st, g);
         return;
     }
-#ifndef EPC_GEMM_NO_DEEP_PREFETCH
     const int kslice = (g.K + g.splitk - 1) / g.splitk;
     if (g.splitk > 1 && kslice >= 8 * S_BK) {   // deep-K slices (dW = x^T dy over all rows): loads two k-tiles ahead
         if (pieces == 1)
@@ -643,7 +592,6 @@ static void launch_gemm_split(const GemmArgs& g, int batch, int pieces, hipStrea
             hipLaunchKernelGGL((gemm_split_kernel<WM, WN, 3, false, 2>), grid, dim3(256), 0, st, g);
         return;
     }
-#endif
     if (pieces == 1)
         hipLaunchKernelGGL((gemm_split_kernel<WM, WN, 1>), grid, dim3(256), 0, st, g);
     else if (pieces == 2)
@@ -754,7 +702,6 @@ static int gemm_impl(const float* A, const float* B, float* C, const float* bias
             return EPC_OK;
         }
     }
-#ifndef EPC_GEMM_F32_ONLY
     // sides of at least 64: the split-bf16 kernel with the tile that fits; short sides stay on the f32 MFMA kernel
     if (M >= 64 && N >= 64 && K >= 32) {
         const bool bigm = M >= 128, bign = N >= 128;
@@ -765,7 +712,6 @@ static int gemm_impl(const float* A, const float* B, float* C, const float* bias
         EPC_CHECK_LAUNCH();
         return finish();
     }
-#endif
     dim3 grid((N + G_BN - 1) / G_BN, (M + G_BM - 1) / G_BM, batch * splitk);
     hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, st, g);
     EPC_CHECK_LAUNCH();
@@ -946,7 +892,6 @@ static int gemm_stats_impl(const float* A, const float* B, float* C, const float
     const int tiles = epc_gemm_stats_tiles(M);
     EPC_CHECK_ARG(stats_floats >= (size_t)tiles * 3 * N, "statistics buffer too small (epc_gemm_stats_tiles(M) * 3 * N floats)");
     hipStream_t st = (hipStream_t)stream;
-#ifndef EPC_NO_THIN_FORWARD
     if (pieces == 3 && N == 64 && K == 64 && sAm == 64 && sAk == 1 && sBk == 64 && sBn == 1 && ldc == 64 &&
         ((reinterpret_cast<size_t>(A) | reinterpret_cast<size_t>(C)) & 15) == 0) {
         // the thin layers: one pass, one partial per 256 rows (fewer than the tiles the caller sized `stats` for)
@@ -958,7 +903,6 @@ static int gemm_stats_impl(const float* A, const float* B, float* C, const float
         EPC_CHECK_LAUNCH();
         return EPC_OK;
     }
-#endif
     GemmArgs g{A, B, C, bias, M, N, K, sAm, sAk, sBk, sBn, ldc, 0, 0, 0, 1, 0, stats, nullptr};
     g.a_scale = a_scale, g.b_scale = b_scale, g.descale = 1.0f / (a_scale * b_scale);
     const bool bigm = M >= 128, bign = N >= 128;
@@ -1151,9 +1095,7 @@ __global__ __launch_bounds__(256) void linear_stats64_kernel(const float* __rest
 //                                           -> out0 = dbeta, out1 = dgamma            (BatchNorm backward)
 // C must be a multiple of 4 (every BatchNorm site of the network has 64, 256 or 1024 channels).
 // ----------------------------------------------------------------------------------------------------------------
-#ifndef CR_ROWS
 #define CR_ROWS 256      // rows per workgroup
-#endif
 #define CR_COUNTERS 64   // counter slots at the head of the workspace: C <= 4096
 
 
@@ -1836,20 +1778,17 @@ extern "C" int epc_bn_apply_bwd_given(const float* dy, const float* z, const flo
 // every row) one kernel does the rest: a wave takes 32 rows at a time and
 //   * forms dz = gamma rstd (dy [z-mask] - dbeta/rows - zhat dgamma/rows) in registers, in the row layout (lane = row, eight
 //     consecutive channels per k-step) -- which IS the B operand of dx^T = W dz^T: dx leaves as whole float4s per lane;
-//   * forms dz again in the column layout (lane = channel, eight consecutive ROWS per k-step: eight coalesced dword loads) next to
-//     x in the same layout: the operands of dW = x^T dz with the rows as K.  dz is never written;
+//   * forms the operands of dW = x^T dz with the rows as K, x and dz, from the same reads (below: through a per-wave LDS image).
+//     dz is never written;
 //   * keeps its 64 x 64 dW partial in registers over its rows; the four waves meet in LDS (fixed order) and the workgroup
 //     stores ONE partial.  partial_sum_kernel adds the partials in ascending order: dW is the same bits on every run.
 // GEMM arithmetic: two bf16 pieces per operand, three products (that of epc_gemm_f32_fast, the other backward GEMMs).
 // ----------------------------------------------------------------------------------------------------------------
-#ifndef LB_TILES_PER_WAVE
 #define LB_TILES_PER_WAVE 2
-#endif
 #define LB_ROWS_PER_WG (4 * 32 * LB_TILES_PER_WAVE)
 
-#ifndef LB_COLUMN_LOADS
 // dW = x^T dz needs both operands with the ROWS as k: lane = channel, eight consecutive rows per k-step.  The first form of this
-// kernel (kept under -DLB_COLUMN_LOADS) read x, dy and z a second time in that layout -- 96 lane-coalesced dword loads per
+// kernel (b2826b8 has it) read x, dy and z a second time in that layout -- 96 lane-coalesced dword loads per
 // 32-row tile next to the 16 float4 loads of the row layout -- and was bound by issuing them (29 us per layer).  Here every
 // tensor is read ONCE, in the row layout; the bf16 pieces of x and of dz go through a per-wave LDS image [row][channel]
 // (128-B rows, 16-B chunks XOR-swizzled) and come back transposed by ds_read_b64_tr_b16: lane 4q + p of a 16-lane group
@@ -2070,191 +2009,6 @@ __global__ __launch_bounds__(256, 2) void linear_bn_bwd64_kernel(
                 for (int r = 0; r < 16; ++r) out[(32 * mt + mfma_row(r, h)) * 64 + 32 * nt + i] = accW[mt][nt][r];
     }
 }
-#else
-__global__ __launch_bounds__(256) void linear_bn_bwd64_kernel(
-    const float* __restrict__ dy, const float* __restrict__ z, const float* __restrict__ x, const float* __restrict__ W,
-    const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ dbeta, const float* __restrict__ dgamma, float eps,
-    float inv_rows, int relu, int rows, float* __restrict__ dx, float* __restrict__ dWpart, BnParams xbn,
-    const float* __restrict__ dx_addend) {
-    // xbn: the layer's input was relu(bn(x)) of the previous layer's pre-activation x (epc_linear_stats64_bn): the dW operand is
-    // formed the same way as it is loaded.  dx_addend (rows, 64): dx leaves as W dz + addend (the gradient that reaches the same
-    // tensor by the block's residual path, so that the neighbour backward gathers ONE tensor).
-    __shared__ __attribute__((aligned(16))) float coef[6][64];          // s, t (mask), mean, k1, dbeta/rows, rstd dgamma/rows
-    __shared__ float xcoef[2][64];
-    __shared__ u32x4 Wf[2][4][2][64];                                    // W as A fragments: [in tile][k-step][hi, lo][lane]
-    __shared__ __attribute__((aligned(16))) float red[2][4][16][64];     // parked dW partials: [slot][tile][register][lane]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 31, h = lane >> 5;
-    if (tid < 64) {
-        const float mu = mean[tid], rs = 1.0f / sqrtf(var[tid] + eps), ga = gamma[tid];
-        const BnAffine a = bn_affine(mu, var[tid], ga, beta[tid], eps);
-        coef[0][tid] = a.s, coef[1][tid] = a.t, coef[2][tid] = mu;
-        coef[3][tid] = ga * rs, coef[4][tid] = dbeta[tid] * inv_rows, coef[5][tid] = rs * (dgamma[tid] * inv_rows);
-        if (xbn.mean) {
-            const BnAffine xa = bn_affine(xbn.mean[tid], xbn.var[tid], xbn.gamma[tid], xbn.beta[tid], xbn.eps);
-            xcoef[0][tid] = xa.s, xcoef[1][tid] = xa.t;
-        }
-    }
-    // W (in, out) row-major: A[m = in][k = out]; lane (m = 32 mt + i, k group h) of k-step s holds W[m][16 s + 8 h .. + 7]
-    for (int f = tid; f < 2 * 4 * 64; f += 256) {
-        const int l = f & 63, s4 = (f >> 6) & 3, mt = f >> 8;
-        const float* src = W + (size_t)(32 * mt + (l & 31)) * 64 + 16 * s4 + 8 * (l >> 5);
-        const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-        const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        bf16x8 ph, pl;
-        split8(v, ph, pl);
-        Wf[mt][s4][0][l] = __builtin_bit_cast(u32x4, ph);
-        Wf[mt][s4][1][l] = __builtin_bit_cast(u32x4, pl);
-    }
-    __syncthreads();
-
-    f32x16 accW[2][2];   // [in tile mt][out tile nt]: register 4g + e = in channel 32 mt + 8 g + 4 h + e, lane = out channel 32 nt + i
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) accW[mt][nt][r] = 0.f;
-
-    auto dz_of = [&](float dyv, float zv, float cs, float ct, float mu, float k1, float bb, float gg) {
-        const float d = (relu && !(zv * cs + ct > 0.f)) ? 0.f : dyv;   // the forward's own expression (bn_value)
-        return k1 * (d - bb - (zv - mu) * gg);
-    };
-
-    for (int t = 0; t < LB_TILES_PER_WAVE; ++t) {
-        const int base = blockIdx.x * LB_ROWS_PER_WG + (wave * LB_TILES_PER_WAVE + t) * 32;   // wave-uniform
-        if (base >= rows) break;
-        // ---- row layout: dz as B fragments (n = row base + i, k = out channel), dx^T = W dz^T ----
-        if (dx) {
-            const int row = base + i;
-            const bool ok = row < rows;
-            const size_t o = (size_t)(ok ? row : 0) * 64 + 8 * h;
-            bf16x8 zh[4], zl[4];
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const float4 g0 = *reinterpret_cast<const float4*>(dy + o + 16 * s4), g1 = *reinterpret_cast<const float4*>(dy + o + 16 * s4 + 4);
-                const float4 z0 = *reinterpret_cast<const float4*>(z + o + 16 * s4), z1 = *reinterpret_cast<const float4*>(z + o + 16 * s4 + 4);
-                const float gv[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-                const float zv[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
-                float dzv[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int c = 16 * s4 + 8 * h + q;
-                    const float v = dz_of(gv[q], zv[q], coef[0][c], coef[1][c], coef[2][c], coef[3][c], coef[4][c], coef[5][c]);
-                    dzv[q] = ok ? v : 0.f;
-                }
-                split8(dzv, zh[s4], zl[s4]);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) {
-                    const bf16x8 wh = __builtin_bit_cast(bf16x8, Wf[mt][s4][0][lane]), wl = __builtin_bit_cast(bf16x8, Wf[mt][s4][1][lane]);
-                    acc = mfma_bf16(wl, zh[s4], acc);
-                    acc = mfma_bf16(wh, zl[s4], acc);
-                    acc = mfma_bf16(wh, zh[s4], acc);
-                }
-                if (ok) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        float4 v = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
-                        if (dx_addend) {
-                            const float4 a = *reinterpret_cast<const float4*>(dx_addend + (size_t)row * 64 + 32 * mt + 8 * g + 4 * h);
-                            v.x += a.x, v.y += a.y, v.z += a.z, v.w += a.w;
-                        }
-                        *reinterpret_cast<float4*>(dx + (size_t)row * 64 + 32 * mt + 8 * g + 4 * h) = v;
-                    }
-                }
-            }
-        }
-        // ---- column layout: lane = channel, k = rows base + 16 s + 8 h + q;  dW += x^T dz ----
-        bf16x8 xh[2][2], xl[2][2];   // [in tile][k-step]
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                // (loads from clamped rows, zeroed afterwards: a guarded load is an exec-masked branch with a full wait at its
-                // join -- the 96 loads of this phase would go out one round trip at a time)
-                float v[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = x[(size_t)min(base + 16 * s2 + 8 * h + q, rows - 1) * 64 + 32 * mt + i];
-                if (xbn.mean) {
-                    const float xs = xcoef[0][32 * mt + i], xt = xcoef[1][32 * mt + i];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) v[q] = fmaxf(v[q] * xs + xt, 0.f);
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = (base + 16 * s2 + 8 * h + q < rows) ? v[q] : 0.f;
-                split8(v, xh[mt][s2], xl[mt][s2]);
-            }
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int c = 32 * nt + i;
-            const float cs = coef[0][c], ct = coef[1][c], mu = coef[2][c], k1 = coef[3][c], bb = coef[4][c], gg = coef[5][c];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                float v[8], gy[8], gz[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const size_t o = (size_t)min(base + 16 * s2 + 8 * h + q, rows - 1) * 64 + c;
-                    gy[q] = dy[o], gz[q] = z[o];
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float d = dz_of(gy[q], gz[q], cs, ct, mu, k1, bb, gg);
-                    v[q] = (base + 16 * s2 + 8 * h + q < rows) ? d : 0.f;
-                }
-                bf16x8 dh, dl;
-                split8(v, dh, dl);
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    accW[mt][nt] = mfma_bf16(xl[mt][s2], dh, accW[mt][nt]);
-                    accW[mt][nt] = mfma_bf16(xh[mt][s2], dl, accW[mt][nt]);
-                    accW[mt][nt] = mfma_bf16(xh[mt][s2], dh, accW[mt][nt]);
-                }
-            }
-        }
-    }
-    // ---- the four waves' partials meet pairwise, ((w0 + w1) + (w2 + w3)): a fixed order; wave 0 stores the workgroup's ----
-    auto park = [&](int slot) {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) red[slot][mt * 2 + nt][r][lane] = accW[mt][nt][r];
-    };
-    auto take = [&](int slot) {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) accW[mt][nt][r] += red[slot][mt * 2 + nt][r][lane];
-    };
-    if (wave & 1) park(wave >> 1);
-    __syncthreads();
-    if (!(wave & 1)) take(wave >> 1);
-    __syncthreads();
-    if (wave == 2) park(0);
-    __syncthreads();
-    if (wave == 0) {
-        take(0);
-        float* out = dWpart + (size_t)blockIdx.x * 4096;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) out[(32 * mt + mfma_row(r, h)) * 64 + 32 * nt + i] = accW[mt][nt][r];
-    }
-}
-
-#endif   // LB_COLUMN_LOADS
 
 // out[e] = sum over p < P of part[p][e], added in ascending p whatever the launch geometry (16 groups of a workgroup take
 // every 16th partial each, their sums meet in LDS in group order: a fixed tree): the ordered counterpart of an atomic

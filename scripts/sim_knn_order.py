@@ -1,8 +1,8 @@
 """CPU model of the culled kNN kernel's pass 1 (csrc/knn.hip) on one 4096-point cloud: per wave of 64 consecutive queries,
 32-point candidate tiles with bounding boxes, per-lane sorted top-20 lists, a tile is scanned when any lane's box bound
-beats its threshold, a network pass is counted whenever any lane improves on a candidate.  It reproduces the kernel's
-KNN_STATS counters (26.6 tiles scanned, ~50 hit batches, ~244 passes per wave on a Hilbert-ordered uniform cloud; 37.8 /
-265 on the Z-order) and was used to decide, before touching the kernel, which ideas were worth building: Hilbert vs
+beats its threshold, a network pass is counted whenever any lane improves on a candidate.  It reproduced the event counters
+of an instrumented kernel build (26.6 tiles scanned, ~50 hit batches, ~244 passes per wave on a Hilbert-ordered uniform
+cloud; 37.8 / 265 on the Z-order; the counters are in 2fcfbdc, removed since) and was used to decide, before touching the kernel, which ideas were worth building: Hilbert vs
 Z-order (built), tile visiting orders, a per-lane index-neighbourhood first phase, a wave-level scalar pre-test.
 Run: python scripts/sim_knn_order.py   (numpy only, ~2 minutes)."""
 import numpy as np

@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import numpy as np, torch
 import helpers as H
 from helpers import O
-V, tf_util, ops, L = H.pkg("variables"), H.pkg("utils.tf_util"), H.pkg("ops"), H.pkg("lib")
+V, tf_util, ops = H.pkg("variables"), H.pkg("utils.tf_util"), H.pkg("ops")
 dev = torch.device("cuda:0")
 ncl, n = int(os.environ.get("NCL", "18")), int(os.environ.get("N", "4096"))
 arch = os.environ.get("ARCH", "epc-net"); nb = 4 if arch == "epc-net" else 2
@@ -54,28 +54,3 @@ for label, f in (("launch chain", False), ("persistent fwd", True)):
 ref = outs["launch chain"]
 for k, v in outs.items():
     print("%-28s max |cat - launch chain| = %.3e (scale %.3e), rel L2 %.3e" % (k, np.abs(v - ref).max(), np.abs(ref).max(), np.linalg.norm(v - ref) / np.linalg.norm(ref)))
-
-if os.environ.get("STAMPS", "0") == "1":      # needs a -DPST_STAMPS build of the library (scripts/build_variant.sh, EPCNET_LIB=...)
-    ops.CHAIN_PERSIST_FWD = True
-    for _ in range(3):
-        run()
-    torch.cuda.synchronize()
-    ws = ops.chain_workspace(dev)
-    nbytes = ws.numel()
-    st_ = ws[nbytes - 512 * 64 * 8:].view(torch.int64).view(512, 64).cpu().numpy()
-    P = L.lib().epc_chain_parts(ncl * n)
-    st_ = st_[:P]
-    nst = int((st_[0] != 0).sum())
-    t0 = st_[:, 0].min()
-    names = ["start", "S done"]
-    for b in range(nb):
-        names += ["b%d reduced0" % b, "b%d gathered0" % b, "b%d pooled0" % b, "b%d G done" % b, "b%d posted_a" % b,
-                  "b%d reduced_a" % b, "b%d gathered_a" % b, "b%d pooled_a" % b, "b%d M done" % b, "b%d posted_b" % b,
-                  "b%d reduced_b" % b, "b%d gathered_b" % b, "b%d pooled_b" % b, "b%d H done" % b, "b%d posted0'" % b]
-    print("stamp (10-ns ticks -> us): min / median / max over %d workgroups, relative to the earliest start; delta of medians; [leaders' median]" % P)
-    prev = 0.0
-    for k in range(nst):
-        col = (st_[:, k] - t0) / 100.0
-        med = float(np.median(col))
-        print("  %-18s %8.2f %8.2f %8.2f   +%6.2f   [%8.2f]" % (names[k] if k < len(names) else "?", col.min(), med, col.max(), med - prev, float(np.median(col[:8]))))
-        prev = med

@@ -29,12 +29,3 @@ for B in [int(a) for a in sys.argv[1:]] or [18, 22, 64, 256]:
         res[form] = (e0.elapsed_time(e1) / 20, idx, cnt, kth)
     same = all(torch.equal(res[0][k], res[1][k]) for k in (1, 2, 3))
     print("knn %3d clouds: one lane %.3f ms, four lanes %.3f ms, identical outputs: %s" % (B, res[0][0], res[1][0], same), flush=True)
-    if hasattr(lib, "epc_debug_knn_stats"):
-        for form in (0, 1):
-            st8 = (ctypes.c_ulonglong * 8)()
-            lib.epc_debug_knn_stats(st8, 1)
-            lib.epc_knn_topk_form(srt.data_ptr(), B, N, 32, idx.data_ptr(), cnt.data_ptr(), kth.data_ptr(), form, st); torch.cuda.synchronize()
-            lib.epc_debug_knn_stats(st8, 1)
-            waves = B * N / (64 if form == 0 else 16)
-            print("    form %d per wave: votes %.1f, tiles scanned %.1f | hit batches %.1f, network passes %.1f | p2 tiles %.1f, emit batches %.1f"
-                  % ((form,) + tuple(st8[i] / waves for i in range(6))))

@@ -1,5 +1,5 @@
-"""Tuning aid (GPU box): per-stage HIP-event times of epc_net_forward for 64 x 4096 clouds, no output checks
-(ablation builds produce wrong descriptors on purpose).  Usage: EPCNET_LIB=/tmp/x.so python scripts/time_stages.py name"""
+"""Tuning aid (GPU box): per-stage HIP-event times of epc_net_forward for 64 x 4096 clouds, no output checks.  EPCNET_LIB
+selects another build of the library to compare.  Usage: [EPCNET_LIB=/path/to/libepcnet_hip.so] python scripts/time_stages.py name"""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
