@@ -1,5 +1,6 @@
 // EPC_PRECISION_FAST form of conv5 (+BN+ReLU) + per-point L2 norm + soft assignment (EPC-Net: models/epc-net.py:136-139,
-// 147-148 + loupe.py:249-272), and the two VLAD aggregate kernels (fast and f32-equivalent).  The f32-equivalent conv5 kernels
+// 147-148 + loupe.py:249-272), the same conv5 + the global max-pool (EPC-Net-L: conv5_max_f16_kernel), and the two VLAD
+// aggregate kernels (fast and f32-equivalent).  The f32-equivalent conv5 kernels
 // (EPC-Net and EPC-Net-L) live in conv5_f32.hip.
 //
 // Arithmetic ("f16 + f6"): ONE fp16 value per activation; weights as fp16 hi + MX-fp6 lo of W * 2^8: per 32-channel chunk 16
@@ -40,6 +41,138 @@ struct C5Lds {  // offsets in floats (4 B)
     static constexpr int TOTAL = OFF_CBN + 128;
 };
 
+// ---- the f16 + f6 product, shared by conv5_kernel (EPC-Net) and conv5_max_f16_kernel (EPC-Net-L) --------------------------
+// A wave's operands for its 32-point tile: lane (j, h) holds point j's inputs as fp16 fragments (k-step s covers channels
+// 16s + 8h .. +7) -- ONE fp16 value per input, the weights carry the hi + lo split (W5_SCALE comment in common.h) -- and the
+// same values as MX fp6 (the lo-term operand): per 64-wide k-step the lane's 32 consecutive channels 64ks + 32h .. +31 in
+// six dwords, their block scale in byte ks of xsc.
+template <int CIN>
+struct C5Operands {
+    f16x8 xf[CIN / 16];
+    i32x6 x6[CIN / 64];
+    int xsc;
+};
+
+template <int CIN>
+__device__ __forceinline__ void c5_to_fp6(f16x32 v, int ks, C5Operands<CIN>& x) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
+    const u32x16 w = __builtin_bit_cast(u32x16, v);
+    u16x2 m2 = {0, 0};
+#pragma unroll
+    for (int i = 0; i < 16; ++i)   // |fp16| orders like its bit pattern: packed 16-bit max
+        m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, w[i] & 0x7fff7fffu));
+    const unsigned short mb = m2[0] > m2[1] ? m2[0] : m2[1];
+    const float m = (float)__builtin_bit_cast(_Float16, mb);
+    const int e = fp6_block_exponent(m, -12, 14);          // 2^-e stays an fp16 normal: the scaling below is exact
+    const _Float16 down = (_Float16)exp2i(-e);
+    x.x6[ks] = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(v * down, 1.0f);
+    x.xsc |= (127 + e) << (8 * ks);
+}
+
+// Rows g0 .. g0 + 31 of cat (CIN channels; fp16 when CAT16, else f32, rounded to fp16 on load) -> the lane's operands; an
+// inactive wave (tail of the grid) gets zeros.
+template <int CIN, bool CAT16>
+__device__ __forceinline__ void c5_load_operands(const float* __restrict__ cat, int g0, bool active, int j, int h,
+                                                 C5Operands<CIN>& x) {
+    constexpr int STEPS = CIN / 16;
+    x.xsc = 0;
+    if constexpr (CAT16) {  // fp16 rows (the blocks' out16): the 16 B a lane reads ARE its fragment
+        const unsigned short* row = reinterpret_cast<const unsigned short*>(cat) + (size_t)(active ? g0 + j : 0) * CIN + 8 * h;
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) {
+            u32x4 w = *reinterpret_cast<const u32x4*>(row + 16 * s);
+            if (!active) w = u32x4{0u, 0u, 0u, 0u};
+            x.xf[s] = __builtin_bit_cast(f16x8, w);
+        }
+#pragma unroll
+        for (int ks = 0; ks < CIN / 64; ++ks) {   // channels 64ks + 32h .. +31 of the lane's point
+            typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
+            u32x16 w16;
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                u32x4 w = *reinterpret_cast<const u32x4*>(row + 64 * ks + 24 * h + 8 * q4);   // row already holds +8h
+                if (!active) w = u32x4{0u, 0u, 0u, 0u};
+                w16[4 * q4] = w[0], w16[4 * q4 + 1] = w[1], w16[4 * q4 + 2] = w[2], w16[4 * q4 + 3] = w[3];
+            }
+            c5_to_fp6<CIN>(__builtin_bit_cast(f16x32, w16), ks, x);
+        }
+    } else {
+        const float* row = cat + (size_t)(active ? g0 + j : 0) * CIN + 8 * h;
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) {
+            const float4 a = active ? ld4(row + 16 * s) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 b = active ? ld4(row + 16 * s + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            x.xf[s][0] = (_Float16)a.x, x.xf[s][1] = (_Float16)a.y, x.xf[s][2] = (_Float16)a.z, x.xf[s][3] = (_Float16)a.w;
+            x.xf[s][4] = (_Float16)b.x, x.xf[s][5] = (_Float16)b.y, x.xf[s][6] = (_Float16)b.z, x.xf[s][7] = (_Float16)b.w;
+        }
+        const float* row0 = row - 8 * h;   // channel 0 of the lane's point
+#pragma unroll
+        for (int ks = 0; ks < CIN / 64; ++ks) {
+            f16x32 v;
+#pragma unroll
+            for (int w8 = 0; w8 < 8; ++w8) {
+                const float4 a = active ? ld4(row0 + 64 * ks + 32 * h + 4 * w8) : make_float4(0.f, 0.f, 0.f, 0.f);
+                // (through fp16: the fp6 copy must describe the same input the hi term sees)
+                v[4 * w8] = (_Float16)a.x, v[4 * w8 + 1] = (_Float16)a.y, v[4 * w8 + 2] = (_Float16)a.z, v[4 * w8 + 3] = (_Float16)a.w;
+            }
+            c5_to_fp6<CIN>(v, ks, x);
+        }
+    }
+}
+
+// One 32-channel chunk of the product, accumulated onto acc (the caller initialises it with the scaled bias): fragments from
+// the chunk's LDS copy w5 (C5Lds layout).  SWAP = false: D[channel][point] (weights as A: lane = point, registers =
+// channels); SWAP = true: the operands exchanged, D[point][channel] (lane = channel, registers = points) -- the same products.
+template <int CIN, bool SWAP>
+__device__ __forceinline__ void c5_chunk_chain(const float* w5, const C5Operands<CIN>& x, int lane, f32x16& acc) {
+    using L = C5Lds<CIN>;
+    constexpr int STEPS = CIN / 16;
+    // lo term first (small): W_lo and the inputs as MX fp6, K = 64 per instruction in 8 passes (the fp16 K = 16
+    // instruction takes 8 as well) -- the lo term is a 2^-11 correction, so 4 significant bits on each side keep it
+    // to 2^-15 of the product.  Block scales: byte ks of the lanes' scale dwords (op_sel).
+    const float* wl = w5 + L::W5_LO8;
+    const int wsc = __float_as_int(w5[L::W5_LOSC + lane]);
+    auto lo_step = [&](auto ksc) {
+        constexpr int ks = decltype(ksc)::value;
+        if constexpr (ks < CIN / 64) {
+            const u32x4 l0 = *reinterpret_cast<const u32x4*>(wl + ks * L::LO6_KS + lane * 4);
+            const uint2 l1 = *reinterpret_cast<const uint2*>(wl + ks * L::LO6_KS + 256 + lane * 2);
+            const i32x8 a = {(int)l0[0], (int)l0[1], (int)l0[2], (int)l0[3], (int)l1.x, (int)l1.y, 0, 0};
+            const i32x8 b6 = {x.x6[ks][0], x.x6[ks][1], x.x6[ks][2], x.x6[ks][3], x.x6[ks][4], x.x6[ks][5], 0, 0};
+            if constexpr (SWAP)
+                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b6, a, acc, 2, 2, ks, x.xsc, ks, wsc);
+            else
+                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b6, acc, 2, 2, ks, wsc, ks, x.xsc);
+        }
+    };
+    lo_step(std::integral_constant<int, 0>{});
+    lo_step(std::integral_constant<int, 1>{});
+    lo_step(std::integral_constant<int, 2>{});
+    lo_step(std::integral_constant<int, 3>{});
+    static_assert(CIN / 64 <= 4, "one scale dword holds four block scales");
+    // fragment reads run PF k-steps ahead of the MFMAs that consume them: eight waves share the LDS port, so a
+    // read returns after ~8 other 1-KB reads (64+ cycles) while a k-step's MFMA takes 32 -- with one read in flight
+    // per wave the port idles.  Depths 1, 2, 3, 4, 6 measured 0.258-0.260 ms alike, so the shallowest (fewest
+    // registers) stays.
+    constexpr int PF = 1;
+    static_assert(PF < STEPS, "the ring holds PF + 1 k-steps");
+    constexpr int RING = PF + 1;
+    f16x8 fa[RING];
+#pragma unroll
+    for (int s = 0; s < PF; ++s) fa[s] = ldfrag16(w5 + (s * 64 + lane) * 4);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+        if (s + PF < STEPS) fa[(s + PF) % RING] = ldfrag16(w5 + ((s + PF) * 64 + lane) * 4);
+        __builtin_amdgcn_sched_barrier(0);  // keep the reads AHEAD of this step's MFMAs (hipcc sinks them otherwise)
+        if constexpr (SWAP)
+            acc = mfma_f16(x.xf[s], fa[s % RING], acc);
+        else
+            acc = mfma_f16(fa[s % RING], x.xf[s], acc);
+    }
+}
+
 // packed conv5 stage (4-byte units): [W5p: 24*CIN*32 floats][b5f 1024][Wcp 1024*32 (fp16)][cbn_s 64][cbn_t 64]
 // CAT16: the input rows are fp16 (the fast block chain's out16) instead of f32.
 template <int CIN, bool CAT16>
@@ -52,7 +185,6 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_kernel(const float* __restri
                                                            float* __restrict__ apart,
                                                            int32_t* __restrict__ status) {
     using L = C5Lds<CIN>;
-    constexpr int STEPS = CIN / 16;
     static_assert(8 * L::T_WAVE <= 2 * L::W5_CHUNK, "the transpose tiles must fit in the W5 buffers");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -90,72 +222,9 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_kernel(const float* __restri
     const int g0 = (blockIdx.x * C5_WAVES + wave) * 32;
     const bool active = g0 < total_points;
 
-    // this lane's B fragments: point j, k-step s covers input channels 16s + 8h .. +7.  ONE fp16 value per input, the weights
-    // carry the hi + lo split (W5_SCALE comment in common.h) -- the input rounding averages out over the cloud's points in the
-    // aggregation.
     constexpr float kDescale = 1.0f / W5_SCALE;
-    f16x8 xf[STEPS];
-    // the same inputs as MX fp6 (B operand of the lo-term MFMA): per 64-wide k-step the lane's 32 consecutive channels
-    // 64ks + 32h .. +31 in six dwords, their block scale in byte ks of xsc
-    i32x6 x6[CIN / 64];
-    int xsc = 0;
-    auto to_fp6 = [&](f16x32 v, int ks) {
-        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-        typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
-        const u32x16 w = __builtin_bit_cast(u32x16, v);
-        u16x2 m2 = {0, 0};
-#pragma unroll
-        for (int i = 0; i < 16; ++i)   // |fp16| orders like its bit pattern: packed 16-bit max
-            m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, w[i] & 0x7fff7fffu));
-        const unsigned short mb = m2[0] > m2[1] ? m2[0] : m2[1];
-        const float m = (float)__builtin_bit_cast(_Float16, mb);
-        const int e = fp6_block_exponent(m, -12, 14);          // 2^-e stays an fp16 normal: the scaling below is exact
-        const _Float16 down = (_Float16)exp2i(-e);
-        x6[ks] = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(v * down, 1.0f);
-        xsc |= (127 + e) << (8 * ks);
-    };
-    if constexpr (CAT16) {  // fp16 rows (the blocks' out16): the 16 B a lane reads ARE its fragment
-        const unsigned short* row = reinterpret_cast<const unsigned short*>(cat) + (size_t)(active ? g0 + j : 0) * CIN + 8 * h;
-#pragma unroll
-        for (int s = 0; s < STEPS; ++s) {
-            u32x4 w = *reinterpret_cast<const u32x4*>(row + 16 * s);
-            if (!active) w = u32x4{0u, 0u, 0u, 0u};
-            xf[s] = __builtin_bit_cast(f16x8, w);
-        }
-#pragma unroll
-        for (int ks = 0; ks < CIN / 64; ++ks) {   // channels 64ks + 32h .. +31 of the lane's point
-            typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
-            u32x16 w16;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                u32x4 w = *reinterpret_cast<const u32x4*>(row + 64 * ks + 24 * h + 8 * q4);   // row already holds +8h
-                if (!active) w = u32x4{0u, 0u, 0u, 0u};
-                w16[4 * q4] = w[0], w16[4 * q4 + 1] = w[1], w16[4 * q4 + 2] = w[2], w16[4 * q4 + 3] = w[3];
-            }
-            to_fp6(__builtin_bit_cast(f16x32, w16), ks);
-        }
-    } else {
-        const float* row = cat + (size_t)(active ? g0 + j : 0) * CIN + 8 * h;
-#pragma unroll
-        for (int s = 0; s < STEPS; ++s) {
-            const float4 a = active ? ld4(row + 16 * s) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 b = active ? ld4(row + 16 * s + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            xf[s][0] = (_Float16)a.x, xf[s][1] = (_Float16)a.y, xf[s][2] = (_Float16)a.z, xf[s][3] = (_Float16)a.w;
-            xf[s][4] = (_Float16)b.x, xf[s][5] = (_Float16)b.y, xf[s][6] = (_Float16)b.z, xf[s][7] = (_Float16)b.w;
-        }
-        const float* row0 = row - 8 * h;   // channel 0 of the lane's point
-#pragma unroll
-        for (int ks = 0; ks < CIN / 64; ++ks) {
-            f16x32 v;
-#pragma unroll
-            for (int w8 = 0; w8 < 8; ++w8) {
-                const float4 a = active ? ld4(row0 + 64 * ks + 32 * h + 4 * w8) : make_float4(0.f, 0.f, 0.f, 0.f);
-                // (through fp16: the fp6 copy must describe the same input the hi term sees)
-                v[4 * w8] = (_Float16)a.x, v[4 * w8 + 1] = (_Float16)a.y, v[4 * w8 + 2] = (_Float16)a.z, v[4 * w8 + 3] = (_Float16)a.w;
-            }
-            to_fp6(v, ks);
-        }
-    }
+    C5Operands<CIN> x;   // this lane's operands (point j): the input rounding averages out over the cloud's points in the aggregation
+    c5_load_operands<CIN, CAT16>(cat, g0, active, j, h, x);
 
     f32x16 P[2];
 #pragma unroll
@@ -181,43 +250,7 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_kernel(const float* __restri
             acc[4 * g + 2] = bv.z;
             acc[4 * g + 3] = bv.w;
         }
-        // lo term first (small): W_lo and the inputs as MX fp6, K = 64 per instruction in 8 passes (the fp16 K = 16
-        // instruction takes 8 as well) -- the lo term is a 2^-11 correction, so 4 significant bits on each side keep it
-        // to 2^-15 of the product.  Block scales: byte ks of the lanes' scale dwords (op_sel).
-        const float* wl = w5 + L::W5_LO8;
-        const int wsc = __float_as_int(w5[L::W5_LOSC + lane]);
-        auto lo_step = [&](auto ksc) {
-            constexpr int ks = decltype(ksc)::value;
-            if constexpr (ks < CIN / 64) {
-                const u32x4 l0 = *reinterpret_cast<const u32x4*>(wl + ks * L::LO6_KS + lane * 4);
-                const uint2 l1 = *reinterpret_cast<const uint2*>(wl + ks * L::LO6_KS + 256 + lane * 2);
-                const i32x8 a = {(int)l0[0], (int)l0[1], (int)l0[2], (int)l0[3], (int)l1.x, (int)l1.y, 0, 0};
-                const i32x8 b6 = {x6[ks][0], x6[ks][1], x6[ks][2], x6[ks][3], x6[ks][4], x6[ks][5], 0, 0};
-                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b6, acc, 2, 2, ks, wsc, ks, xsc);
-            }
-        };
-        lo_step(std::integral_constant<int, 0>{});
-        lo_step(std::integral_constant<int, 1>{});
-        lo_step(std::integral_constant<int, 2>{});
-        lo_step(std::integral_constant<int, 3>{});
-        static_assert(CIN / 64 <= 4, "one scale dword holds four block scales");
-        // fragment reads run PF k-steps ahead of the MFMAs that consume them: eight waves share the LDS port, so a
-        // read returns after ~8 other 1-KB reads (64+ cycles) while a k-step's MFMA takes 32 -- with one read in flight
-        // per wave the port idles.  Depths 1, 2, 3, 4, 6 measured 0.258-0.260 ms alike, so the shallowest (fewest
-        // registers) stays.
-        constexpr int PF = 1;
-        static_assert(PF < STEPS, "the ring holds PF + 1 k-steps");
-        constexpr int RING = PF + 1;
-        f16x8 fa[RING];
-#pragma unroll
-        for (int s = 0; s < PF; ++s) fa[s] = ldfrag16(w5 + (s * 64 + lane) * 4);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < STEPS; ++s) {
-            if (s + PF < STEPS) fa[(s + PF) % RING] = ldfrag16(w5 + ((s + PF) * 64 + lane) * 4);
-            __builtin_amdgcn_sched_barrier(0);  // keep the reads AHEAD of this step's MFMAs (hipcc sinks them otherwise)
-            acc = mfma_f16(fa[s % RING], xf[s], acc);
-        }
+        c5_chunk_chain<CIN, false>(w5, x, lane, acc);
     };
     auto chunk_epi = [&](int c) {
         // ReLU and the 2^-8 that removes W5_SCALE (bias and weights are packed scaled): max on the bit pattern
@@ -398,6 +431,158 @@ extern "C" int epc_conv5_assign_fwd(const void* cat, int cat_fp16, int cin, cons
                                        assign, (float*)assign_frag, apart, status, (hipStream_t)stream, __func__);
     return launch_conv5<256, false>((const float*)cat, (const float*)packed_conv5, num_points_total, n, (float*)feat_frag, rnorm,
                                     assign, (float*)assign_frag, apart, status, (hipStream_t)stream, __func__);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// EPC_PRECISION_FAST conv5 + global max-pool (EPC-Net-L: models/epc-net-l.py:84-92) on the fp16 concat rows of the fast blocks.
+// The product is conv5_kernel's (c5_load_operands + c5_chunk_chain: fp16 activations against fp16 hi + MX-fp6 lo weights of
+// W' * 2^8, the scaled bias as the accumulator's start, f32 accumulation) with the operands exchanged, so that the accumulator
+// is D[point][channel]: lane = channel 32c + (lane & 31), registers = points; the max over the tile's 32 points is over the 16
+// registers and the two lane halves.  ReLU and the exact 2^-8 commute with the maximum, so they are applied once, to it; the
+// conv5 output is never rounded to fp16 (no range check here: the blocks' is the last).
+//
+// Geometry: WAVES waves, one 32-point tile per wave; the 32-channel chunks of the pack (96 * CIN bytes) stream through a
+// double-buffered LDS copy shared by the workgroup (LDS-DMA, one barrier per chunk; the wait before it drains vmcnt, so no
+// count depends on the order of the wave's memory operations).  Combining tiles is conv5_max_f32_kernel's: when the
+// workgroup's tiles lie in one cloud (n % (32 * WAVES) == 0) the per-wave maxima meet in LDS (one slab per chunk parity,
+// folded one chunk late) and leave as 1024 atomics at the end; otherwise every wave issues its own.  Values are >= 0 (ReLU)
+// and pooled starts at 0 (the launcher zeroes it), so the unsigned max on the bit patterns is the float max: order-free.
+// ---------------------------------------------------------------------------------------------------------------------------
+#define C5MF_WAVES 4
+template <int CIN, int WAVES>
+struct C5mfLds {  // offsets in floats
+    static constexpr int W5_CHUNK = C5Lds<CIN>::W5_CHUNK;
+    static constexpr int OFF_W5 = 0;                          // two chunk buffers (chunk parity)
+    static constexpr int OFF_B5 = 2 * W5_CHUNK;               // the scaled bias, 1024
+    static constexpr int OFF_RED = OFF_B5 + 1024;             // per-wave maxima of a chunk: [parity][wave][32 channels]
+    static constexpr int OFF_MAX = OFF_RED + 2 * WAVES * 32;  // the workgroup's 1024 maxima (one-cloud workgroups)
+    static constexpr int TOTAL = OFF_MAX + 1024;
+};
+
+// packed conv5 stage (4-byte units): [W5p: 24*CIN*32 floats][b5f 1024] (the fast layout, pack.hip)
+template <int CIN, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, 4) void conv5_max_f16_kernel(const unsigned short* __restrict__ cat16,
+                                                                      const float* __restrict__ pack, int total_points, int n,
+                                                                      float* __restrict__ pooled) {
+    using L = C5mfLds<CIN, WAVES>;
+    constexpr int THREADS = 64 * WAVES;
+    constexpr int PIECES = L::W5_CHUNK / 256;                  // 1-KB LDS-DMA pieces per chunk (12 at CIN = 128)
+    constexpr int PER_WAVE = (PIECES + WAVES - 1) / WAVES;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const float* gw5 = pack;
+    const float* gb5 = pack + (size_t)CIN * 1024;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const unsigned lds_base = (unsigned)(size_t)(const __attribute__((address_space(3))) float*)lds;
+    const unsigned lane_off = lane * 16;
+    auto stage_chunk = [&](int c, auto bufc) {
+        constexpr int buf = decltype(bufc)::value;
+#pragma unroll
+        for (int u = 0; u < PER_WAVE; ++u) {
+            const int piece = u * WAVES + wave_u;
+            if (PIECES % WAVES == 0 || piece < PIECES)
+                glds16(gw5 + (size_t)c * L::W5_CHUNK + piece * 256, lane_off,
+                       lds_base + 4u * (L::OFF_W5 + buf * L::W5_CHUNK + piece * 256));
+        }
+    };
+    stage_chunk(0, std::integral_constant<int, 0>{});
+    for (int o = tid; o < 1024; o += THREADS) lds[L::OFF_B5 + o] = gb5[o];
+
+    const int g0 = (blockIdx.x * WAVES + wave) * 32;
+    const bool active = g0 < total_points;
+    const bool wg_one_cloud = n % (WAVES * 32) == 0;          // the workgroup's tiles share a cloud
+    C5Operands<CIN> x;
+    c5_load_operands<CIN, true>(reinterpret_cast<const float*>(cat16), g0, active, j, h, x);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    constexpr float kDescale = 1.0f / W5_SCALE;
+    unsigned int* wdst = reinterpret_cast<unsigned int*>(pooled + (size_t)(active ? g0 / n : 0) * 1024 + j);
+    // the workgroup's maxima of chunk c from the per-wave ones (written before the barrier that ended chunk c)
+    auto fold = [&](int c) {
+        if (wg_one_cloud && tid < 32) {
+            const float* red = lds + L::OFF_RED + (c & 1) * (WAVES * 32) + tid;
+            float m = red[0];
+#pragma unroll
+            for (int w = 1; w < WAVES; ++w) m = fmaxf(m, red[32 * w]);
+            lds[L::OFF_MAX + 32 * c + tid] = m;
+        }
+    };
+    auto do_chunk = [&](int c, auto bufc) {
+        constexpr int buf = decltype(bufc)::value;
+        if (c > 0) fold(c - 1);
+        if (c + 1 < 32) stage_chunk(c + 1, std::integral_constant<int, buf ^ 1>{});
+        f32x16 acc;
+        const float bv = lds[L::OFF_B5 + 32 * c + j];           // lane = channel: the scaled bias starts every point's sum
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = bv;
+        c5_chunk_chain<CIN, true>(lds + L::OFF_W5 + buf * L::W5_CHUNK, x, lane, acc);
+        float m = acc[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) {
+            const float a = acc[r];   // (a scalar copy, as in conv5_kernel's epilogue)
+            m = fmaxf(m, a);
+        }
+        m = fmaxf(m, __shfl_xor(m, 32));
+        const int vb = __float_as_int(m);
+        m = active ? __int_as_float(vb > 0 ? vb : 0) * kDescale : 0.f;   // ReLU on the bit pattern, then 2^-8
+        if (wg_one_cloud) {
+            if (h == 0) lds[L::OFF_RED + (c & 1) * (WAVES * 32) + wave * 32 + j] = m;
+        } else if (active && h == 0) {
+            atomicMax(wdst + 32 * c, __float_as_uint(m));
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next chunk's pieces have landed (and this wave's atomics have left)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    };
+    for (int c = 0; c < 32; c += 2) {
+        do_chunk(c, std::integral_constant<int, 0>{});
+        do_chunk(c + 1, std::integral_constant<int, 1>{});
+    }
+    if (wg_one_cloud) {
+        fold(31);
+        __syncthreads();
+        unsigned int* dst = reinterpret_cast<unsigned int*>(pooled + (size_t)((blockIdx.x * WAVES * 32) / n) * 1024);
+        for (int o = tid; o < 1024; o += THREADS) atomicMax(dst + o, __float_as_uint(lds[L::OFF_MAX + o]));
+    }
+}
+
+template <int WAVES>
+static int launch_conv5_max_f16(const void* cat16, const void* packed_conv5, long total, int n, float* pooled, hipStream_t stream,
+                                const char* who) {
+    const size_t lds_bytes = C5mfLds<128, WAVES>::TOTAL * sizeof(float);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv5_max_f16_kernel<128, WAVES>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) {
+        epc_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+        return EPC_EHIP;
+    }
+    const unsigned blocks = (unsigned)((total + WAVES * 32 - 1) / (WAVES * 32));
+    hipLaunchKernelGGL((conv5_max_f16_kernel<128, WAVES>), dim3(blocks), dim3(64 * WAVES), lds_bytes, stream,
+                       (const unsigned short*)cat16, (const float*)packed_conv5, (int)total, n, pooled);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        epc_set_error("%s: launch failed: %s", who, hipGetErrorString(le));
+        return EPC_EHIP;
+    }
+    return EPC_OK;
+}
+
+extern "C" int epc_conv5_maxpool_f16_fwd(const void* cat16, int cin, const void* packed_conv5, int num_clouds, int n,
+                                         float* pooled, void* stream) {
+    EPC_CHECK_ARG(cat16 && packed_conv5 && pooled, "null pointer");
+    EPC_CHECK_ARG(cin == 128, "EPC-Net-L conv5 takes the 128-channel concat (models/epc-net-l.py:84)");
+    EPC_CHECK_ARG(n > 0 && n % 32 == 0 && num_clouds >= 0, "num_points must be a multiple of 32");
+    if (num_clouds == 0) return EPC_OK;
+    const long total = (long)num_clouds * n;
+    EPC_CHECK_ARG(total < (1L << 31), "too many points");
+    hipError_t e = hipMemsetAsync(pooled, 0, (size_t)num_clouds * 1024 * sizeof(float), (hipStream_t)stream);
+    if (e != hipSuccess) {
+        epc_set_error("epc_conv5_maxpool_f16_fwd: hipMemsetAsync: %s", hipGetErrorString(e));
+        return EPC_EHIP;
+    }
+    return launch_conv5_max_f16<C5MF_WAVES>(cat16, packed_conv5, total, n, pooled, (hipStream_t)stream, __func__);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

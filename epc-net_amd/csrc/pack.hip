@@ -14,8 +14,8 @@ struct StageLayout {
     size_t guard;   // 64 floats after the stages: word 0 = max |packed 16-bit operand| bit pattern (fp16 range guard)
 };
 
-// EPC-Net in EPC_PRECISION_FAST packs fp16 operands (scaled by W5_SCALE); everything else packs split-bf16 operands
-static bool cfg_fast(const epc_cfg* c) { return c->arch == EPC_ARCH_EPC_NET && c->precision == EPC_PRECISION_FAST; }
+// EPC_PRECISION_FAST (either model) packs fp16 operands (scaled by W5_SCALE); EPC_PRECISION_F32 packs scaled split-fp16 ones
+static bool cfg_fast(const epc_cfg* c) { return c->precision == EPC_PRECISION_FAST; }
 
 static bool cfg_ok(const epc_cfg* c) {
     if (!c) return false;
@@ -360,7 +360,7 @@ extern "C" int epc_net_pack_weights(const epc_cfg* cfg, const char* const* names
     float* P = (float*)packed;
     hipStream_t st = (hipStream_t)stream;
     const int nblocks = cfg->arch == EPC_ARCH_EPC_NET ? 4 : 2;
-    const int f16 = cfg_fast(cfg) ? 1 : 0;  // EPC-Net FAST: fp16 activations (common.h); otherwise split-bf16
+    const int f16 = cfg_fast(cfg) ? 1 : 0;  // FAST: fp16 activations (common.h); otherwise scaled split-fp16
     unsigned int* guard = (unsigned int*)(P + L.guard);
     {
         hipError_t e = hipMemsetAsync(guard, 0, 64 * sizeof(float), st);

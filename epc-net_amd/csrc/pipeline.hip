@@ -11,8 +11,8 @@ static int micro_batch(const epc_cfg* c, int num_clouds) {
     return num_clouds < mb ? num_clouds : mb;
 }
 
-// EPC-Net in EPC_PRECISION_FAST: fp16 rows / fragments between the stages; otherwise f32 tensors, split-bf16 kernels
-static bool fast_path(const epc_cfg* c) { return c->arch == EPC_ARCH_EPC_NET && c->precision == EPC_PRECISION_FAST; }
+// EPC_PRECISION_FAST (either model): fp16 rows / fragments between the stages; otherwise f32 tensors, f32-equivalent kernels
+static bool fast_path(const epc_cfg* c) { return c->precision == EPC_PRECISION_FAST; }
 
 struct WsLayout {
     size_t status, sorted, idx, cnt, kth, xa, xb, xa16, xb16, cat, feat, rnorm, assign, afrag, vlad, colss, apart, head, pooled, total;
@@ -32,17 +32,18 @@ static WsLayout ws_layout(const epc_cfg* c, int mb) {
     w.idx = take(M * EPC_KNN_CAP * 4);
     w.cnt = take(M * 4);
     w.kth = take(M * 4);
-    // EPC-Net: the block chain's tensors are fp16 rows (block.hip); EPC-Net-L: f32 rows
+    // FAST: the block chain's tensors are fp16 rows (block.hip); F32: f32 rows
     w.xa = w.xb = w.xa16 = w.xb16 = 0;
     const bool fast = fast_path(c);
+    const size_t ccat = c->arch == EPC_ARCH_EPC_NET ? 256 : 128;
     if (fast) {
         w.xa16 = take(M * 64 * 2);
         w.xb16 = take(M * 64 * 2);
-        w.cat = take(M * 256 * 2);
+        w.cat = take(M * ccat * 2);
     } else {
         w.xa = take(M * 64 * 4);
         w.xb = take(M * 64 * 4);
-        w.cat = take(M * (c->arch == EPC_ARCH_EPC_NET ? 256 : 128) * 4);
+        w.cat = take(M * ccat * 4);
     }
     w.feat = w.rnorm = w.assign = w.afrag = w.vlad = w.colss = w.apart = w.head = w.pooled = 0;
     if (c->arch == EPC_ARCH_EPC_NET) {
@@ -199,7 +200,10 @@ static int forward_pass(const epc_cfg* cfg, const char* pk, const float* pc, int
     } else {
         float* pooled = (float*)(ws + w.pooled);
         TRY(mark(prof, EPC_STAGE_CONV5, stream));
-        TRY(epc_conv5_maxpool_fwd(cat, ccat, pk + epc_net_packed_offset(cfg, 5), nc, n, pooled, stream));
+        if (f16)
+            TRY(epc_conv5_maxpool_f16_fwd(cat, ccat, pk + epc_net_packed_offset(cfg, 5), nc, n, pooled, stream));
+        else
+            TRY(epc_conv5_maxpool_fwd(cat, ccat, pk + epc_net_packed_offset(cfg, 5), nc, n, pooled, stream));
         TRY(mark(prof, EPC_STAGE_HEAD, stream));
         TRY(epc_fc_head_fwd(pooled, pk + epc_net_packed_offset(cfg, 6), nc, o, status, stream));
     }

@@ -17,7 +17,7 @@ ARCH_IDS = {"epc-net": L.EPC_ARCH_EPC_NET, "epc-net-l": L.EPC_ARCH_EPC_NET_L}
 DEFAULT_PARAMS = {"CLUSTER_SIZE": 64, "FEATURE_OUTPUT_DIM": 256, "KNN": 20, "INPUT_DIM": 3, "GROUPS": 4}
 # Arithmetic of the inference path when neither the engine nor params["PRECISION"] names one (include/epcnet.h:
 # EPC_PRECISION_*).  "f32" = the reference's class of arithmetic (float32 graph, models/epc-net.py:24-26) on split
-# half-precision MFMA; "fast" = EPC-Net's f16 + f6 path: an explicit opt-in for checkpoints it has been validated on
+# half-precision MFMA; "fast" = the f16 + f6 path (either model): an explicit opt-in for checkpoints it has been validated on
 # (tests/test_gpu_adversarial.py: it is wrong by 1e-2 on heavy-tailed weights while staying inside fp16's range, so
 # nothing selects it automatically).
 DEFAULT_PRECISION = "f32"
@@ -56,10 +56,12 @@ class InferenceEngine:
         # passes kept in flight on separate HIP streams (submit / long calls).  Default: two in the `fast` arithmetic (+12 %),
         # ONE in the f32-equivalent one -- its kernels fill every CU's registers and LDS (the persistent block kernel the whole
         # chip): a second lane only delays the first (bench.py `overlapped`: 55.6 k against 57.5 k clouds/s)
-        # EPC-Net-L: two lanes as well -- a batch of 256 clouds or more goes as 128-cloud halves in flight (the VALU-bound kNN of one
-        # half beside the L1-bound blocks / the matrix-bound conv5 of the other: +3-4 %, the same bits; `_forward`)
+        # EPC-Net-L, f32-equivalent: two lanes as well -- a batch of 256 clouds or more goes as 128-cloud halves in flight (the VALU-bound
+        # kNN of one half beside the L1-bound blocks / the matrix-bound conv5 of the other: +3-4 %, the same bits; `_forward`).  EPC-Net-L,
+        # `fast`: ONE lane -- the halves do not pay there (scripts/time_l_fast.py, two runs: -0.5 % and +0.6 % against one 256-cloud
+        # pass, inside the run-to-run spread), the same bits either way
         if in_flight is None:
-            in_flight = 2 if ((self.precision == "fast" and arch == "epc-net") or arch == "epc-net-l") else 1
+            in_flight = 2 if (arch == "epc-net") == (self.precision == "fast") else 1
         self.in_flight = max(1, min(int(in_flight), 8))
         self._lanes = None                                 # [(torch.cuda.Stream, workspace tensor or None, last event or None)]
         self._next_lane = 0
@@ -139,7 +141,7 @@ class InferenceEngine:
         epcnet.h EPC_STATUS_FP16_RANGE -- e.g. the zero-padding clouds of evaluate.py:425-430).  A cloud that is still NaN
         afterwards has a NaN / Inf coordinate -- the reference returns NaN for it as well."""
         out = self._forward(xyz, out, profile)
-        if check and self.arch == "epc-net" and self.resolved_precision == "fast":
+        if check and self.resolved_precision == "fast":
             bad = torch.isnan(out).any(dim=1).nonzero().flatten()
             if bad.numel():
                 if self._fallback is None:

@@ -26,7 +26,7 @@ EPC_KNN_CAP = 32
 EPC_ERANGE = -5
 STATUS_NAMES = {0: "EPC_OK", -1: "EPC_EINVAL", -2: "EPC_ENOMEM", -3: "EPC_EHIP", -4: "EPC_ENOTFOUND", -5: "EPC_ERANGE"}
 # epc_cfg.precision (include/epcnet.h): f32-equivalent arithmetic (conv layers scaled split-fp16 x3, assignment / aggregate
-# split-bf16 x3, f32 tensors in HBM except the 3-byte `feat` map) / EPC-Net's f16 + f6 fast arithmetic
+# split-bf16 x3, f32 tensors in HBM except the 3-byte `feat` map) / the f16 + f6 fast arithmetic (either model)
 EPC_PRECISION_F32 = 0
 EPC_PRECISION_FAST = 1
 PRECISION_IDS = {"f32": EPC_PRECISION_F32, "fast": EPC_PRECISION_FAST}
@@ -40,7 +40,7 @@ EXPORTS = [
     "epc_net_forward", "epc_net_forward_overlapped", "epc_net_last_status", "epc_conv5_assign_f32_fwd",
     "epc_vlad_aggregate_f32_fwd", "epc_knn_topk", "epc_knn_topk_conv1", "epc_knn_topk_form", "epc_knn_topk_conv1_form", "epc_knn_mask", "epc_conv1_fwd", "epc_proxyconv_block_fwd",
     "epc_conv5_assign_fwd", "epc_vlad_aggregate_fwd", "epc_vlad_head_workspace_bytes", "epc_vlad_head_fwd",
-    "epc_conv5_maxpool_fwd", "epc_fc_head_fwd", "epc_pairwise_topk", "epc_pairwise_topk_workspace_bytes",
+    "epc_conv5_maxpool_fwd", "epc_conv5_maxpool_f16_fwd", "epc_fc_head_fwd", "epc_pairwise_topk", "epc_pairwise_topk_workspace_bytes",
     "epc_pairwise_topk_ws", "epc_net_packed_offset",
     "epc_profile_create", "epc_profile_destroy", "epc_net_forward_profiled", "epc_profile_elapsed_ms",
     "epc_morton_sort",
@@ -118,6 +118,7 @@ _lib.epc_vlad_head_workspace_bytes.restype = c_size_t
 _lib.epc_vlad_head_workspace_bytes.argtypes = [c_int, c_int]
 _lib.epc_vlad_head_fwd.argtypes = [_P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]
 _lib.epc_conv5_maxpool_fwd.argtypes = [_P, c_int, _P, c_int, c_int, _P, _P]
+_lib.epc_conv5_maxpool_f16_fwd.argtypes = _lib.epc_conv5_maxpool_fwd.argtypes
 _lib.epc_fc_head_fwd.argtypes = [_P, _P, c_int, _P, _P, _P]
 _lib.epc_pairwise_topk.argtypes = [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P]
 _lib.epc_pairwise_topk_workspace_bytes.restype = c_size_t

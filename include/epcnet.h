@@ -40,7 +40,7 @@ typedef enum epc_status {
 
 /* Arithmetic of the inference path (epc_cfg.precision).  The reference computes in float32 (models/epc-net.py:24-26
  * tf.placeholder(tf.float32 ...), every op of utils/tf_util.py:52-107).
- *   EPC_PRECISION_F32  f32-equivalent (the default; EPC-Net-L always).  Every dense contraction is a SPLIT product on the
+ *   EPC_PRECISION_F32  f32-equivalent (the default).  Every dense contraction is a SPLIT product on the
  *                      16-bit matrix pipe with f32 accumulation -- three MFMA products (lo*hi + hi*lo + hi*hi) per algorithmic one:
  *                        - the conv layers (the 64 -> 64 layers of the ProxyConv blocks, conv5 of both models): SCALED split-fp16
  *                          ("f16x3").  Every row of the activation operand and every column of the BN-folded weight operand is
@@ -56,8 +56,10 @@ typedef enum epc_status {
  *                      3-byte values (the upper 24 bits of the float32, rounded) -- the 16 significant bits its only reader
  *                      keeps when it splits into bf16 hi + lo.  Measured 2-3e-7 from the float32 oracle on ordinary weights,
  *                      <= 1e-4 on the adversarial set (tests/test_gpu_adversarial.py).
- *   EPC_PRECISION_FAST EPC-Net only: one fp16 value per activation, weights fp16 hi + MX-fp6 lo, fp16 tensors in HBM
- *                      (DESIGN.md 2).  Folded weights must satisfy |W' * 256| <= 65504 (checked by
+ *   EPC_PRECISION_FAST both models: one fp16 value per activation, weights fp16 hi + MX-fp6 lo, fp16 tensors in HBM
+ *                      (DESIGN.md 2); for EPC-Net-L: fp16 rows through conv1 and the blocks, conv5 in f16 + f6 with the max
+ *                      over the cloud's points taken from the f32 accumulator, fc1 in f32.
+ *                      Folded weights must satisfy |W' * 256| <= 65504 (checked by
  *                      epc_net_pack_weights: EPC_ERANGE) and activations must stay inside fp16's range (checked by the
  *                      kernels per cloud: EPC_STATUS_FP16_RANGE, the cloud's descriptor is returned as NaN, never as a
  *                      wrong finite vector). */
@@ -83,7 +85,7 @@ typedef struct epc_cfg {
     int32_t output_dim;    /* FEATURE_OUTPUT_DIM, must be 256              */
     int32_t groups;        /* GROUPS, must divide 1024   (EPC-Net only)    */
     int32_t micro_batch;   /* clouds processed per internal pass (<= 0: library default) */
-    int32_t precision;     /* EPC_PRECISION_* (EPC-Net-L: ignored, always f32-equivalent) */
+    int32_t precision;     /* EPC_PRECISION_* (either model)               */
 } epc_cfg;
 
 const char* epc_last_error(void); /* thread-local, valid until the next failing call on this thread */
@@ -178,7 +180,7 @@ int epc_knn_topk(const float* xyz, int num_clouds, int n, int cap, int32_t* idx,
 int epc_knn_mask(const float* xyz, const float* kth, int num_clouds, int n, float* mask, void* stream);
 
 /* models/epc-net.py:66-69 conv1 (3->64) + folded BN + ReLU.  Writes x (M,64) f32 and/or x16 (M,64) fp16 (either may
- * be NULL): EPC-Net's blocks consume the fp16 rows, EPC-Net-L's the f32 rows. */
+ * be NULL): the EPC_PRECISION_FAST blocks consume the fp16 rows, the EPC_PRECISION_F32 ones the f32 rows. */
 int epc_conv1_fwd(const float* xyz, const void* packed_conv1, int num_points_total, float* x, void* x16, void* stream);
 /* epc_knn_topk and epc_conv1_fwd of the same (sorted) clouds in ONE launch: the kNN workgroup holds the cloud in LDS, so
  * conv1 costs it ~1.5 % more work instead of a launch of its own.  Bit-identical to the two separate calls.
@@ -204,7 +206,7 @@ int epc_knn_topk_conv1_form(const float* xyz, int num_clouds, int n, int cap, vo
  * models/epc-net.py:134).  Two forms, selected by x16 and matching the arch the weights were packed for:
  *   x16 == NULL (f32-equivalent pack of either model): f32 rows x -> out, x_next (f32); scaled split-fp16 (f16x3) MFMA
  *     layers, f32-accurate (EPC_PRECISION_F32 above).
- *   x16 != NULL (EPC-Net pack):   fp16 rows x16 -> out16, x_next16 (fp16; x, out, x_next are ignored): every tensor that
+ *   x16 != NULL (FAST pack):      fp16 rows x16 -> out16, x_next16 (fp16; x, out, x_next are ignored): every tensor that
  *     crosses HBM is fp16 and every MFMA operand is one fp16 value per activation against fp16 hi+lo weights; sums,
  *     mean, xm - x, t + xm and the accumulators are f32.  The roundings are independent per point and channel and
  *     average out in the VLAD aggregation (descriptor effect 6e-7). */
@@ -271,6 +273,12 @@ int epc_vlad_head_fwd(const float* V, const float* colss, const void* packed_hea
 /* models/epc-net-l.py:84-98: conv5 (128->1024)+BN+ReLU, global max over N, fc1 (1024->256)+BN+ReLU, L2. */
 int epc_conv5_maxpool_fwd(const float* cat, int cin, const void* packed_conv5, int num_clouds, int n,
                           float* pooled, void* stream);
+/* The same conv5 + max-pool in EPC_PRECISION_FAST (weights packed for that precision): cat16 (num_clouds * n, cin) fp16 -- the
+ * fast blocks' out16 -- against fp16 hi + MX-fp6 lo conv5 weights, f32 accumulation; bias, ReLU and the max over the cloud's n
+ * points are taken from the f32 accumulator, so pooled (num_clouds, 1024) is f32 and never rounded to fp16.  cin must be 128 and
+ * n a multiple of 32; pooled is overwritten. */
+int epc_conv5_maxpool_f16_fwd(const void* cat16, int cin, const void* packed_conv5, int num_clouds, int n, float* pooled,
+                              void* stream);
 int epc_fc_head_fwd(const float* pooled, const void* packed_fc, int num_clouds, float* out, const int32_t* status,
                     void* stream);
 
