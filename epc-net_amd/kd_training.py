@@ -41,29 +41,30 @@ class DistillStep(TrainStep):
         self.gamma = float(params.get("GAMMA", 0.0))
         self.feature_loss_when_unused = feature_loss_when_unused
 
-    def teacher_outputs(self, vecs, need_features: bool):
-        """kd_train.py:262-275 with is_training=False: (features or None, soft labels (rows, 256)); no gradients."""
+    def teacher_outputs(self, vecs, need_features: bool, graph=None):
+        """kd_train.py:262-275 with is_training=False: (features or None, soft labels (rows, 256)); no gradients.
+        ``graph``: the (sorted clouds, KnnGraph) a cloud bank assembled for ``vecs`` (TrainStep.step_ids)."""
         with torch.no_grad(), variable_scope(self.teacher_outer):
             if need_features:
-                fea, out = self.teacher.forward(vecs, False, bn_decay=None, params=self.params)
+                fea, out = self.teacher.forward(vecs, False, bn_decay=None, params=self.params, graph=graph)
             else:
                 fea, out = None, self.teacher.descriptors(vecs, self.params)
         return fea, out.reshape(-1, out.shape[-1])
 
-    def compute_loss(self, query, positives, negatives, other_neg, is_training: bool, bn_decay=None):
+    def compute_loss(self, query, positives, negatives, other_neg, is_training: bool, bn_decay=None, graph=None):
         p = self.params
         if self.loss_type not in ("square_error_sum", "square_error_mean"):
             raise NameError("name 'loss_fea' is not defined")            # kd_train.py:387 for the other LOSS_TYPEs
         vecs = torch.cat([query, positives, negatives, other_neg], 1)
         need_fea = self.gamma != 0.0 or self.feature_loss_when_unused
-        fea_t, soft_t = self.teacher_outputs(vecs, need_fea)
+        fea_t, soft_t = self.teacher_outputs(vecs, need_fea, graph)
         from . import ops
         fuse_was = ops.FUSE_TAIL_BACKWARD
         if self.gamma != 0.0:
             ops.FUSE_TAIL_BACKWARD = False      # the features get a second gradient (loss_fea): their backward cannot be pre-empted
         try:
             with variable_scope(self.outer):
-                fea_s, out_vecs = self.model.forward(vecs, is_training, bn_decay=bn_decay, params=p)     # :365
+                fea_s, out_vecs = self.model.forward(vecs, is_training, bn_decay=bn_decay, params=p, graph=graph)     # :365
         finally:
             ops.FUSE_TAIL_BACKWARD = fuse_was
         with variable_scope(self.outer):

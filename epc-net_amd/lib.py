@@ -61,6 +61,7 @@ EXPORTS = [
     "epc_hidden_proj_ok", "epc_hidden_proj_scratch_bytes", "epc_hidden_proj_fwd", "epc_hidden_proj_bwd",
     "epc_maxpool_points_fwd", "epc_maxpool_points_bwd", "epc_vlad_w2_grad", "epc_group_sum_fwd", "epc_group_sum_bwd",
     "epc_hidden_tail_ok", "epc_hidden_tail_fwd", "epc_hidden_tail_bwd",
+    "epc_bank_record_bytes", "epc_bank_store", "epc_bank_assemble",
 ]
 EPC_NUM_STAGES = 10
 STAGE_NAMES = ["sort", "knn", "conv1", "block1", "block2", "block3", "block4", "conv5", "aggregate", "head"]
@@ -279,6 +280,10 @@ _lib.epc_maxpool_points_bwd.argtypes = [_P, _P, c_int, c_int, c_int, _P, _P]
 _lib.epc_vlad_w2_grad.argtypes = [_P, _P, c_int, c_int, c_int, _P, _P]
 _lib.epc_group_sum_fwd.argtypes = [_P, c_int, c_int, c_int, _P, _P]
 _lib.epc_group_sum_bwd.argtypes = [_P, c_int, c_int, c_int, _P, _P]
+_lib.epc_bank_record_bytes.restype = c_size_t
+_lib.epc_bank_record_bytes.argtypes = [c_int, c_int]
+_lib.epc_bank_store.argtypes = [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
+_lib.epc_bank_assemble.argtypes = [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
 _lib.epc_profile_create.argtypes = [POINTER(_P)]
 _lib.epc_profile_destroy.argtypes = [_P]
 _lib.epc_net_forward_profiled.argtypes = [POINTER(EpcCfg), _P, _P, c_int, _P, _P, c_size_t, _P, _P]

@@ -24,7 +24,7 @@ def declare_variables(params, num_points, backbone_scope='fastdgcnn'):
         tf_util.declare_fully_connected('fc1', 1024, params["FEATURE_OUTPUT_DIM"])
 
 
-def forward(point_cloud, is_training, bn_decay=None, params=None):
+def forward(point_cloud, is_training, bn_decay=None, params=None, graph=None):
     """models/epc-net-l.py:29-102."""
     if params is None:
         raise TypeError("forward() needs the config dict as `params` (models/epc-net-l.py:37-40)")
@@ -38,22 +38,26 @@ def forward(point_cloud, is_training, bn_decay=None, params=None):
     declare_variables(params, num_points)
     pc = point_cloud.reshape(batch_num_queries * num_pointclouds_per_query, num_points, INPUT_DIM)
     if is_training:
-        output = forward_ops(pc, True, bn_decay, params)
+        output = forward_ops(pc, True, bn_decay, params, graph=graph)
     else:
         output = engine_for(ARCH, params).forward(pc)
     return output.reshape(batch_num_queries, num_pointclouds_per_query, OUTPUT_DIM)
 
 
-def forward_ops(point_cloud, is_training, bn_decay, params, backbone_scope='fastdgcnn', return_features=False):
+def forward_ops(point_cloud, is_training, bn_decay, params, backbone_scope='fastdgcnn', return_features=False, graph=None):
     """models/epc-net-l.py:44-98 op by op on the differentiable operators (training path / unfused cross-check)."""
     import torch
     from .. import loupe as lp
     from .. import ops
     num_points = int(point_cloud.shape[1])
     k = params["KNN"]
-    point_cloud = ops.morton_sort(point_cloud)           # re-ordering only (permutation-invariant network)
+    if graph is not None:                                # (sorted clouds, their finished KnnGraph): ops.CloudBank.assemble
+        point_cloud, dpist = graph
+    else:
+        point_cloud = ops.morton_sort(point_cloud)       # re-ordering only (permutation-invariant network)
     with variable_scope(backbone_scope):
-        dpist = ops.KnnGraph(point_cloud)
+        if graph is None:
+            dpist = ops.KnnGraph(point_cloud)
         conv = lambda x, n, scope: tf_util.conv1d(x, n, 1, padding='VALID', stride=1, bn=True, is_training=is_training,
                                                   scope=scope, bn_decay=bn_decay)
         # conv1 .. conv2_b and the concat of the two block outputs (:62-83): one fused chain in training (tf_util.proxyconv_backbone)

@@ -34,7 +34,7 @@ def declare_variables(params, num_points, backbone_scope='fastdgcnn'):
                   add_batch_norm=True, is_training=False).declare_variables()
 
 
-def forward(point_cloud, is_training, bn_decay=None, params=None):
+def forward(point_cloud, is_training, bn_decay=None, params=None, graph=None):
     """models/epc-net.py:29-157.
     INPUT : batch_num_queries X num_pointclouds_per_query X num_points_per_pointcloud X input_dim
     OUTPUT: batch_num_queries X num_pointclouds_per_query X output_dim ("last_output")."""
@@ -51,13 +51,13 @@ def forward(point_cloud, is_training, bn_decay=None, params=None):
     declare_variables(params, num_points)
     pc = point_cloud.reshape(batch_num_queries * num_pointclouds_per_query, num_points, INPUT_DIM)
     if is_training:
-        output = forward_ops(pc, True, bn_decay, params)
+        output = forward_ops(pc, True, bn_decay, params, graph=graph)
     else:
         output = engine_for(ARCH, params).forward(pc)
     return output.reshape(batch_num_queries, num_pointclouds_per_query, OUTPUT_DIM)
 
 
-def forward_ops(point_cloud, is_training, bn_decay, params, backbone_scope='fastdgcnn', return_features=False):
+def forward_ops(point_cloud, is_training, bn_decay, params, backbone_scope='fastdgcnn', return_features=False, graph=None):
     """The same graph built op by op from the differentiable operators, line for line as models/epc-net.py:62-155.
     Used for is_training=True (batch statistics, EMA updates, gradients); with is_training=False it is an
     independent (unfused) second implementation of the inference path (tests cross-check the two).
@@ -68,9 +68,13 @@ def forward_ops(point_cloud, is_training, bn_decay, params, backbone_scope='fast
     from .. import ops
     num_points = int(point_cloud.shape[1])
     k = params["KNN"]
-    point_cloud = ops.morton_sort(point_cloud)           # re-ordering only (permutation-invariant network)
+    if graph is not None:                                # (sorted clouds, their finished KnnGraph): ops.CloudBank.assemble
+        point_cloud, dpist = graph
+    else:
+        point_cloud = ops.morton_sort(point_cloud)       # re-ordering only (permutation-invariant network)
     with variable_scope(backbone_scope):
-        dpist = ops.KnnGraph(point_cloud)                    # tf_util.pairwise_distance_mask in index form (:63)
+        if graph is None:
+            dpist = ops.KnnGraph(point_cloud)                # tf_util.pairwise_distance_mask in index form (:63)
         # conv1 .. conv4_b and the concat of the four block outputs (:66-134): one fused chain in training (tf_util.proxyconv_backbone)
         x = tf_util.proxyconv_backbone(point_cloud, dpist, k, 4, bn_decay=bn_decay, is_training=is_training,
                                        head_follows=not return_features)

@@ -20,7 +20,7 @@ def declare_variables(params, num_points):
     _base.declare_variables(params, num_points, backbone_scope=BACKBONE_SCOPE)
 
 
-def forward(point_cloud, is_training, bn_decay=None, params=None):
+def forward(point_cloud, is_training, bn_decay=None, params=None, graph=None):
     """models/kd_epc-net.py:29-158 -> (point features (B*P*N, 1024), output (B, P, FEATURE_OUTPUT_DIM))."""
     if params is None:
         raise TypeError("forward() needs the config dict as `params`")
@@ -31,7 +31,7 @@ def forward(point_cloud, is_training, bn_decay=None, params=None):
         raise ValueError("last dimension %d != INPUT_DIM %d" % (dim, params["INPUT_DIM"]))
     declare_variables(params, n)
     feats, output = _base.forward_ops(point_cloud.reshape(b * p, n, dim), bool(is_training), bn_decay, params,
-                                      backbone_scope=BACKBONE_SCOPE, return_features=True)
+                                      backbone_scope=BACKBONE_SCOPE, return_features=True, graph=graph)
     return feats, output.reshape(b, p, params["FEATURE_OUTPUT_DIM"])
 
 

@@ -480,6 +480,115 @@ class KnnGraph:
         self._scratch = cursor
         return rdeg, roff, cursor, rlist, oc, ol
 
+    @classmethod
+    def from_parts(cls, xyz, kth, idx, cnt, transposed, overflow):
+        """A graph over tensors somebody else produced (CloudBank.assemble): ``xyz`` (clouds, n, 3) as the lists were built on it,
+        ``kth`` / ``idx`` / ``cnt`` as tf_util.knn_index returns them, ``transposed`` = (rdeg, roff, rlist), ``overflow`` =
+        (ovf_cnt, ovf_list).  ``transposed()`` and ``overflow()`` return them; nothing is launched."""
+        g = cls.__new__(cls)
+        g.xyz = xyz
+        g.num_clouds, g.n = int(xyz.shape[0]), int(xyz.shape[1])
+        g.kth, g.idx, g.cnt = kth, idx, cnt
+        g._transposed, g._overflow = tuple(transposed), tuple(overflow)
+        return g
+
+
+class CloudBank:
+    """A training set resident in device memory: one record per cloud holding the cloud in Hilbert order and its finished kNN
+    graph (include/epcnet.h, "Cloud bank"), so that a training step assembles its batch from record ids in ONE launch instead of
+    re-running sort, kNN and transposition -- all functions of one cloud's coordinates (utils/tf_util.py:647-666).  What
+    ``assemble`` returns equals ``morton_sort`` + ``KnnGraph`` + ``transposed()`` + ``overflow()`` on the same clouds bit for bit.
+    Records are immutable once added.  ``capacity`` records of ``bytes_per_cloud`` bytes are allocated at construction."""
+
+    ADD_CHUNK = 64            # clouds per pass of ``add`` (bounds its temporaries: 64 x 1.2 MB at 4096 points)
+    MAX_IDS = 2048            # ids per ``assemble`` (the bank's status words: one bit per slot)
+
+    def __init__(self, num_points: int, capacity: int, device):
+        L.require_gpu()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise EpcNetError(-1, "a CloudBank lives on a ROCm device: the HIP path has no CPU fallback")
+        self.n, self.capacity, self.cap = int(num_points), int(capacity), L.EPC_KNN_CAP
+        self.bytes_per_cloud = int(L.lib().epc_bank_record_bytes(self.n, self.cap))
+        if self.bytes_per_cloud == 0 or self.n > 8192:      # (8192: the kNN entry's bound; the record format itself allows 65536)
+            raise EpcNetError(-1, "CloudBank: unsupported cloud size %d (a multiple of 8, at most 8192 points)" % self.n)
+        if self.capacity <= 0:
+            raise EpcNetError(-1, "CloudBank: capacity must be positive")
+        self.records = torch.zeros(self.capacity * self.bytes_per_cloud, dtype=torch.uint8, device=self.device)
+        self.status = torch.zeros(self.MAX_IDS // 32, dtype=torch.int32, device=self.device)     # sticky bad-id bits of assemble
+        self._store_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._size = 0
+
+    def __len__(self) -> int:
+        return self._size
+
+    def add(self, xyz):
+        """Append the clouds ``xyz`` (M, n, 3) (a device tensor); returns their ids as a list of ints.  Runs the existing sort / kNN /
+        transposition in chunks of at most ADD_CHUNK clouds and stores the narrowed records."""
+        if not torch.is_tensor(xyz) or not xyz.is_cuda:
+            raise EpcNetError(-1, "CloudBank.add: the clouds must live on a ROCm device (no CPU fallback)")
+        if xyz.dim() != 3 or int(xyz.shape[1]) != self.n or int(xyz.shape[2]) != 3:
+            raise EpcNetError(-1, "CloudBank.add: expected (M, %d, 3), got %s" % (self.n, tuple(xyz.shape)))
+        M = int(xyz.shape[0])
+        if self._size + M > self.capacity:
+            raise EpcNetError(-2, "CloudBank.add: %d clouds do not fit (%d of %d records taken)" % (M, self._size, self.capacity))
+        first = self._size
+        for a in range(0, M, self.ADD_CHUNK):
+            part = morton_sort(xyz[a:a + self.ADD_CHUNK])
+            g = KnnGraph(part)
+            rdeg, roff, rlist = g.transposed()
+            oc, ol = g.overflow()
+            self._store_status.zero_()
+            L.check(L.lib().epc_bank_store(self.records.data_ptr(), self.capacity, self._size, g.num_clouds, self.n, self.cap,
+                                           part.data_ptr(), g.kth.data_ptr(), g.cnt.data_ptr(), g.idx.data_ptr(), rdeg.data_ptr(),
+                                           roff.data_ptr(), rlist.data_ptr(), oc.data_ptr(), ol.data_ptr(),
+                                           self._store_status.data_ptr(), _st()))
+            if int(self._store_status.item()) != 0:
+                raise EpcNetError(-1, "CloudBank.add: a graph of clouds %d..%d does not fit the 16-bit record format; nothing "
+                                      "of that chunk was stored" % (a, a + g.num_clouds - 1))
+            self._size += g.num_clouds
+        return list(range(first, first + M))
+
+    def buffers(self, num_ids: int):
+        """The preallocated outputs of ``assemble`` for ``num_ids`` ids: pass them as ``out`` so that every call -- every replay of a
+        captured graph -- writes the same addresses."""
+        T, n, cap, dev = int(num_ids), self.n, self.cap, self.device
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        return {"xyz": torch.empty((T, n, 3), dtype=torch.float32, device=dev),
+                "kth": torch.empty((T, n), dtype=torch.float32, device=dev), "cnt": i32(T, n), "idx": i32(T, n, cap),
+                "rdeg": i32(T * n), "roff": i32(T * n), "rlist": i32(T * n * cap), "ovf_cnt": i32(T), "ovf_list": i32(T, n),
+                "poison": torch.zeros((), dtype=torch.float32, device=dev)}
+
+    def assemble(self, ids, out=None):
+        """(xyz_sorted (T, n, 3), KnnGraph) of the records ``ids``: T int32 in DEVICE memory (repeats allowed), read when the kernel
+        runs.  One launch (epc_bank_assemble).  An id outside the bank gives that slot NaN coordinates and an empty graph, sets its
+        bit in the bank's status words (see ``check``) and makes ``out["poison"]`` (0-d float, 0 otherwise) NaN for this call."""
+        if not torch.is_tensor(ids) or not ids.is_cuda or ids.dtype != torch.int32 or not ids.is_contiguous():
+            raise EpcNetError(-1, "CloudBank.assemble: ids must be a contiguous int32 tensor on the ROCm device (no CPU fallback)")
+        T = int(ids.numel())
+        if not 0 < T <= self.MAX_IDS:
+            raise EpcNetError(-1, "CloudBank.assemble: between 1 and %d ids per call" % self.MAX_IDS)
+        o = out if out is not None else self.buffers(T)
+        if int(o["xyz"].shape[0]) != T:
+            raise EpcNetError(-1, "CloudBank.assemble: `out` was made for %d ids, got %d" % (int(o["xyz"].shape[0]), T))
+        if self._size == 0:
+            raise EpcNetError(-1, "CloudBank.assemble: the bank is empty")
+        L.check(L.lib().epc_bank_assemble(self.records.data_ptr(), self._size, ids.data_ptr(), T, self.n, self.cap,
+                                          o["xyz"].data_ptr(), o["kth"].data_ptr(), o["cnt"].data_ptr(), o["idx"].data_ptr(),
+                                          o["rdeg"].data_ptr(), o["roff"].data_ptr(), o["rlist"].data_ptr(), o["ovf_cnt"].data_ptr(),
+                                          o["ovf_list"].data_ptr(), self.status.data_ptr(), o["poison"].data_ptr(), _st()))
+        graph = KnnGraph.from_parts(o["xyz"], o["kth"], o["idx"], o["cnt"], (o["rdeg"], o["roff"], o["rlist"]),
+                                    (o["ovf_cnt"], o["ovf_list"]))
+        return o["xyz"], graph
+
+    def check(self) -> None:
+        """Read the status words of every ``assemble`` since the last check (a device synchronisation); raises EpcNetError naming
+        the slots that held an id outside the bank, and clears the words."""
+        words = self.status.cpu().tolist()
+        bad = [32 * w + b for w, v in enumerate(words) for b in range(32) if (v >> b) & 1]
+        if bad:
+            self.status.zero_()
+            raise EpcNetError(-1, "CloudBank: assemble was given an id outside [0, %d) in slot(s) %s" % (self._size, bad))
 
 
 class NeighbourMean(torch.autograd.Function):

@@ -23,7 +23,7 @@ import torch
 
 from . import tf_bundle
 from .retrieval import get_latent_vectors
-from .utils.loading_pointclouds import NUM_POINTS, get_query_tuple, get_random_hard_negatives
+from .utils.loading_pointclouds import NUM_POINTS, get_query_tuple, get_query_tuple_ids, get_random_hard_negatives
 from .variables import variable_scope
 
 SAMPLED_NEG = 4000     # train.py:340
@@ -34,9 +34,14 @@ EVAL_BATCHES = 5       # train.py:527
 class Trainer:
     def __init__(self, step, train_queries: Dict[int, dict], train_data: np.ndarray,
                  test_queries: Optional[Dict[int, dict]] = None, test_data: Optional[np.ndarray] = None,
-                 save_path: Optional[str] = None, logger: Optional[logging.Logger] = None, graph: bool = False):
+                 save_path: Optional[str] = None, logger: Optional[logging.Logger] = None, graph: bool = False,
+                 bank: bool = False):
         """``step``: a TrainStep / DistillStep; ``*_queries``: the pickles of generate_training_tuples (key -> {'query',
-        'positives', 'negatives'}); ``*_data``: (T, 4096, INPUT_DIM) float32 arrays in key order (train.py:159-190)."""
+        'positives', 'negatives'}); ``*_data``: (T, 4096, INPUT_DIM) float32 arrays in key order (train.py:159-190).
+        ``bank=True``: ``train_data`` is uploaded ONCE into an ``ops.CloudBank`` (sorted clouds + finished kNN graphs, ~0.65 MB per
+        4096-point cloud of device memory) and the loop steps on cloud ids (``step.step_ids``): no per-step tuple assembly and
+        upload on the host, no per-step sort / kNN / transposition on the device; same tuples, same losses, bit for bit.  It serves
+        the unaugmented protocol of train.py:388.  ``evaluate_loss``, the mining and the descriptor cache keep reading the arrays."""
         self.step = step
         self.params = step.params
         self.TRAINING_QUERIES, self.train_data = train_queries, train_data
@@ -54,6 +59,20 @@ class Trainer:
         self.num_points = int(p.get("NUM_POINTS", NUM_POINTS))
         self.device = step.store.device
         self.history: List[dict] = []
+        self.bank = self._build_bank(train_data) if bank else None
+
+    def _build_bank(self, data: np.ndarray):
+        """Upload ``data`` (T, n, 3) into a CloudBank, in slices that bound the staging copy; logs the one-time cost."""
+        import time
+        from . import ops
+        t0 = time.perf_counter()
+        bank = ops.CloudBank(int(data.shape[1]), int(data.shape[0]), self.device)
+        for a in range(0, int(data.shape[0]), 1024):
+            bank.add(torch.as_tensor(data[a:a + 1024], dtype=torch.float32).to(self.device))
+        torch.cuda.synchronize(self.device)
+        self.log.info("Cloud bank: %d clouds, %.1f MB on %s (%d bytes per cloud), built in %.2f s", len(bank),
+                      len(bank) * bank.bytes_per_cloud / 1e6, self.device, bank.bytes_per_cloud, time.perf_counter() - t0)
+        return bank
 
     # ---- inference with the current weights ------------------------------------------------------------------------
     def _engine(self):
@@ -93,6 +112,21 @@ class Trainer:
         dev = lambda a: torch.as_tensor(a, dtype=torch.float32).to(self.device)
         return (dev(q), dev(pos), dev(neg), dev(o)), ""
 
+    def _tuple_ids(self, keys, queries, hard_negs_of: Optional[Callable[[int], List[int]]]):
+        """``_tuples`` for the cloud bank: the same draws (``random`` consumed identically) and the same skips, as id arrays
+        (B,1), (B,P), (B,Nn), (B,1) for ``step.step_ids``.  Returns (arrays or None, reason)."""
+        tuples = []
+        for key in keys:
+            if len(queries[key]["positives"]) < self.P:
+                return None, "FAULTY TUPLE"
+            hard = hard_negs_of(key) if hard_negs_of is not None else []
+            tuples.append(get_query_tuple_ids(int(key), queries[key], self.P, self.N, queries, hard_neg=hard, other_neg=True))
+            if len(tuples[-1][3]) != 1:                                                          # train.py:401
+                return None, "NO OTHER NEG"
+        as_ids = lambda rows: np.asarray(rows, dtype=np.int64).reshape(len(tuples), -1)
+        return (as_ids([[t[0]] for t in tuples]), as_ids([t[1] for t in tuples]), as_ids([t[2] for t in tuples]),
+                as_ids([t[3] for t in tuples])), ""
+
     def _hard_negatives(self, key: int) -> List[int]:
         """train.py:373-377 / :390-395 (the three cache states)."""
         if len(self.TRAINING_LATENT_VECTORS) == 0:
@@ -123,14 +157,22 @@ class Trainer:
         for i in range(iter_num if max_iters is None else min(iter_num, max_iters)):
             base = (i * world + rank) * self.B
             keys = idxs[base:base + self.B]
-            batch, why = self._tuples(keys, self.TRAINING_QUERIES, self.train_data, self._hard_negatives)
+            if self.bank is not None:
+                batch, why = self._tuple_ids(keys, self.TRAINING_QUERIES, self._hard_negatives)
+            else:
+                batch, why = self._tuples(keys, self.TRAINING_QUERIES, self.train_data, self._hard_negatives)
             if not D.all_true(batch is not None, self.device):
                 # a rank that skipped alone would leave the others waiting in the gradient all-reduce
                 self.log.info("Epoch: [%d/%d][%d/%d] %s!!!", epoch, self.max_epoch, i + 1, iter_num,
                               why or "another rank drew a faulty tuple")
                 continue
-            loss, lr, _ = self.step.step(*batch, epoch=epoch, graph=self.graph) if self.graph else self.step.step(*batch, epoch=epoch)
+            if self.bank is not None:
+                loss, lr, _ = self.step.step_ids(self.bank, *batch, epoch=epoch, graph=self.graph)
+            else:
+                loss, lr, _ = self.step.step(*batch, epoch=epoch, graph=self.graph) if self.graph else self.step.step(*batch, epoch=epoch)
             losses.append(float(loss))
+            if not np.isfinite(losses[-1]) and self.bank is not None:
+                self.bank.check()       # an id outside the bank (a query dict that does not match train_data) raises here, naming the slot
             if not np.isfinite(losses[-1]):
                 # a persistent chain launch that was abandoned (a grid barrier ran out of its spin budget) leaves NaN: say so, and reset
                 from . import ops

@@ -164,14 +164,61 @@ class TrainStep:
         # (the graphed path returns the replayed graph's static output buffer: clone it, or the next replay overwrites it)
         return (loss.detach().clone() if graph else loss.detach()), lr, bn_decay
 
+    def step_ids(self, bank, query_ids, positive_ids, negative_ids, other_ids, epoch: int = 0, graph: bool = False):
+        """``step`` on clouds of a device-resident ``ops.CloudBank``, named by their record ids: (B,1), (B,P), (B,Nn), (B,1) integer
+        tensors or arrays.  The batch -- sorted clouds and their finished kNN graph -- is assembled from the bank in one launch
+        (epc_bank_assemble) instead of being sorted, searched and transposed again; every later kernel reads the same bits, so the
+        step is the one ``step`` runs on the same clouds.  ``graph=True``: the ids live in a static device buffer that is refreshed
+        before every replay, like the schedule values, and the assemble launch is INSIDE the captured graph (the first of the three
+        in the data-parallel form).  Unaugmented tuples only (the reference's protocol, train.py:388): a rotated or jittered cloud
+        has another graph -- use ``step``.  An id outside the bank gives a NaN loss (and a step on an empty cloud in that slot: go back
+        to the state before it); ``bank.check()`` names the slot."""
+        import numpy as np
+        p = self.params
+        parts = [np.asarray(x.detach().cpu() if torch.is_tensor(x) else x).astype(np.int64) for x in
+                 (query_ids, positive_ids, negative_ids, other_ids)]
+        B = int(parts[0].shape[0])
+        if any(x.ndim != 2 or x.shape[0] != B for x in parts) or parts[0].shape[1] != 1 or parts[3].shape[1] != 1:
+            raise ValueError("step_ids: ids must be (B,1), (B,P), (B,Nn), (B,1); got %s" % ([x.shape for x in parts],))
+        ids = np.ascontiguousarray(np.concatenate(parts, 1).reshape(-1)).astype(np.int32)       # train.py:252's order, per query
+        self._ensure_built(bank.n)
+        bn_decay = get_bn_decay(self.global_step, p.get("BATCH_NUM_QUERIES", B), p.get("DECAY_STEP", 200000))
+        lr = get_learning_rate(epoch, p.get("BASE_LEARNING_RATE", 5e-5))
+        t = self.global_step + 1
+        sizes = [int(x.shape[1]) for x in parts]
+        if graph:
+            loss = self._graphed_step(None, None, None, None, lr, bn_decay, t, bank=(bank, torch.from_numpy(ids), B, sizes))
+            src = self._graph["source"]
+        else:
+            src = self._bank_source(bank, ids.size, B, sizes, bank.device)
+            src["ids"].copy_(torch.from_numpy(ids))
+            loss = self._eager_step(*src["in"], lr, bn_decay, t, source=src)
+        self.store.bump(self.outer or None)
+        self.global_step += 1
+        # The returned loss = the step's loss + the assemble launch's verdict (0, or NaN when an id was outside the bank): the NaN
+        # coordinates of such a slot alone do not reach the loss (the ReLUs and hinges are fmaxf).  One launch, where ``step`` clones
+        # the replayed graph's static loss buffer; the step's own arithmetic is untouched.
+        return loss.detach() + src["out"]["poison"], lr, bn_decay
+
+    @staticmethod
+    def _bank_source(bank, num_ids, B, sizes, dev):
+        """The static buffers of a bank-fed step: the id buffer, the outputs of ``bank.assemble`` and the four input tensors as
+        dim-1 slices of the assembled (B, 1 + P + Nn + 1, n, 3) coordinates (train.py:252's concat is then that buffer itself)."""
+        out = bank.buffers(num_ids)
+        joined = out["xyz"].view(B, num_ids // B, bank.n, 3)
+        return {"bank": bank, "ids": torch.zeros(num_ids, dtype=torch.int32, device=dev), "out": out,
+                "in": list(torch.split(joined, sizes, 1))}
+
     # -- the three phases of a step ------------------------------------------------------------------------------------
-    def _forward_backward(self, query, positives, negatives, other_neg, bn_decay, between=None):
+    def _forward_backward(self, query, positives, negatives, other_neg, bn_decay, between=None, source=None):
         """Forward in training mode, loss, backward, and the moving-average updates of this step (UPDATE_OPS,
         train.py:275-277).  Returns (loss, gradients in trainable_names() order).
         ``between`` (data-parallel steps): the backward is cut at the backbone's output (tf_util.BACKBONE_TAP) -- first the head
         (loss -> VLAD -> conv5: every gradient above the cut, 95 % of the bytes), then ``between(head_names, head_grads)`` is called
         (it packs them and starts their exchange), then the backbone's backward runs under that exchange.  Same kernels in the same
-        order as the uncut backward: same bits."""
+        order as the uncut backward: same bits.
+        ``source`` (step_ids): the buffers of ``_bank_source`` -- the four inputs are views of its assembled coordinates, which the
+        assemble launch fills HERE (inside whatever capture is open) together with the graph the model then does not rebuild."""
         from .utils import tf_util
         from .loupe import SLIM_DECAY
         names = self.trainable_names()
@@ -181,7 +228,12 @@ class TrainStep:
         tf_util.BACKBONE_TAP = None
         prev = ops.set_gemm_precision(self.precision)
         try:
-            loss = self.compute_loss(query, positives, negatives, other_neg, True, bn_decay)
+            if source is not None:
+                with torch.no_grad():
+                    assembled = source["bank"].assemble(source["ids"], out=source["out"])
+                loss = self.compute_loss(query, positives, negatives, other_neg, True, bn_decay, graph=assembled)
+            else:
+                loss = self.compute_loss(query, positives, negatives, other_neg, True, bn_decay)
             tap = tf_util.BACKBONE_TAP
             if between is not None and tap is not None and tap.requires_grad:
                 # Which variables lie below the cut is a property of the GRAPH: those the backbone's output depends on
@@ -343,10 +395,10 @@ class TrainStep:
         else:
             dist.all_reduce(ex["flat"], op=dist.ReduceOp.SUM)
 
-    def _eager_step(self, query, positives, negatives, other_neg, lr, bn_decay, t):
+    def _eager_step(self, query, positives, negatives, other_neg, lr, bn_decay, t, source=None):
         from . import distributed as D
         if not D.collectives_active():
-            loss, grads = self._forward_backward(query, positives, negatives, other_neg, bn_decay)
+            loss, grads = self._forward_backward(query, positives, negatives, other_neg, bn_decay, source=source)
             self._apply(grads, lr, t)
             return loss
         # Data parallelism over tuples: every rank its own tuple and batch statistics; gradients and moving statistics
@@ -360,7 +412,7 @@ class TrainStep:
             pending.append(dist.all_reduce(ex["flat"][:ex["head_end"]], op=dist.ReduceOp.SUM, async_op=True))
 
         loss, grads = self._forward_backward(query, positives, negatives, other_neg, bn_decay,
-                                             between=between if self.overlap_exchange else None)
+                                             between=between if self.overlap_exchange else None, source=source)
         ex = self._exchange_layout()
         self._pack_rest(ex, grads, bool(pending))
         self._exchange_rest(ex, bool(pending))
@@ -387,99 +439,125 @@ class TrainStep:
         out += [self.m[n] for n in self.trainable_names()] + [self.v[n] for n in self.trainable_names()]
         return out
 
-    def _graphed_step(self, query, positives, negatives, other_neg, lr, bn_decay, t):
+    def _graphed_step(self, query, positives, negatives, other_neg, lr, bn_decay, t, bank=None):
+        """``bank`` (step_ids): (CloudBank, ids (T,) int32 on the host, B, [1, P, Nn, 1]) instead of the four tensors."""
         from . import distributed as D
         inputs = (query, positives, negatives, other_neg)
-        shapes = tuple(tuple(x.shape) for x in inputs)
+        if bank is not None:
+            shapes = ("ids", id(bank[0]), bank[2], tuple(bank[3]))
+        else:
+            shapes = tuple(tuple(x.shape) for x in inputs)
         dp = D.collectives_active()
         g = self._graph
-        if g is None or g["shapes"] != shapes or g["dp"] != dp:
+        if (g is None or g["shapes"] != shapes or g["dp"] != dp) and bank is not None:
+            dev = bank[0].device
+            src = self._bank_source(bank[0], int(bank[1].numel()), bank[2], bank[3], dev)
+            # "joined" = the assembled coordinates (the device the replays are synchronised on is read from it)
+            g = {"shapes": shapes, "dp": dp, "joined": src["out"]["xyz"], "in": src["in"], "source": src,
+                 "lr_t": torch.zeros(1, dtype=torch.float32, device=dev),
+                 "bn_decay": torch.zeros((), dtype=torch.float32, device=dev)}
+            src["ids"].copy_(bank[1])
+            self._capture_step(g, dev, dp, lr, bn_decay, t)
+        elif g is None or g["shapes"] != shapes or g["dp"] != dp:
             dev = query.device
             # the four inputs are slices of ONE buffer in train.py:252's order, so that its concat is the buffer itself
             joined = torch.empty((query.shape[0], sum(s[1] for s in shapes)) + tuple(query.shape[2:]), dtype=query.dtype,
                                  device=dev)
             g = {"shapes": shapes, "dp": dp, "joined": joined, "in": list(torch.split(joined, [s[1] for s in shapes], 1)),
                  "lr_t": torch.zeros(1, dtype=torch.float32, device=dev),
-                 "bn_decay": torch.zeros((), dtype=torch.float32, device=dev)}
+                 "bn_decay": torch.zeros((), dtype=torch.float32, device=dev), "source": None}
             for dst, src in zip(g["in"], inputs):
                 dst.copy_(src)
-            g["lr_t"].fill_(self._lr_t(lr, t))
-            g["bn_decay"].fill_(bn_decay)
-            # warm-up on a side stream (lazy allocations, kernel attributes), on a snapshot of the state that is restored.
-            # No collective here: every rank restores its own snapshot, so the ranks stay in step.
-            snap = [x.detach().clone() for x in self._state_tensors()]
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                cut = []
-                loss, grads = self._forward_backward(*g["in"], g["bn_decay"],
-                                                     between=(lambda hn, hg: (self._pack_head(self._exchange_layout(), hn, hg), cut.append(1)))
-                                                     if dp and self.overlap_exchange else None)
-                if dp:
-                    self._pack_rest(self._exchange_layout(), grads, bool(cut))
-                    grads = self._unpack_mean(self._exchange_layout(), 1)
-                self._apply(grads, g["lr_t"], t)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            ex = self._exchange_layout() if dp else None      # (after the warm-up's graph walk: the split the captures will see)
-            with torch.no_grad():
-                for x, s0 in zip(self._state_tensors(), snap):
-                    x.copy_(s0)
-            for name in self.trainable_names():
-                self.store.vars[name].grad = None
-            g["graph"] = torch.cuda.CUDAGraph()
-            if not dp:
-                with torch.cuda.graph(g["graph"]):
-                    g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"])
-                    self._apply(grads, g["lr_t"], t)
-            else:
-                # Data-parallel: [forward, head backward, pack head] | RCCL (head, asynchronous) | [backbone backward, moving averages,
-                # pack rest] | RCCL (rest) | [mean, unpack, Adam] -- the captures end and begin INSIDE the step, at the cut of its
-                # backward (the `between` callback runs on this thread, between two autograd calls).
-                ws = D.world()[1]
-                g["graph_mid"] = torch.cuda.CUDAGraph() if self.overlap_exchange else None
-                g["graph2"] = torch.cuda.CUDAGraph()
-                g["cut"] = False
-                torch.cuda.synchronize(dev)
-                cap = torch.cuda.Stream(device=dev)
-                cap.wait_stream(torch.cuda.current_stream(dev))
-
-                open_graph = [None]        # the graph whose capture is open RIGHT NOW: the only one a failure may end
-
-                def begin(graph, **kw):
-                    graph.capture_begin(**kw)
-                    open_graph[0] = graph
-
-                def end():
-                    graph, open_graph[0] = open_graph[0], None
-                    if graph is not None:
-                        graph.capture_end()
-
-                def between(hn, hg):
-                    self._pack_head(ex, hn, hg)
-                    end()
-                    begin(g["graph_mid"], pool=g["graph"].pool())
-                    g["cut"] = True
-
-                with torch.cuda.stream(cap):
-                    try:
-                        begin(g["graph"])
-                        g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"],
-                                                                  between=between if self.overlap_exchange else None)
-                        self._pack_rest(ex, grads, g["cut"])
-                        end()
-                        begin(g["graph2"], pool=g["graph"].pool())
-                        self._apply(self._unpack_mean(ex, ws), g["lr_t"], t)
-                    finally:
-                        end()
-                torch.cuda.current_stream(dev).wait_stream(cap)
-                g["ex"] = ex
-            self._graph = g
-        src = _joined_along_dim1(inputs)
-        if src is not None:                       # the caller's four slices of one tuple tensor: one copy, not four
-            g["joined"].copy_(src)
+            self._capture_step(g, dev, dp, lr, bn_decay, t)
+        if bank is not None:
+            g["source"]["ids"].copy_(bank[1])     # the ids of THIS step: the assemble launch inside the graph reads the buffer
         else:
-            for dst, s_ in zip(g["in"], inputs):
-                dst.copy_(s_)
+            src = _joined_along_dim1(inputs)
+            if src is not None:                       # the caller's four slices of one tuple tensor: one copy, not four
+                g["joined"].copy_(src)
+            else:
+                for dst, s_ in zip(g["in"], inputs):
+                    dst.copy_(s_)
+        return self._replay_step(g, dp, lr, bn_decay, t)
+
+    def _capture_step(self, g, dev, dp, lr, bn_decay, t):
+        """Warm up and capture the step over the static buffers of ``g`` (``g["in"]``: the inputs; ``g["source"]``: the bank buffers of
+        step_ids or None); leaves the graph(s) in ``g`` and makes it the current one."""
+        from . import distributed as D
+        source = g["source"]
+        g["lr_t"].fill_(self._lr_t(lr, t))
+        g["bn_decay"].fill_(bn_decay)
+        # warm-up on a side stream (lazy allocations, kernel attributes), on a snapshot of the state that is restored.
+        # No collective here: every rank restores its own snapshot, so the ranks stay in step.
+        snap = [x.detach().clone() for x in self._state_tensors()]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            cut = []
+            loss, grads = self._forward_backward(*g["in"], g["bn_decay"],
+                                                 between=(lambda hn, hg: (self._pack_head(self._exchange_layout(), hn, hg), cut.append(1)))
+                                                 if dp and self.overlap_exchange else None, source=source)
+            if dp:
+                self._pack_rest(self._exchange_layout(), grads, bool(cut))
+                grads = self._unpack_mean(self._exchange_layout(), 1)
+            self._apply(grads, g["lr_t"], t)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        ex = self._exchange_layout() if dp else None      # (after the warm-up's graph walk: the split the captures will see)
+        with torch.no_grad():
+            for x, s0 in zip(self._state_tensors(), snap):
+                x.copy_(s0)
+        for name in self.trainable_names():
+            self.store.vars[name].grad = None
+        g["graph"] = torch.cuda.CUDAGraph()
+        if not dp:
+            with torch.cuda.graph(g["graph"]):
+                g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"], source=source)
+                self._apply(grads, g["lr_t"], t)
+        else:
+            # Data-parallel: [forward, head backward, pack head] | RCCL (head, asynchronous) | [backbone backward, moving averages,
+            # pack rest] | RCCL (rest) | [mean, unpack, Adam] -- the captures end and begin INSIDE the step, at the cut of its
+            # backward (the `between` callback runs on this thread, between two autograd calls).
+            ws = D.world()[1]
+            g["graph_mid"] = torch.cuda.CUDAGraph() if self.overlap_exchange else None
+            g["graph2"] = torch.cuda.CUDAGraph()
+            g["cut"] = False
+            torch.cuda.synchronize(dev)
+            cap = torch.cuda.Stream(device=dev)
+            cap.wait_stream(torch.cuda.current_stream(dev))
+
+            open_graph = [None]        # the graph whose capture is open RIGHT NOW: the only one a failure may end (ADVICE r4)
+
+            def begin(graph, **kw):
+                graph.capture_begin(**kw)
+                open_graph[0] = graph
+
+            def end():
+                graph, open_graph[0] = open_graph[0], None
+                if graph is not None:
+                    graph.capture_end()
+
+            def between(hn, hg):
+                self._pack_head(ex, hn, hg)
+                end()
+                begin(g["graph_mid"], pool=g["graph"].pool())
+                g["cut"] = True
+
+            with torch.cuda.stream(cap):
+                try:
+                    begin(g["graph"])
+                    g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"],
+                                                              between=between if self.overlap_exchange else None, source=source)
+                    self._pack_rest(ex, grads, g["cut"])
+                    end()
+                    begin(g["graph2"], pool=g["graph"].pool())
+                    self._apply(self._unpack_mean(ex, ws), g["lr_t"], t)
+                finally:
+                    end()
+            torch.cuda.current_stream(dev).wait_stream(cap)
+            g["ex"] = ex
+        self._graph = g
+
+    def _replay_step(self, g, dp, lr, bn_decay, t):
         g["lr_t"].fill_(self._lr_t(lr, t))
         g["bn_decay"].fill_(bn_decay)
         g["graph"].replay()
@@ -505,15 +583,19 @@ class TrainStep:
             self._replays_since_sync = 0
         return g["loss"]
 
-    def compute_loss(self, query, positives, negatives, other_neg, is_training: bool, bn_decay=None):
+    def compute_loss(self, query, positives, negatives, other_neg, is_training: bool, bn_decay=None, graph=None):
         """train.py:251-264: concat -> forward -> split -> lazy quadruplet loss.  ``is_training=False`` is the
-        evaluation loss of train.py:568-576 (stored statistics, no moving-average update)."""
+        evaluation loss of train.py:568-576 (stored statistics, no moving-average update).  ``graph``: the (sorted clouds, KnnGraph)
+        of the concatenated inputs when a cloud bank assembled them (step_ids); the model then builds neither."""
         p = self.params
         with variable_scope(self.outer):
             vecs = _joined_along_dim1((query, positives, negatives, other_neg))                         # train.py:252
             if vecs is None:
                 vecs = torch.cat([query, positives, negatives, other_neg], 1)
-            out_vecs = self.model.forward(vecs, is_training, bn_decay=bn_decay, params=p)                # :254
+            if graph is not None:
+                out_vecs = self.model.forward(vecs, is_training, bn_decay=bn_decay, params=p, graph=graph)
+            else:
+                out_vecs = self.model.forward(vecs, is_training, bn_decay=bn_decay, params=p)            # :254
             q_vec, pos_vecs, neg_vecs, other_neg_vec = torch.split(
                 out_vecs, [1, int(positives.shape[1]), int(negatives.shape[1]), 1], 1)                  # :255
             loss = self.model.lazy_quadruplet_loss(q_vec, pos_vecs, neg_vecs, other_neg_vec,

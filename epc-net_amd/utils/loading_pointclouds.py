@@ -108,6 +108,35 @@ def get_query_tuple(idx, dict_value, num_pos, num_neg, QUERY_DICT, hard_neg=[], 
     return [query, positives, negatives, data[possible_negs[0]]]
 
 
+def get_query_tuple_ids(idx, dict_value, num_pos, num_neg, QUERY_DICT, hard_neg=[], other_neg=False):
+    """The draws of ``get_query_tuple`` as INDICES into the preloaded array instead of slices of it (a device-resident cloud
+    bank is addressed by them: ops.CloudBank): [query id, positive ids, negative ids(, other-negative ids)].  ``random`` is
+    consumed exactly as there -- the same shuffles in the same order -- so ``data[ids]`` are that function's arrays and a seeded
+    run visits the same tuples.  "No possible other negative" is an EMPTY list (there: an empty array)."""
+    random.shuffle(dict_value["positives"])
+    pos_indices = [dict_value["positives"][i] for i in range(num_pos)]
+    random.shuffle(dict_value["negatives"])
+    if len(hard_neg) == 0:
+        neg_indices = [dict_value["negatives"][i] for i in range(num_neg)]
+    else:
+        neg_indices = list(hard_neg)
+        j = 0
+        while len(neg_indices) < num_neg:
+            if dict_value["negatives"][j] not in hard_neg:
+                neg_indices.append(dict_value["negatives"][j])
+            j += 1
+    if not other_neg:
+        return [idx, pos_indices, neg_indices]
+    neighbors = list(dict_value["positives"])
+    for neg in neg_indices:
+        neighbors.extend(QUERY_DICT[neg]["positives"])
+    possible_negs = list(set(QUERY_DICT.keys()) - set(neighbors))
+    random.shuffle(possible_negs)
+    if len(possible_negs) == 0:
+        return [idx, pos_indices, neg_indices, []]
+    return [idx, pos_indices, neg_indices, [possible_negs[0]]]
+
+
 def get_random_hard_negatives(query_vec, random_negs: Sequence[int], num_to_take: int, latent_vectors,
                               search=None) -> List[int]:
     """train.py:857-869: the ``num_to_take`` sampled negatives whose cached descriptors are nearest to the query's.

@@ -641,6 +641,56 @@ int epc_chain_persist_reset(void* workspace, void* stream);
 /* per cloud the points whose neighbour list overflowed (cnt > cap), ascending: ovf_cnt (num_clouds), ovf_list (num_clouds, n) */
 int epc_knn_overflow_lists(const int32_t* cnt, int cap, int num_clouds, int n, int32_t* ovf_cnt, int32_t* ovf_list, void* stream);
 
+/* ---- Cloud bank: a training set resident in device memory with its finished kNN graphs (csrc/graph_bank.hip) -------------------
+ * The Hilbert order, the neighbour lists, their transposition and the overflow lists are functions of ONE cloud's coordinates
+ * (utils/tf_util.py:647-666; neighbours never cross clouds), and the reference trains on the unaugmented preloaded submaps
+ * (train.py:228-230, :388), which its epochs revisit.  A bank keeps one fixed-size RECORD per cloud; a training step assembles its
+ * batch from a list of record ids in one launch instead of rebuilding sort, kNN and transposition.  What is assembled equals, bit
+ * for bit, what epc_morton_sort -> epc_knn_topk -> epc_knn_transpose + epc_knn_overflow_lists give on the same clouds
+ * (epc_knn_transpose sorts every list ascending, so the graph is a deterministic function of the cloud).
+ * The bank is caller-owned device memory of num_records * epc_bank_record_bytes(n, cap) bytes, 16-byte aligned; the library keeps
+ * no state about it.
+ * Record of a cloud of n points with cap list slots per point, every section 16-byte aligned, in this order:
+ *   int32 {ovf_cnt, rlist_used, n, cap}                         16 bytes
+ *   xyz    n x 3 float32   the coordinates in Hilbert order
+ *   kth    n float32  |  cnt  n int32  |  rdeg  n int32
+ *   roff   n int32         RELATIVE to the cloud's segment of rlist (the absolute offset minus c n cap)
+ *   idx    n x cap uint16  cloud-local; only the first min(cnt, cap) slots of a row carry meaning, the others are stored as 0
+ *   rlist  n x cap uint16  cloud-local (the absolute row minus c n); rlist_used entries, the others are stored as 0
+ *   ovf    n uint16        the overflow list; ovf_cnt entries, the others are stored as 0
+ * = 16 + n (28 + 4 cap + 2) bytes: 647,184 for n = 4096, cap = 32 (the 32-bit tensors: 1,179,652), so the bytes of a bank are a
+ * deterministic function of its clouds.  Preconditions: n a multiple of 8, 8 <= n <= 65536 (every cloud-local index fits 16 bits);
+ * cap a multiple of 8, EPC_KNN_SELECT <= cap <= 64; num_clouds n cap < 2^31; every tensor 16-byte aligned. */
+/* bytes of one record; 0 for an unsupported shape */
+size_t epc_bank_record_bytes(int n, int cap);
+/* Store num_clouds clouds into the records first_slot .. first_slot + num_clouds - 1 of a bank of num_records records.  Inputs: what the
+ * existing path leaves for the batch -- xyz_sorted (epc_morton_sort), kth / cnt / idx (epc_knn_topk, int32 lists), rdeg / roff / rlist
+ * (epc_knn_transpose: absolute offsets and rows, the lists of a cloud PACKED in point order from the start of its segment) and
+ * ovf_cnt / ovf_list (epc_knn_overflow_lists).  Two launches: the first checks every meaningful value of the whole batch (cnt in
+ * [0, n]; list entries, listed rows and overflow entries inside their cloud; the packing of the lists); if any fails it writes
+ * status[0] = 1 and the second launch stores NOTHING -- a value that does not fit its 16-bit field is refused, never truncated.
+ * status: one int32 in device memory that the caller zeroes beforehand and reads afterwards (a non-zero word also refuses the store).
+ * A shape outside the preconditions (n > 65536, ...) or slots outside the bank: EPC_EINVAL, nothing launched. */
+int epc_bank_store(void* bank, int num_records, int first_slot, int num_clouds, int n, int cap, const float* xyz_sorted,
+                   const float* kth, const int32_t* cnt, const int32_t* idx, const int32_t* rdeg, const int32_t* roff,
+                   const int32_t* rlist, const int32_t* ovf_cnt, const int32_t* ovf_list, int32_t* status, void* stream);
+/* Assemble the batch of the records ids[0 .. num_ids) (int32 in DEVICE memory, read when the kernel runs: a captured graph replays
+ * with whatever the buffer then holds; repeats allowed) in the layout the training kernels read: xyz (num_ids, n, 3), kth, cnt
+ * (num_ids, n), idx (num_ids, n, cap) int32 cloud-local, rdeg, roff (num_ids n; roff + t n cap), rlist (num_ids n cap) int32 absolute
+ * rows (+ t n; slot t's lists inside [t n cap, (t + 1) n cap)), ovf_cnt (num_ids), ovf_list (num_ids, n).  ONE launch, a workgroup per
+ * (slot, slab of the record); no atomics.  Left UNWRITTEN: the tail of every rlist segment past the slot's last list (nothing reads
+ * past roff + rdeg) and the entries of ovf_list past ovf_cnt.
+ * An id outside [0, num_records) reads no record: that slot's xyz is filled with NaN, it gets an empty graph (cnt = rdeg = ovf_cnt = 0,
+ * list entries 0) and bit (t % 32) of status[t / 32] is set.  status: (num_ids + 31) / 32 int32 words in device memory, only ever
+ * OR-ed into (sticky): the caller zeroes them and reads them when it wants to know.  poison (one float in device memory, may be
+ * NULL): OVERWRITTEN by every launch with 0.0f, or NaN when any id of THIS launch was outside the bank -- a value a training step adds
+ * to its loss, because NaN coordinates alone do not reach it (the ReLUs and the loss's hinges are fmaxf, which drops a NaN operand).
+ * Cost: a byte mover, ~0.55 MB read + ~1.0 MB written per 4096-point cloud, ~28 MB at 18 clouds = 4.5 us at the 6.3 TB/s a copy reaches
+ * on MI355X; DESIGN.md 4 has the measured time. */
+int epc_bank_assemble(const void* bank, int num_records, const int32_t* ids, int num_ids, int n, int cap, float* xyz, float* kth,
+                      int32_t* cnt, int32_t* idx, int32_t* rdeg, int32_t* roff, int32_t* rlist, int32_t* ovf_cnt, int32_t* ovf_list,
+                      int32_t* status, float* poison, void* stream);
+
 /* Backward of loupe.py:255-291 with respect to the point features: df[b][n][f] = sum_k a[b][n][k] dvlad[b][f][k] + sum_k dz[b][n][k] Wc[f][k]
  * (a, dz: (num_clouds n_points, 64) -- the soft assignment and the gradient of its pre-BatchNorm logits; dvlad (num_clouds, F, 64);
  * Wc = cluster_weights (F, 64); df (num_clouds n_points, F)).  One pass: the rows' operand resident in registers, the cloud's right
