@@ -16,7 +16,7 @@
 // point on the lane) are directly the next layer's B operands.  The gather runs whole rows (f32: 16 lanes x float4,
 // 4 points per wave-instruction; fp16: 8 lanes x 16 B, 8 points), results go through a per-wave LDS staging tile to
 // switch between the row layout and the MFMA layout.
-#include "common.h"
+#include "train_common.h"
 
 #define BLK_WAVES 12  // f32 kernel: 12 x 8.7 KB staging tiles + the 49-KB weight pack = 154 KB (3 waves per SIMD)
 #define BLK_THREADS (64 * BLK_WAVES)
@@ -607,11 +607,7 @@ extern "C" int epc_proxyconv_block_fwd(const float* x, const void* x16, const fl
     const size_t lds_bytes = f16 ? (size_t)BLK16_LDS_BYTES : BLK_LDS_FLOATS * sizeof(float);
     const void* fn = f16 ? reinterpret_cast<const void*>(proxyconv_block_f16_kernel)
                          : reinterpret_cast<const void*>(proxyconv_block_kernel);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        epc_set_error("epc_proxyconv_block_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    EPC_SET_DYN_LDS(fn, lds_bytes);
     const int wpb = f16 ? BLK16_WAVES : BLK_WAVES;
     unsigned blocks = (unsigned)((total + wpb * 32 - 1) / (wpb * 32));
     if (!f16) {

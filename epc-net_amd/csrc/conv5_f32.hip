@@ -65,7 +65,7 @@
 // operand: for point group p, k index 8 q + e of the chunk's 32 channels <-> channel 16 (e >> 2) + 4 q + (e & 3); the
 // cluster weights are packed in that k order (pack.hip pack_wc_bf16x2_kernel).
 #include <type_traits>
-#include "common.h"
+#include "train_common.h"
 
 #define C5_THREADS 512
 #define C5_WAVES 8
@@ -561,15 +561,6 @@ __global__ __launch_bounds__(C5M_THREADS, 4) void conv5_max_f32_kernel(const flo
     }
 }
 
-static int c5_set_lds(const void* fn, size_t lds_bytes, const char* who) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        epc_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-        return EPC_EHIP;
-    }
-    return EPC_OK;
-}
-
 extern "C" int epc_conv5_assign_f32_fwd(const float* cat, int cin, const void* packed_conv5, int num_points_total,
                                         void* feat_frag, float* rnorm, float* assign, void* assign_frag, float* apart,
                                         void* stream) {
@@ -578,7 +569,7 @@ extern "C" int epc_conv5_assign_f32_fwd(const float* cat, int cin, const void* p
     EPC_CHECK_ARG(num_points_total >= 0 && num_points_total % 32 == 0, "point count must be a multiple of 32");
     if (num_points_total == 0) return EPC_OK;
     const size_t lds_bytes = C5fLds<256>::TOTAL * sizeof(float);
-    if (int rc = c5_set_lds(reinterpret_cast<const void*>(conv5_vlad_f32_kernel<256>), lds_bytes, __func__)) return rc;
+    EPC_SET_DYN_LDS(conv5_vlad_f32_kernel<256>, lds_bytes);
     const unsigned blocks = (unsigned)((num_points_total + C5_WAVES * 32 - 1) / (C5_WAVES * 32));
     hipLaunchKernelGGL((conv5_vlad_f32_kernel<256>), dim3(blocks), dim3(C5_THREADS), lds_bytes, (hipStream_t)stream, cat,
                        (const float*)packed_conv5, num_points_total, (float*)feat_frag, rnorm, assign, (float*)assign_frag, apart);
@@ -599,7 +590,7 @@ extern "C" int epc_conv5_maxpool_fwd(const float* cat, int cin, const void* pack
         return EPC_EHIP;
     }
     const size_t lds_bytes = C5mLds<128>::TOTAL * sizeof(float);
-    if (int rc = c5_set_lds(reinterpret_cast<const void*>(conv5_max_f32_kernel<128>), lds_bytes, __func__)) return rc;
+    EPC_SET_DYN_LDS(conv5_max_f32_kernel<128>, lds_bytes);
     const unsigned blocks = (unsigned)((total + C5M_WAVES * 32 - 1) / (C5M_WAVES * 32));
     hipLaunchKernelGGL((conv5_max_f32_kernel<128>), dim3(blocks), dim3(C5M_THREADS), lds_bytes, (hipStream_t)stream, cat,
                        (const float*)packed_conv5, (int)total, n, pooled);

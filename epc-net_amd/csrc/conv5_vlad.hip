@@ -14,7 +14,7 @@
 // registers as B fragments for all 32 output chunks; W5 (hi + lo: 3 B per weight, 768 KB) streams through a
 // double-buffered LDS chunk shared by the 8 waves (LDS-DMA, one barrier per chunk).
 #include <type_traits>
-#include "common.h"
+#include "train_common.h"
 
 #define C5_THREADS 512
 #define C5_WAVES 8
@@ -399,12 +399,7 @@ template <int CIN, bool CAT16>
 static int launch_conv5(const float* cat, const float* pack, long total, int n, float* feat, float* rnorm,
                         float* assign, float* assign_frag, float* apart, int32_t* status, hipStream_t stream, const char* who) {
     const size_t lds_bytes = C5Lds<CIN>::TOTAL * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv5_kernel<CIN, CAT16>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        epc_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    if (int rc = epc_set_dyn_lds(reinterpret_cast<const void*>(conv5_kernel<CIN, CAT16>), lds_bytes, who)) return rc;
     const unsigned blocks = (unsigned)((total + C5_WAVES * 32 - 1) / (C5_WAVES * 32));
     hipLaunchKernelGGL((conv5_kernel<CIN, CAT16>), dim3(blocks), dim3(C5_THREADS), lds_bytes, stream, cat, pack, (int)total, n, feat,
                        rnorm, assign, assign_frag, apart, status);
@@ -552,12 +547,7 @@ template <int WAVES>
 static int launch_conv5_max_f16(const void* cat16, const void* packed_conv5, long total, int n, float* pooled, hipStream_t stream,
                                 const char* who) {
     const size_t lds_bytes = C5mfLds<128, WAVES>::TOTAL * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv5_max_f16_kernel<128, WAVES>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        epc_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    if (int rc = epc_set_dyn_lds(reinterpret_cast<const void*>(conv5_max_f16_kernel<128, WAVES>), lds_bytes, who)) return rc;
     const unsigned blocks = (unsigned)((total + WAVES * 32 - 1) / (WAVES * 32));
     hipLaunchKernelGGL((conv5_max_f16_kernel<128, WAVES>), dim3(blocks), dim3(64 * WAVES), lds_bytes, stream,
                        (const unsigned short*)cat16, (const float*)packed_conv5, (int)total, n, pooled);
@@ -803,12 +793,7 @@ extern "C" int epc_vlad_aggregate_fwd(const void* feat_frag, const void* assign_
     EPC_CHECK_ARG(num_clouds >= 0 && num_clouds <= 65535, "bad shape");
     if (num_clouds == 0) return EPC_OK;
     const size_t lds_bytes = (AGG_XCH_FLOATS + 8 * 64) * sizeof(float) + 8 * 32 * AGG_ROW * sizeof(unsigned short);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vlad_aggregate_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        epc_set_error("epc_vlad_aggregate_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    EPC_SET_DYN_LDS(vlad_aggregate_kernel, lds_bytes);
     hipLaunchKernelGGL(vlad_aggregate_kernel, dim3(32 * ((num_clouds + 7) / 8)), dim3(AGG_THREADS), lds_bytes,
                        (hipStream_t)stream, (const float*)feat_frag, (const float*)assign_frag, rnorm, apart, centres, n,
                        num_clouds, V, colss);
@@ -1044,12 +1029,7 @@ extern "C" int epc_vlad_aggregate_f32_fwd(const void* feat_frag, const void* ass
     EPC_CHECK_ARG(num_clouds >= 0 && num_clouds <= 65535, "bad shape");
     if (num_clouds == 0) return EPC_OK;
     const size_t lds_bytes = (AGG_XCH_FLOATS + 8 * 64) * sizeof(float) + 2 * 8 * 32 * AGG_ROW * sizeof(unsigned short);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vlad_aggregate_f32_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        epc_set_error("epc_vlad_aggregate_f32_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    EPC_SET_DYN_LDS(vlad_aggregate_f32_kernel, lds_bytes);
     hipLaunchKernelGGL(vlad_aggregate_f32_kernel, dim3(32 * ((num_clouds + 7) / 8)), dim3(AGG_THREADS), lds_bytes,
                        (hipStream_t)stream, (const float*)feat_frag, (const float*)assign_frag, rnorm, apart, centres, n, num_clouds, V,
                        colss);

@@ -24,7 +24,7 @@
 // reaches on this chip (8 TB/s HBM3E) that is 4.5 us, so the launch is bound by its ~2 us boundary as much as by its bytes.  One
 // thread moves one 16-byte chunk per iteration: a dwordx4 load, and for the u16 sections the widening in registers and two dwordx4
 // stores.  The grid is (slabs, T) with slabs chosen by the host so that T x slabs is ~4 workgroups per CU at any T.
-#include "common.h"
+#include "train_common.h"
 
 namespace {
 
@@ -269,12 +269,10 @@ __global__ __launch_bounds__(BANK_THREADS) void bank_store_kernel(uint4* __restr
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 inline bool tensors_ok(const BankTensors& b) {
-    return b.xyz && b.kth && b.cnt && b.idx && b.rdeg && b.roff && b.rlist && b.ovf_cnt && b.ovf_list && aligned16(b.xyz) &&
-           aligned16(b.kth) && aligned16(b.cnt) && aligned16(b.idx) && aligned16(b.rdeg) && aligned16(b.roff) && aligned16(b.rlist) &&
-           aligned16(b.ovf_list);
+    return b.xyz && b.kth && b.cnt && b.idx && b.rdeg && b.roff && b.rlist && b.ovf_cnt && b.ovf_list && epc_aligned16(b.xyz) &&
+           epc_aligned16(b.kth) && epc_aligned16(b.cnt) && epc_aligned16(b.idx) && epc_aligned16(b.rdeg) && epc_aligned16(b.roff) && epc_aligned16(b.rlist) &&
+           epc_aligned16(b.ovf_list);
 }
 
 // workgroups per cloud: ~4 per CU over the whole batch, at least 256 chunks each
@@ -294,7 +292,7 @@ extern "C" int epc_bank_store(void* bank, int num_records, int first_slot, int n
                               const float* kth, const int32_t* cnt, const int32_t* idx, const int32_t* rdeg, const int32_t* roff,
                               const int32_t* rlist, const int32_t* ovf_cnt, const int32_t* ovf_list, int32_t* status, void* stream) {
     EPC_CHECK_ARG(bank_shape_ok(n, cap), "unsupported record shape (n a multiple of 8 in [8, 65536], cap a multiple of 8 in [20, 64])");
-    EPC_CHECK_ARG(bank && status && aligned16(bank), "null / unaligned bank or status");
+    EPC_CHECK_ARG(bank && status && epc_aligned16(bank), "null / unaligned bank or status");
     EPC_CHECK_ARG(num_clouds > 0 && first_slot >= 0 && num_records > 0 && (long)first_slot + num_clouds <= (long)num_records,
                   "slots outside the bank");
     EPC_CHECK_ARG((long)num_clouds * n * cap < (1L << 31), "too many edges for 32-bit offsets");
@@ -315,7 +313,7 @@ extern "C" int epc_bank_assemble(const void* bank, int num_records, const int32_
                                  float* kth, int32_t* cnt, int32_t* idx, int32_t* rdeg, int32_t* roff, int32_t* rlist, int32_t* ovf_cnt,
                                  int32_t* ovf_list, int32_t* status, float* poison, void* stream) {
     EPC_CHECK_ARG(bank_shape_ok(n, cap), "unsupported record shape (n a multiple of 8 in [8, 65536], cap a multiple of 8 in [20, 64])");
-    EPC_CHECK_ARG(bank && ids && status && aligned16(bank) && num_records > 0, "null / unaligned bank, ids or status");
+    EPC_CHECK_ARG(bank && ids && status && epc_aligned16(bank) && num_records > 0, "null / unaligned bank, ids or status");
     EPC_CHECK_ARG(num_ids > 0 && num_ids <= 65535 && (long)num_ids * n * cap < (1L << 31), "bad number of ids");
     BankTensors o{xyz, kth, cnt, idx, rdeg, roff, rlist, ovf_cnt, ovf_list};
     EPC_CHECK_ARG(tensors_ok(o), "null / unaligned tensor");

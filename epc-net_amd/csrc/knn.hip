@@ -18,7 +18,7 @@
 // pairs -- was measured slower on gfx950: 0.35 vs 0.30 ms.)
 //
 // knn_topk_stream_kernel (any N): same two passes with candidates streamed through an LDS tile, no culling.
-#include "common.h"
+#include "train_common.h"
 #include <stdlib.h>
 
 #define KNN_THREADS 1024   // re-tuned on Hilbert-ordered clouds (r01_o): 1024 0.248 ms, 512 0.262, 256 0.372 per 64 clouds
@@ -856,12 +856,8 @@ static int launch_knn(const float* xyz, int num_clouds, int n, int cap, int32_t*
         const bool wide_grid = (long)grid.x * grid.y >= 2L * num_cus;
 #define EPC_KNN_LAUNCH(C1, B)                                                                                                   \
     do {                                                                                                                        \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_topk_culled_kernel<EPC_KNN_SELECT, C1, B>),       \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                        \
-        if (e_ != hipSuccess) {                                                                                                 \
-            epc_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e_));                                           \
-            return EPC_EHIP;                                                                                                    \
-        }                                                                                                                       \
+        if (int rc_ = epc_set_dyn_lds(reinterpret_cast<const void*>(knn_topk_culled_kernel<EPC_KNN_SELECT, C1, B>), lds_bytes, who)) \
+            return rc_;                                                                                                         \
         hipLaunchKernelGGL((knn_topk_culled_kernel<EPC_KNN_SELECT, C1, B>), grid, dim3(KNN_THREADS), lds_bytes,                \
                            (hipStream_t)stream, xyz, n, cap, idx, cnt, kth, C1 ? conv1_pack : nullptr, C1 ? x32 : nullptr,     \
                            C1 ? (unsigned short*)x16 : nullptr, C1 ? idx_u16 : 0, status);                                      \
@@ -884,12 +880,8 @@ static int launch_knn(const float* xyz, int num_clouds, int n, int cap, int32_t*
             const dim3 qgrid(wgs, num_clouds), qblock(64 * g);
 #define EPC_KNN_QLAUNCH(C1, W)                                                                                                   \
     do {                                                                                                                        \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_topk_quad_kernel<EPC_KNN_SELECT, C1, W>),         \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                        \
-        if (e_ != hipSuccess) {                                                                                                 \
-            epc_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e_));                                           \
-            return EPC_EHIP;                                                                                                    \
-        }                                                                                                                       \
+        if (int rc_ = epc_set_dyn_lds(reinterpret_cast<const void*>(knn_topk_quad_kernel<EPC_KNN_SELECT, C1, W>), lds_bytes, who)) \
+            return rc_;                                                                                                         \
         hipLaunchKernelGGL((knn_topk_quad_kernel<EPC_KNN_SELECT, C1, W>), qgrid, qblock, lds_bytes,                             \
                            (hipStream_t)stream, xyz, n, cap, idx, cnt, kth, C1 ? conv1_pack : nullptr, C1 ? x32 : nullptr,     \
                            C1 ? (unsigned short*)x16 : nullptr, C1 ? idx_u16 : 0, status, rounds);                              \

@@ -11,7 +11,7 @@
 // First form: one wave per query.  Exact Euclidean distances sum_c (q_c - d_c)^2 in f32 (no ||q||^2+||d||^2-2q.d cancellation),
 // kept in LDS; then k rounds of wave-wide arg-min (ties -> lower database index), so the result is the sorted
 // k-nearest list.  Database sizes on this path are 10^2..10^4 rows (Oxford runs hold ~400 submaps each).
-#include "common.h"
+#include "train_common.h"
 
 __global__ __launch_bounds__(64) void pairwise_topk_kernel(const float* __restrict__ db, int num_db,
                                                            const float* __restrict__ queries, int dim, int k,
@@ -76,12 +76,7 @@ extern "C" int epc_pairwise_topk(const float* database, int num_db, const float*
     const size_t lds_bytes = ((size_t)dim + num_db) * sizeof(float);
     EPC_CHECK_ARG(lds_bytes <= 160 * 1024, "database shard too large for one LDS-resident pass (shard it)");
     if (num_q == 0) return EPC_OK;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pairwise_topk_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        epc_set_error("epc_pairwise_topk: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    EPC_SET_DYN_LDS(pairwise_topk_kernel, lds_bytes);
     hipLaunchKernelGGL(pairwise_topk_kernel, dim3(num_q), dim3(64), lds_bytes, (hipStream_t)stream, database,
                        num_db, queries, dim, k, idx, dist);
     EPC_CHECK_LAUNCH();
@@ -430,12 +425,7 @@ extern "C" int epc_pairwise_topk_ws(const float* database, int num_db, const flo
     EPC_CHECK_LAUNCH();
     const int in_lds = (size_t)num_db * 4 <= 149 * 1024;
     const size_t lds_bytes = (in_lds ? (((size_t)num_db + 3) & ~(size_t)3) * 4 : 0) + 4 * 64 * 4;   // the row (if it fits) + the selection's 4 x 64 words
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(select_rerank_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(150 * 1024));
-    if (e != hipSuccess) {
-        epc_set_error("epc_pairwise_topk_ws: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    EPC_SET_DYN_LDS(select_rerank_kernel, 150 * 1024);
     for (int q0 = 0; q0 < num_q; q0 += ch) {
         const int nq = (num_q - q0) < ch ? (num_q - q0) : ch;
         const float* Qc = queries + (size_t)q0 * dim;

@@ -9,7 +9,7 @@
 //
 // One workgroup (1024 threads) per cloud: cloud bounding box -> 10 bits per axis -> 30-bit Hilbert index; 64-bit keys
 // (index << 32 | original point index: a total order, so the result is deterministic) are sorted in LDS.
-#include "common.h"
+#include "train_common.h"
 
 #define SORT_THREADS 1024
 #define SORT_MAX_N 16384  // 128 KB of 8-byte keys
@@ -296,12 +296,7 @@ int epc_sort_launch(const float* xyz, int num_clouds, int n, float* xyz_sorted, 
     // keys (8 B each; the n <= 4096 path splits the area into two 4-B key arrays) + that path's 4097 bucket counters
     const size_t lds_bytes = (size_t)npow2 * sizeof(unsigned long long) +
                              (npow2 == 4 * SORT_THREADS ? (size_t)(npow2 + 4) * sizeof(unsigned int) : 0);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(morton_sort_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) {
-        epc_set_error("epc_morton_sort: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    if (int rc = epc_set_dyn_lds(reinterpret_cast<const void*>(morton_sort_kernel), lds_bytes, "epc_morton_sort")) return rc;
     hipLaunchKernelGGL(morton_sort_kernel, dim3(num_clouds), dim3(SORT_THREADS), lds_bytes, (hipStream_t)stream, xyz,
                        n, npow2, xyz_sorted, perm, status_zero);
     EPC_CHECK_LAUNCH();

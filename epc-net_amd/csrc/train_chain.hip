@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64 * CH_FWD_MAX_WAVES) void chain_fwd_linear_kernel
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] = src[(size_t)q * 64];
             bf16x8 p[PF];
-            ch_split<PF>(v, p);
+            bf16_split<PF>(v, p);
 #pragma unroll
             for (int pc = 0; pc < PF; ++pc) Wf[nt][s4][pc][l] = __builtin_bit_cast(u32x4, p[pc]);
         }
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(64 * CH_FWD_MAX_WAVES) void chain_fwd_linear_kernel
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = 0.f;
             }
-            ch_split<PF>(v, a[s4]);
+            bf16_split<PF>(v, a[s4]);
         }
         if (!g.W) continue;
 #pragma unroll
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(64 * CH_FWD_MAX_WAVES) void chain_fwd_linear_kernel
                 bf16x8 w[PF];
 #pragma unroll
                 for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                acc = ch_prod<PF>(a[s4], w, acc);
+                acc = bf16_prod<PF>(a[s4], w, acc);
             }
             const float bv = nt ? b1 : b0;
             if (tl == wave) piv[nt] = __shfl(acc[0], i);   // row `base` of the wave's first tile
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64 * CH_GATHER_MAX_WAVES) void chain_fwd_gather_ker
 #pragma unroll
         for (int u = 0; u < 8; ++u) v[u] = src[(size_t)u * 64];
         bf16x8 p[PF];
-        ch_split<PF>(v, p);
+        bf16_split<PF>(v, p);
 #pragma unroll
         for (int pc = 0; pc < PF; ++pc) Wf[nt][s4][pc][l] = __builtin_bit_cast(u32x4, p[pc]);
     }
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(64 * CH_GATHER_MAX_WAVES) void chain_fwd_gather_ker
         for (int s4 = 0; s4 < 4; ++s4) {
             float v[8];
             ch_ld8(stg + i * CH_STG_STRIDE + 16 * s4 + 8 * h, v);
-            ch_split<PF>(v, a[s4]);
+            bf16_split<PF>(v, a[s4]);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // in registers: the tile may be overwritten by the next round
 #pragma unroll
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(64 * CH_GATHER_MAX_WAVES) void chain_fwd_gather_ker
                 bf16x8 w[PF];
 #pragma unroll
                 for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                acc = ch_prod<PF>(a[s4], w, acc);
+                acc = bf16_prod<PF>(a[s4], w, acc);
             }
             const float bv = nt ? b1 : b0;
             if (tl == wave) piv[nt] = __shfl(acc[0], i);
@@ -352,7 +352,7 @@ struct ChBwdLinearArgs {
 
 template <int PB>
 __global__ __launch_bounds__(64 * CH_BWD_MAX_WAVES) void chain_bwd_linear_kernel(ChBwdLinearArgs g) {
-    extern __shared__ __attribute__((aligned(16))) char img_all[];   // per wave: hi + lo image (2 * CH_IMG_BYTES); also the pooling scratch
+    extern __shared__ __attribute__((aligned(16))) char img_all[];   // per wave: hi + lo image (2 * BF16_IMG_BYTES); also the pooling scratch
                                                                       // (16 KB) and, at the end, the parked partials (16 KB per parked wave)
     __shared__ __attribute__((aligned(16))) float coef[6][64];    // s, t (mask), mean, k1, dbeta / rows, rstd dgamma / rows
     __shared__ __attribute__((aligned(16))) float xcoef[2][64];   // the input's BatchNorm: s, t
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(64 * CH_BWD_MAX_WAVES) void chain_bwd_linear_kernel
         float v[8];
         ch_ld8(g.W + (size_t)(32 * mt + (l & 31)) * 64 + 16 * s4 + 8 * (l >> 5), v);
         bf16x8 p[PB];
-        ch_split<PB>(v, p);
+        bf16_split<PB>(v, p);
 #pragma unroll
         for (int pc = 0; pc < PB; ++pc) Wf[mt][s4][pc][l] = __builtin_bit_cast(u32x4, p[pc]);
     }
@@ -400,16 +400,16 @@ __global__ __launch_bounds__(64 * CH_BWD_MAX_WAVES) void chain_bwd_linear_kernel
     ch_pool_sums(g.sums, g.parts, reinterpret_cast<double*>(img_all), s_sum, g.dbeta, g.dgamma);
     if (tid < 64) {
         const float mu = bv[0][0], rs = 1.0f / sqrtf(bv[0][1] + g.eps), ga = bv[0][2];
-        const ChBnAffine a = ch_bn_affine(mu, bv[0][1], ga, bv[0][3], g.eps);
+        const BnAffine a = bn_affine(mu, bv[0][1], ga, bv[0][3], g.eps);
         coef[0][tid] = a.s, coef[1][tid] = a.t, coef[2][tid] = mu;
         coef[3][tid] = ga * rs, coef[4][tid] = s_sum[0][tid] * inv_rows, coef[5][tid] = rs * (s_sum[1][tid] * inv_rows);
         if (g.xbn.mean) {
-            const ChBnAffine xa = ch_bn_affine(bv[1][0], bv[1][1], bv[1][2], bv[1][3], g.eps);
+            const BnAffine xa = bn_affine(bv[1][0], bv[1][1], bv[1][2], bv[1][3], g.eps);
             xcoef[0][tid] = xa.s, xcoef[1][tid] = xa.t;
         }
         if (g.zp) {
             const float pm = bv[2][0];
-            const ChBnAffine pa = ch_bn_affine(pm, bv[2][1], bv[2][2], bv[2][3], g.eps);
+            const BnAffine pa = bn_affine(pm, bv[2][1], bv[2][2], bv[2][3], g.eps);
             pcoef[0][tid] = pa.s, pcoef[1][tid] = pa.t, pcoef[2][tid] = pm, pcoef[3][tid] = 1.0f / sqrtf(bv[2][1] + g.eps);
         }
     }
@@ -429,11 +429,11 @@ __global__ __launch_bounds__(64 * CH_BWD_MAX_WAVES) void chain_bwd_linear_kernel
     for (int o = 0; o < 8; ++o) psum[o] = 0.f;
     float* mysum = sumt[wave];
 
-    char* my = img_all + (size_t)wave * 2 * CH_IMG_BYTES;
+    char* my = img_all + (size_t)wave * 2 * BF16_IMG_BYTES;
     auto put = [&](int s4, const bf16x8 (&p)[PB]) {   // the lane's row i, channels 16 s4 + 8 h .. + 7 = chunk 2 s4 + h
-        const int o = ch_img_off(i, 2 * s4 + h);
+        const int o = bf16_img_off(i, 2 * s4 + h);
 #pragma unroll
-        for (int pc = 0; pc < PB; ++pc) *reinterpret_cast<u32x4*>(my + pc * CH_IMG_BYTES + o) = __builtin_bit_cast(u32x4, p[pc]);
+        for (int pc = 0; pc < PB; ++pc) *reinterpret_cast<u32x4*>(my + pc * BF16_IMG_BYTES + o) = __builtin_bit_cast(u32x4, p[pc]);
     };
 
     // one tile of 32 rows; gv / zv: its dy and z rows, already requested
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(64 * CH_BWD_MAX_WAVES) void chain_bwd_linear_kernel
                     const float v = k1[u] * (dd - bb[u] - (zv[s4][u] - mu[u]) * gg[u]);
                     dzv[u] = ok ? v : 0.f;
                 }
-                ch_split<PB>(dzv, zf[s4]);
+                bf16_split<PB>(dzv, zf[s4]);
                 put(s4, zf[s4]);
             }
         }
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(64 * CH_BWD_MAX_WAVES) void chain_bwd_linear_kernel
                     bf16x8 w[PB];
 #pragma unroll
                     for (int pc = 0; pc < PB; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[mt][s4][pc][lane]);
-                    acc = ch_prod<PB>(w, zf[s4], acc);
+                    acc = bf16_prod<PB>(w, zf[s4], acc);
                 }
                 // the in-tile's addend and producer rows are requested together, ahead of the octet loop (whose LDS waits would
                 // otherwise serialise eight global round trips)
@@ -531,7 +531,7 @@ __global__ __launch_bounds__(64 * CH_BWD_MAX_WAVES) void chain_bwd_linear_kernel
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-                for (int pc = 0; pc < PB; ++pc) dzt[nt][s2][pc] = ch_tr_frag(my + pc * CH_IMG_BYTES, nt, s2, lane);
+                for (int pc = 0; pc < PB; ++pc) dzt[nt][s2][pc] = bf16_tr_frag(my + pc * BF16_IMG_BYTES, nt, s2, lane);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // they are in registers: the image may be overwritten
         // ---- x (row layout) -> pieces -> image -> A fragments of dW (k = rows, m = in channel) ----
 #pragma unroll
@@ -546,7 +546,7 @@ __global__ __launch_bounds__(64 * CH_BWD_MAX_WAVES) void chain_bwd_linear_kernel
 #pragma unroll
             for (int u = 0; u < 8; ++u) xv[s4][u] = ok ? xv[s4][u] : 0.f;   // (a select, not a branch)
             bf16x8 p[PB];
-            ch_split<PB>(xv[s4], p);
+            bf16_split<PB>(xv[s4], p);
             put(s4, p);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -556,9 +556,9 @@ __global__ __launch_bounds__(64 * CH_BWD_MAX_WAVES) void chain_bwd_linear_kernel
             for (int s2 = 0; s2 < 2; ++s2) {
                 bf16x8 xt[PB];
 #pragma unroll
-                for (int pc = 0; pc < PB; ++pc) xt[pc] = ch_tr_frag(my + pc * CH_IMG_BYTES, mt, s2, lane);
+                for (int pc = 0; pc < PB; ++pc) xt[pc] = bf16_tr_frag(my + pc * BF16_IMG_BYTES, mt, s2, lane);
 #pragma unroll
-                for (int nt = 0; nt < 2; ++nt) accW[mt][nt] = ch_prod<PB>(xt, dzt[nt][s2], accW[mt][nt]);
+                for (int nt = 0; nt < 2; ++nt) accW[mt][nt] = bf16_prod<PB>(xt, dzt[nt][s2], accW[mt][nt]);
             }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // before the next tile overwrites the image
     };
@@ -669,7 +669,7 @@ __global__ __launch_bounds__(CH_GB_THREADS) void chain_bwd_gather_kernel(ChBwdGa
     const int lb = xcd_contiguous_block(blockIdx.x, gridDim.x);
     if (tid < 64) {
         const float pm = g.bn.mean[tid];
-        const ChBnAffine pa = ch_bn_affine(pm, g.bn.var[tid], g.bn.gamma[tid], g.bn.beta[tid], g.eps);
+        const BnAffine pa = bn_affine(pm, g.bn.var[tid], g.bn.gamma[tid], g.bn.beta[tid], g.eps);
         pcoef[0][tid] = pa.s, pcoef[1][tid] = pa.t, pcoef[2][tid] = pm, pcoef[3][tid] = 1.0f / sqrtf(g.bn.var[tid] + g.eps);
     }
     __syncthreads();
@@ -842,7 +842,7 @@ __global__ __launch_bounds__(16 * CH_ROWG) void chain_sums_kernel(const float* _
     const int tid = threadIdx.x, q = tid & 15, rg = tid >> 4;
     if (tid < 64) {
         const float pm = bn.mean[tid];
-        const ChBnAffine pa = ch_bn_affine(pm, bn.var[tid], bn.gamma[tid], bn.beta[tid], eps);
+        const BnAffine pa = bn_affine(pm, bn.var[tid], bn.gamma[tid], bn.beta[tid], eps);
         pcoef[0][tid] = pa.s, pcoef[1][tid] = pa.t, pcoef[2][tid] = pm, pcoef[3][tid] = 1.0f / sqrtf(bn.var[tid] + eps);
     }
     __syncthreads();
@@ -883,7 +883,7 @@ __global__ __launch_bounds__(256) void chain_bn_bwd_kernel(const float* __restri
     const float inv_rows = 1.0f / (float)rows;
     if (tid < 64) {
         const float mu = bn.mean[tid], rs = 1.0f / sqrtf(bn.var[tid] + eps), ga = bn.gamma[tid];
-        const ChBnAffine a = ch_bn_affine(mu, bn.var[tid], ga, bn.beta[tid], eps);
+        const BnAffine a = bn_affine(mu, bn.var[tid], ga, bn.beta[tid], eps);
         coef[0][tid] = a.s, coef[1][tid] = a.t, coef[2][tid] = mu;
         coef[3][tid] = ga * rs, coef[4][tid] = s_sum[0][tid] * inv_rows, coef[5][tid] = rs * (s_sum[1][tid] * inv_rows);
     }
@@ -978,7 +978,6 @@ __global__ __launch_bounds__(OVF_THREADS) void knn_overflow_list_kernel(const in
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------
-static bool ch_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
 // rows per workgroup (= per partial): the 32-row tiles spread evenly over the CUs, at most CH_MAX_TILES per workgroup
 static int ch_wg_rows(int rows) {
@@ -996,13 +995,6 @@ static int ch_waves(int rows, int cap) {
     const int t = ch_wg_rows(rows) / 32;
     return t < cap ? t : cap;
 }
-static int ch_set_lds(const void* fn, size_t bytes, const char* who) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-        epc_set_error("%s: hipFuncSetAttribute failed", who);
-        return EPC_EHIP;
-    }
-    return EPC_OK;
-}
 
 static ChBn make_bn(const float* stats, int rows, const float* bias, float* mean, float* var, const float* gamma, const float* beta) {
     ChBn b;
@@ -1016,11 +1008,11 @@ extern "C" int epc_chain_fwd_linear(const float* zin, const float* in_stats, con
                                     int a_stride, void* a_out_bf16, const float* W, const float* bias, float* z_out, float* stats_out,
                                     int rows, int pieces, void* stream) {
     EPC_CHECK_ARG(zin && in_mean && in_var && in_gamma && in_beta, "null pointer");
-    EPC_CHECK_ARG(!a_out_bf16 || (a_out && a_stride % 8 == 0 && ch_aligned16(a_out_bf16)), "the bf16 copy comes with a_out, 16-byte aligned, stride a multiple of 8");
+    EPC_CHECK_ARG(!a_out_bf16 || (a_out && a_stride % 8 == 0 && epc_aligned16(a_out_bf16)), "the bf16 copy comes with a_out, 16-byte aligned, stride a multiple of 8");
     EPC_CHECK_ARG(rows > 0 && (pieces == 3 || pieces == 1), "bad shape (pieces: 3 or 1)");
     EPC_CHECK_ARG(!W || (z_out && stats_out), "a layer needs z_out and stats_out");
     EPC_CHECK_ARG(W || a_out, "nothing to do: neither a layer nor an activation output");
-    EPC_CHECK_ARG(ch_aligned16(zin) && ch_aligned16(resid) && ch_aligned16(a_out) && ch_aligned16(z_out) && ch_aligned16(in_stats) &&
+    EPC_CHECK_ARG(epc_aligned16(zin) && epc_aligned16(resid) && epc_aligned16(a_out) && epc_aligned16(z_out) && epc_aligned16(in_stats) &&
                       (!a_out || a_stride % 4 == 0),
                   "tensors must be 16-byte aligned, strides multiples of 4");
     ChFwdLinearArgs g;
@@ -1043,7 +1035,7 @@ extern "C" int epc_chain_fwd_gather(const float* z0, const float* in_stats, cons
                   "null pointer");
     EPC_CHECK_ARG(num_clouds > 0 && n > 0 && knn > 0 && cap >= EPC_KNN_SELECT && (pieces == 3 || pieces == 1), "bad shape");
     EPC_CHECK_ARG((long)num_clouds * n < (1L << 31) / 64, "too many rows");
-    EPC_CHECK_ARG(ch_aligned16(z0) && ch_aligned16(xm) && ch_aligned16(d) && ch_aligned16(z_out) && ch_aligned16(in_stats) && ch_aligned16(idx),
+    EPC_CHECK_ARG(epc_aligned16(z0) && epc_aligned16(xm) && epc_aligned16(d) && epc_aligned16(z_out) && epc_aligned16(in_stats) && epc_aligned16(idx),
                   "tensors must be 16-byte aligned");
     const int rows = num_clouds * n;
     ChFwdGatherArgs g;
@@ -1055,7 +1047,7 @@ extern "C" int epc_chain_fwd_gather(const float* z0, const float* in_stats, cons
     size_t lds = (size_t)nw * CH_STG_FLOATS * sizeof(float);
     if (lds < 4 * 16 * 64 * sizeof(double)) lds = 4 * 16 * 64 * sizeof(double);
     const void* fn = pieces == 3 ? reinterpret_cast<const void*>(chain_fwd_gather_kernel<3>) : reinterpret_cast<const void*>(chain_fwd_gather_kernel<1>);
-    if (int rc = ch_set_lds(fn, lds, __func__)) return rc;
+    EPC_SET_DYN_LDS(fn, lds);
     if (pieces == 3) hipLaunchKernelGGL(chain_fwd_gather_kernel<3>, grid, block, lds, (hipStream_t)stream, g);
     else hipLaunchKernelGGL(chain_fwd_gather_kernel<1>, grid, block, lds, (hipStream_t)stream, g);
     EPC_CHECK_LAUNCH();
@@ -1080,8 +1072,8 @@ extern "C" int epc_chain_bwd_linear(const float* dy, int dy_stride, const float*
     EPC_CHECK_ARG(!zp || (p_mean && p_var && p_gamma && p_beta && psums), "zp needs its BatchNorm and psums");
     const bool any = x_mean || x_var || x_gamma || x_beta, all = x_mean && x_var && x_gamma && x_beta;
     EPC_CHECK_ARG(any == all, "x_mean, x_var, x_gamma, x_beta: all four or none");
-    EPC_CHECK_ARG(ch_aligned16(dy) && ch_aligned16(z) && ch_aligned16(x) && ch_aligned16(dx) && ch_aligned16(dx_addend) && ch_aligned16(zp) &&
-                      ch_aligned16(sums) && ch_aligned16(W) && dy_stride % 4 == 0 && x_stride % 4 == 0 && (!dx_addend || addend_stride % 4 == 0),
+    EPC_CHECK_ARG(epc_aligned16(dy) && epc_aligned16(z) && epc_aligned16(x) && epc_aligned16(dx) && epc_aligned16(dx_addend) && epc_aligned16(zp) &&
+                      epc_aligned16(sums) && epc_aligned16(W) && dy_stride % 4 == 0 && x_stride % 4 == 0 && (!dx_addend || addend_stride % 4 == 0),
                   "tensors must be 16-byte aligned, strides multiples of 4");
     ChBwdLinearArgs g;
     g.dy = dy, g.dy_stride = dy_stride, g.z = z, g.bn = make_given(mean, var, gamma, beta), g.sums = sums, g.parts = epc_chain_parts(rows);
@@ -1090,10 +1082,10 @@ extern "C" int epc_chain_bwd_linear(const float* dy, int dy_stride, const float*
     g.zp = zp, g.pbn = make_given(p_mean, p_var, p_gamma, p_beta), g.psums = psums, g.rows = rows, g.wg_rows = ch_wg_rows(rows), g.eps = eps;
     const int nw = ch_waves(rows, CH_BWD_MAX_WAVES);
     const dim3 grid(epc_chain_parts(rows)), block(64 * nw);
-    size_t lds = (size_t)nw * 2 * CH_IMG_BYTES;
+    size_t lds = (size_t)nw * 2 * BF16_IMG_BYTES;
     if (lds < 2 * 16 * 64 * sizeof(double)) lds = 2 * 16 * 64 * sizeof(double);
     const void* fn = pieces == 2 ? reinterpret_cast<const void*>(chain_bwd_linear_kernel<2>) : reinterpret_cast<const void*>(chain_bwd_linear_kernel<1>);
-    if (int rc = ch_set_lds(fn, lds, __func__)) return rc;
+    EPC_SET_DYN_LDS(fn, lds);
     if (pieces == 2) hipLaunchKernelGGL(chain_bwd_linear_kernel<2>, grid, block, lds, (hipStream_t)stream, g);
     else hipLaunchKernelGGL(chain_bwd_linear_kernel<1>, grid, block, lds, (hipStream_t)stream, g);
     EPC_CHECK_LAUNCH();
@@ -1107,7 +1099,7 @@ extern "C" int epc_chain_bwd_gather(const float* s, const float* dout, int dout_
     EPC_CHECK_ARG(s && dout && rdeg && roff && rlist && ovf_cnt && ovf_list && xyz && kth && z0 && mean && var && gamma && beta && psums && dx,
                   "null pointer");
     EPC_CHECK_ARG(num_clouds > 0 && n > 0 && knn > 0 && (long)num_clouds * n < (1L << 31) / 64, "bad shape");
-    EPC_CHECK_ARG(ch_aligned16(s) && ch_aligned16(dout) && ch_aligned16(z0) && ch_aligned16(dx) && dout_stride % 4 == 0,
+    EPC_CHECK_ARG(epc_aligned16(s) && epc_aligned16(dout) && epc_aligned16(z0) && epc_aligned16(dx) && dout_stride % 4 == 0,
                   "tensors must be 16-byte aligned, strides multiples of 4");
     ChBwdGatherArgs g;
     g.s = s, g.dout = dout, g.dout_stride = dout_stride, g.rdeg = rdeg, g.roff = roff, g.rlist = rlist, g.ovf_cnt = ovf_cnt, g.ovf_list = ovf_list, g.xyz = xyz;
@@ -1119,7 +1111,7 @@ extern "C" int epc_chain_bwd_gather(const float* s, const float* dout, int dout_
 }
 
 extern "C" int epc_chain_stats(const float* z, int rows, float* stats, void* stream) {
-    EPC_CHECK_ARG(z && stats && rows > 0 && ch_aligned16(z), "null pointer / bad shape / alignment");
+    EPC_CHECK_ARG(z && stats && rows > 0 && epc_aligned16(z), "null pointer / bad shape / alignment");
     hipLaunchKernelGGL(chain_stats_kernel, dim3(epc_chain_parts(rows)), dim3(256), 0, (hipStream_t)stream, z, rows, ch_wg_rows(rows), stats);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
@@ -1128,7 +1120,7 @@ extern "C" int epc_chain_stats(const float* z, int rows, float* stats, void* str
 extern "C" int epc_chain_sums(const float* dy, int dy_stride, const float* z, const float* mean, const float* var, const float* gamma,
                               const float* beta, float eps, int rows, float* psums, void* stream) {
     EPC_CHECK_ARG(dy && z && mean && var && gamma && beta && psums && rows > 0, "null pointer / bad shape");
-    EPC_CHECK_ARG(ch_aligned16(dy) && ch_aligned16(z) && dy_stride % 4 == 0, "tensors must be 16-byte aligned, strides multiples of 4");
+    EPC_CHECK_ARG(epc_aligned16(dy) && epc_aligned16(z) && dy_stride % 4 == 0, "tensors must be 16-byte aligned, strides multiples of 4");
     hipLaunchKernelGGL(chain_sums_kernel, dim3(epc_chain_parts(rows)), dim3(16 * CH_ROWG), 0, (hipStream_t)stream, dy, dy_stride, z,
                        make_given(mean, var, gamma, beta), eps, rows, ch_wg_rows(rows), psums);
     EPC_CHECK_LAUNCH();
@@ -1139,7 +1131,7 @@ extern "C" int epc_chain_bn_bwd(const float* dy, const float* z, const float* me
                                 const float* beta, float eps, const float* sums, float* dgamma, float* dbeta, int rows, float* dz,
                                 void* stream) {
     EPC_CHECK_ARG(dy && z && mean && var && gamma && beta && sums && dgamma && dbeta && dz && rows > 0, "null pointer / bad shape");
-    EPC_CHECK_ARG(ch_aligned16(dy) && ch_aligned16(z) && ch_aligned16(dz) && ch_aligned16(sums), "tensors must be 16-byte aligned");
+    EPC_CHECK_ARG(epc_aligned16(dy) && epc_aligned16(z) && epc_aligned16(dz) && epc_aligned16(sums), "tensors must be 16-byte aligned");
     hipLaunchKernelGGL(chain_bn_bwd_kernel, dim3(epc_chain_parts(rows)), dim3(256), 0, (hipStream_t)stream, dy, z,
                        make_given(mean, var, gamma, beta), sums, epc_chain_parts(rows), dgamma, dbeta, eps, rows, ch_wg_rows(rows), dz);
     EPC_CHECK_LAUNCH();
@@ -1150,7 +1142,7 @@ extern "C" int epc_chain_dw_sum(int layers, const float* const* partials, float*
     EPC_CHECK_ARG(layers > 0 && layers <= CH_MAX_LAYERS && partials && dW && rows > 0, "bad argument (at most 16 layers per call)");
     ChDwSumArgs g;
     for (int l = 0; l < layers; ++l) {
-        EPC_CHECK_ARG(partials[l] && dW[l] && ch_aligned16(partials[l]) && ch_aligned16(dW[l]), "null / unaligned tensor");
+        EPC_CHECK_ARG(partials[l] && dW[l] && epc_aligned16(partials[l]) && epc_aligned16(dW[l]), "null / unaligned tensor");
         g.part[l] = partials[l], g.out[l] = dW[l];
     }
     g.parts = epc_chain_parts(rows);

@@ -1,7 +1,7 @@
 // Device helpers shared by the launch chain (train_chain.hip) and the persistent chain (train_chain_persist.hip): tile algebra,
 // the pooled training-mode BatchNorm, the moment / sum partials.  See train_chain.hip's header for the design.
 #pragma once
-#include "common.h"
+#include "train_common.h"
 
 // Geometry.  A workgroup takes `wg_rows` consecutive rows (= one partial), a multiple of 32; its waves take the 32-row tiles
 // wave, wave + nw, ... .  wg_rows is chosen on the host so that the grid is ONE workgroup per CU whenever the rows allow it
@@ -13,47 +13,6 @@
 #define CH_FWD_MAX_WAVES 8     // the row-streaming forward layer: two waves per SIMD (at three its weight fragments spill)
 #define CH_GATHER_MAX_WAVES 12 // the gather layer: three waves per SIMD, one tile each -- bytes in flight are what it is short of
 #define CH_BWD_MAX_WAVES 8
-
-typedef short ch_s16x4 __attribute__((ext_vector_type(4)));
-typedef short ch_s16x8 __attribute__((ext_vector_type(8)));
-
-struct ChBnAffine {
-    float s, t;
-};
-// y = z * s + t: the expression the forward and every recomputed ReLU mask share bit for bit (bn_affine of train_ops.hip)
-__device__ __forceinline__ ChBnAffine ch_bn_affine(float mean, float var, float gamma, float beta, float eps) {
-    ChBnAffine a;
-    a.s = (1.0f / sqrtf(var + eps)) * gamma;
-    a.t = beta - mean * a.s;
-    return a;
-}
-
-template <int P>
-__device__ __forceinline__ void ch_split(const float (&v)[8], bf16x8 (&p)[P]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        p[0][j] = (__bf16)v[j];
-        if constexpr (P >= 2) {
-            const float r1 = v[j] - (float)p[0][j];
-            p[1][j] = (__bf16)r1;
-            if constexpr (P >= 3) p[2][j] = (__bf16)(r1 - (float)p[1][j]);
-        }
-    }
-}
-// a (P pieces) times b (P pieces), smallest terms first: six products for P = 3, three for P = 2, one for P = 1
-template <int P>
-__device__ __forceinline__ f32x16 ch_prod(const bf16x8 (&a)[P], const bf16x8 (&b)[P], f32x16 acc) {
-    if constexpr (P == 3) {
-        acc = mfma_bf16(a[2], b[0], acc);
-        acc = mfma_bf16(a[0], b[2], acc);
-        acc = mfma_bf16(a[1], b[1], acc);
-    }
-    if constexpr (P >= 2) {
-        acc = mfma_bf16(a[1], b[0], acc);
-        acc = mfma_bf16(a[0], b[1], acc);
-    }
-    return mfma_bf16(a[0], b[0], acc);
-}
 
 __device__ __forceinline__ void ch_ld8(const float* p, float (&v)[8]) {
     const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
@@ -167,7 +126,7 @@ __device__ __forceinline__ void ch_bn_finish(const ChBn& bn, const ChBnRegs& r, 
             if (blockIdx.x == 0) bn.mean[tid] = mean, bn.var[tid] = var;
         }
         s_mean[tid] = mean, s_var[tid] = var;
-        const ChBnAffine a2 = ch_bn_affine(mean, var, r.gamma, r.beta, eps);
+        const BnAffine a2 = bn_affine(mean, var, r.gamma, r.beta, eps);
         coef[0][tid] = a2.s, coef[1][tid] = a2.t;
     }
     __syncthreads();
@@ -258,23 +217,8 @@ __device__ __forceinline__ void ch_store_stats(float (&s1)[2], float (&s2)[2], c
 struct ChBnGiven {   // a BatchNorm with known batch moments (null mean: none)
     const float *mean, *var, *gamma, *beta;
 };
-#define CH_IMG_BYTES 4096   // one piece of the transposition image: 32 rows x 128 B
 // The producer's column sums go through a small per-wave LDS tile, eight channels at a time (64 per-lane accumulators -- a lane
 // holds ONE row's 32 channels -- would cost the kernel its second wave per SIMD): word of (quantity q, row, channel ch) below;
 // a wave's 32-lane half reads 32 distinct banks (lane = (row group g, q, ch): bank = 8 q + 16 g + 8 r + ch mod 32).
 #define CH_SUMT_WORDS 640
 __device__ __forceinline__ int ch_sumt_word(int qn, int row, int ch) { return qn * 328 + row * 8 + (row >> 3) * 16 + ch; }
-__device__ __forceinline__ int ch_img_off(int row, int chunk) {   // byte offset of 16-byte chunk `chunk` (0..7) of row `row`
-    return 128 * row + 16 * (chunk ^ (((row >> 1) & 1) << 2) ^ (((row >> 2) & 1) << 1));
-}
-// the A / B fragment (k = rows 16 s2 + 8 h .. + 7, m or n = channel 32 t + (lane & 31)) of one piece, read transposed
-__device__ __forceinline__ bf16x8 ch_tr_frag(const char* img, int t, int s2, int lane) {
-    const int g16 = lane >> 4, l16 = lane & 15, qq = l16 >> 2, pp = l16 & 3;
-    const int chunk = 4 * t + 2 * (g16 & 1) + (pp >> 1);
-    const int r0 = 16 * s2 + 8 * (g16 >> 1);
-    typedef __attribute__((address_space(3))) ch_s16x4* lds_ptr;
-    const ch_s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + ch_img_off(r0 + qq, chunk) + 8 * (pp & 1)));
-    const ch_s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + ch_img_off(r0 + 4 + qq, chunk) + 8 * (pp & 1)));
-    const ch_s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}

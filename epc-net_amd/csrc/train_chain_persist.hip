@@ -251,7 +251,7 @@ __device__ __forceinline__ void pst_final_moments(const PstCtx& c, const void* s
         const float var = (float)fmax(B / (double)rows - m1 * m1, 0.0);
         if (blockIdx.x == 0) mean_out[tid] = mean, var_out[tid] = var;
         s_mean[tid] = mean, s_var[tid] = var;
-        const ChBnAffine a2 = ch_bn_affine(mean, var, ga, be, eps);
+        const BnAffine a2 = bn_affine(mean, var, ga, be, eps);
         coef[0][tid] = a2.s, coef[1][tid] = a2.t;
     }
     __syncthreads();
@@ -319,7 +319,7 @@ __device__ __forceinline__ void pst_stage_fwd_weights(const float* W, u32x4 (*Wf
 #pragma unroll
         for (int u = 0; u < 8; ++u) v[u] = src[(size_t)u * 64];
         bf16x8 p[PF];
-        ch_split<PF>(v, p);
+        bf16_split<PF>(v, p);
 #pragma unroll
         for (int pc = 0; pc < PF; ++pc) Wf[nt][s4][pc][l] = __builtin_bit_cast(u32x4, p[pc]);
     }
@@ -511,7 +511,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
             for (int s4 = 0; s4 < 4; ++s4) {
                 float v[8];
                 ch_ld8(tile + i * CH_STG_STRIDE + 16 * s4 + 8 * h, v);
-                ch_split<PF>(v, a[s4]);
+                bf16_split<PF>(v, a[s4]);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // in registers: the tile takes za next
             const float b0 = B.ba ? B.ba[i] : 0.f, b1 = B.ba ? B.ba[32 + i] : 0.f;
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
                     bf16x8 w[PF];
 #pragma unroll
                     for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                    acc = ch_prod<PF>(a[s4], w, acc);
+                    acc = bf16_prod<PF>(a[s4], w, acc);
                 }
                 const float bv = nt ? b1 : b0;
                 piv[nt] = __shfl(acc[0], i);   // row `base`
@@ -561,7 +561,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
                 const bool ok = base + i < rows;
 #pragma unroll
                 for (int u = 0; u < 8; ++u) v[u] = ok ? fmaxf(zr[u] * cs[u] + ct[u], 0.f) : 0.f;
-                ch_split<PF>(v, a[s4]);
+                bf16_split<PF>(v, a[s4]);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // in registers: the tile takes zb next
             const float b0 = B.bb ? B.bb[i] : 0.f, b1 = B.bb ? B.bb[32 + i] : 0.f;
@@ -575,7 +575,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
                     bf16x8 w[PF];
 #pragma unroll
                     for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                    acc = ch_prod<PF>(a[s4], w, acc);
+                    acc = bf16_prod<PF>(a[s4], w, acc);
                 }
                 const float bv = nt ? b1 : b0;
                 piv[nt] = __shfl(acc[0], i);
@@ -619,7 +619,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
                 for (int s4 = 0; s4 < 4; ++s4) {
                     float v[8];
                     ch_ld8(tile + i * CH_STG_STRIDE + 16 * s4 + 8 * h, v);
-                    ch_split<PF>(v, a[s4]);
+                    bf16_split<PF>(v, a[s4]);
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 const float b0 = B.b0_next ? B.b0_next[i] : 0.f, b1 = B.b0_next ? B.b0_next[32 + i] : 0.f;
@@ -634,7 +634,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
                         bf16x8 w[PF];
 #pragma unroll
                         for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                        acc = ch_prod<PF>(a[s4], w, acc);
+                        acc = bf16_prod<PF>(a[s4], w, acc);
                     }
                     const float bv = nt ? b1 : b0;
                     piv[nt] = __shfl(acc[0], i);
@@ -677,7 +677,6 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------
-static bool pst_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 #define PST_DEFAULT_BUDGET 25000000ll   // a quarter second of the 100-MHz s_memrealtime
 
 // rows per workgroup: the chain's own geometry (epc_chain_parts workgroups, the 32-row tiles spread evenly over the CUs)
@@ -722,7 +721,7 @@ extern "C" int epc_chain_fwd_persist(const epc_chain_fwd_args* a, int pieces, vo
     EPC_CHECK_ARG((long)a->num_clouds * a->n < (1L << 31) / 64, "too many rows");
     const int rows = a->num_clouds * a->n;
     EPC_CHECK_ARG(epc_chain_persist_ok(rows), "rows not covered by the persistent chain (epc_chain_persist_ok)");
-    EPC_CHECK_ARG(pst_aligned16(a->cat) && pst_aligned16(a->cat_bf16) && pst_aligned16(a->idx) && pst_aligned16(a->workspace),
+    EPC_CHECK_ARG(epc_aligned16(a->cat) && epc_aligned16(a->cat_bf16) && epc_aligned16(a->idx) && epc_aligned16(a->workspace),
                   "tensors must be 16-byte aligned");
     EPC_CHECK_ARG(epc_chain_parts(rows) <= PST_MAX_PARTS && 1 + 3 * a->nblocks <= PST_MAX_PHASES, "grid / phase count beyond the workspace layout");
     for (int b = 0; b < a->nblocks; ++b) {
@@ -733,7 +732,7 @@ extern "C" int epc_chain_fwd_persist(const epc_chain_fwd_args* a, int pieces, vo
                       "null pointer in a block");
         EPC_CHECK_ARG(last ? (!B.W0_next && !B.z0_next) : (B.W0_next && B.z0_next), "W0_next / z0_next: both in every block but the last");
         EPC_CHECK_ARG(b == 0 || B.z0 == a->blk[b - 1].z0_next, "a block's z0 is the previous block's z0_next");
-        EPC_CHECK_ARG(pst_aligned16(B.z0) && pst_aligned16(B.d) && pst_aligned16(B.za) && pst_aligned16(B.zb) && pst_aligned16(B.z0_next),
+        EPC_CHECK_ARG(epc_aligned16(B.z0) && epc_aligned16(B.d) && epc_aligned16(B.za) && epc_aligned16(B.zb) && epc_aligned16(B.z0_next),
                       "tensors must be 16-byte aligned");
     }
     PstFwdArgs g;
@@ -750,7 +749,7 @@ extern "C" int epc_chain_fwd_persist(const epc_chain_fwd_args* a, int pieces, vo
 }
 
 extern "C" int epc_chain_persist_init(void* workspace, void* stream) {
-    EPC_CHECK_ARG(workspace && pst_aligned16(workspace), "null / unaligned workspace");
+    EPC_CHECK_ARG(workspace && epc_aligned16(workspace), "null / unaligned workspace");
     if (hipMemsetAsync(workspace, 0, PST_WS_BYTES, (hipStream_t)stream) != hipSuccess) {
         epc_set_error("%s: hipMemsetAsync failed", __func__);
         return EPC_EHIP;

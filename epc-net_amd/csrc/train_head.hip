@@ -1,7 +1,7 @@
 // Tail of the training step as single launches: the VLAD normalisations (loupe.py:292-298) and the lazy quadruplet loss
 // (models/epc-net.py:269-284), forward and backward.  In eager torch arithmetic these were ~100 launches of 4-5 us each
 // per step on a few KB..MB of data (a kernel costs at least 4.6 us even inside a HIP graph); here each is one kernel.
-#include "common.h"
+#include "train_common.h"
 
 // ----------------------------------------------------------------------------------------------------------------
 // VLAD normalisations: v = raw - a_sum (x) w2 (loupe.py:284,292); u = l2_normalize(v, over the F axis) per (cloud,
@@ -825,8 +825,8 @@ __device__ __forceinline__ void ht_product(const float* A, const float* __restri
                 for (int j = 0; j < 8; ++j) b8[j] = W[(size_t)(16 * s + 8 * hh + j) * O + 32 * nt + i];
             }
             bf16x8 ap[P], bp[P];
-            ch_split<P>(a8, ap), ch_split<P>(b8, bp);
-            acc = ch_prod<P>(ap, bp, acc);
+            bf16_split<P>(a8, ap), bf16_split<P>(b8, bp);
+            acc = bf16_prod<P>(ap, bp, acc);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -862,7 +862,8 @@ __global__ __launch_bounds__(HT_THREADS) void hidden_tail_fwd_kernel(const float
         p += d * d;
     }
     const float v1 = ht_meet(p, red, c, q, slices, O) / (float)R;
-    const float s1 = (1.0f / sqrtf(v1 + eps)) * gamma1[c], t1 = beta1[c] - m1 * s1;   // y = z s + t (bn_affine's expression)
+    // bn_affine's expression (train_common.h), written out: a call would load gamma and beta ahead of the square root and reorder the kernel's code
+    const float s1 = (1.0f / sqrtf(v1 + eps)) * gamma1[c], t1 = beta1[c] - m1 * s1;
     if (q == 0) mean1[c] = m1, var1[c] = v1, var1u[c] = v1 * bessel1;   // (the fused slim op feeds the Bessel-corrected variance to the moving average)
     // ---- the group sums (rows beyond B: zeros -- the products' tile is 32 rows) ----
 #pragma unroll 2
@@ -913,8 +914,8 @@ __device__ __forceinline__ void ht_dwg(const float* vs, const float* dgls, int O
 #pragma unroll
             for (int j = 0; j < 8; ++j) a8[j] = vs[(16 * s + 8 * hh + j) * O + 32 * mt + i], b8[j] = dgls[(16 * s + 8 * hh + j) * O + 32 * nt + i];
             bf16x8 ap[P], bp[P];
-            ch_split<P>(a8, ap), ch_split<P>(b8, bp);
-            acc = ch_prod<P>(ap, bp, acc);
+            bf16_split<P>(a8, ap), bf16_split<P>(b8, bp);
+            acc = bf16_prod<P>(ap, bp, acc);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) dWg[(size_t)(32 * mt + mfma_row(r, hh)) * O + 32 * nt + i] = acc[r];
@@ -996,10 +997,7 @@ extern "C" int epc_hidden_tail_fwd(const float* h, int B, int G, int O, const fl
     EPC_CHECK_ARG(h && gamma1 && beta1 && Wg && gamma2 && beta2 && mean1 && var1 && var1u && v && gl && mean2 && var2 && var2u && out, "null pointer");
     EPC_CHECK_ARG(ht_shape_ok(B, G, O), "shape not covered (epc_hidden_tail_ok)");
     const size_t lds = ((size_t)2 * HT_ROWS * O + (size_t)(HT_THREADS / O) * O) * sizeof(float);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(hidden_tail_fwd_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        epc_set_error("%s: hipFuncSetAttribute failed", __func__);
-        return EPC_EHIP;
-    }
+    EPC_SET_DYN_LDS(hidden_tail_fwd_kernel<3>, lds);
     hipLaunchKernelGGL(hidden_tail_fwd_kernel<3>, dim3(1), dim3(HT_THREADS), lds, (hipStream_t)stream, h, B, G, O, gamma1, beta1, Wg, gamma2, beta2, eps,
                        bessel1, bessel2, mean1, var1, var1u, v, gl, mean2, var2, var2u, out);
     EPC_CHECK_LAUNCH();
@@ -1020,10 +1018,7 @@ extern "C" int epc_hidden_tail_bwd(const float* dout, const float* h, int B, int
     // oracle/epcnet_oracle_torch.py (bf16_product_rule) and of the per-op GEMM that takes B > 32; the two products with B rows stay f32-accurate
     const int dw_rounded = pieces == 1 && B >= 32;
     const size_t lds = ((size_t)3 * HT_ROWS * O + (size_t)(HT_THREADS / O) * O) * sizeof(float);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(hidden_tail_bwd_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        epc_set_error("%s: hipFuncSetAttribute failed", __func__);
-        return EPC_EHIP;
-    }
+    EPC_SET_DYN_LDS(hidden_tail_bwd_kernel<2>, lds);
     hipLaunchKernelGGL(hidden_tail_bwd_kernel<2>, dim3(1), dim3(HT_THREADS), lds, (hipStream_t)stream, dout, h, B, G, O, gamma1, mean1, var1, v, gl, Wg,
                        gamma2, beta2, mean2, var2, eps, dw_rounded, dh, dgamma1, dbeta1, dWg, dgamma2, dbeta2);
     EPC_CHECK_LAUNCH();

@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256, 3) void h16_df_tail_kernel(const float* __rest
     }
     for (int c = tid; c < 1024; c += 256) {
         const float rs = 1.0f / sqrtf(tail.bn.var[c] + tail.bn.eps);
-        const H16Affine af = h16_affine(tail.bn.mean[c], tail.bn.var[c], tail.bn.gamma[c], tail.bn.beta[c], tail.bn.eps);
+        const BnAffine af = bn_affine(tail.bn.mean[c], tail.bn.var[c], tail.bn.gamma[c], tail.bn.beta[c], tail.bn.eps);
         coef[0][c] = af.s, coef[1][c] = af.t, coef[2][c] = tail.bn.mean[c], coef[3][c] = rs;
     }
     if (h == 0) {
@@ -502,8 +502,8 @@ __global__ __launch_bounds__(256) void h16_expand_kernel(const unsigned* __restr
     float a = bf_lo(w), b = bf_hi(w);
     if (bn.mean) {
         const int c = (int)((2 * e) & 1023);
-        const H16Affine a0 = h16_affine(bn.mean[c], bn.var[c], bn.gamma[c], bn.beta[c], bn.eps);
-        const H16Affine a1 = h16_affine(bn.mean[c + 1], bn.var[c + 1], bn.gamma[c + 1], bn.beta[c + 1], bn.eps);
+        const BnAffine a0 = bn_affine(bn.mean[c], bn.var[c], bn.gamma[c], bn.beta[c], bn.eps);
+        const BnAffine a1 = bn_affine(bn.mean[c + 1], bn.var[c + 1], bn.gamma[c + 1], bn.beta[c + 1], bn.eps);
         const float r = rn ? rn[(2 * e) >> 10] : 1.f;
         a = fmaxf(a * a0.s + a0.t, 0.f) * r, b = fmaxf(b * a1.s + a1.t, 0.f) * r;
     }
@@ -522,7 +522,7 @@ extern "C" int epc_h16_conv5_fwd(const void* cat, int cat_is_bf16, const float* 
     EPC_CHECK_ARG(cat && W5 && b5 && z5 && mean && var && scratch, "null pointer");
     EPC_CHECK_ARG(rows > 0 && rows % 32 == 0 && (long)rows * 1024 < (1L << 32), "rows must be a positive multiple of 32 (rows * 1024 < 2^32)");
     EPC_CHECK_ARG(scratch_bytes >= epc_h16_conv5_fwd_scratch_bytes(rows), "scratch too small (epc_h16_conv5_fwd_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(cat) && h16_aligned16(z5) && h16_aligned16(scratch) && h16_aligned16(b5), "tensors must be 16-byte aligned");
+    EPC_CHECK_ARG(epc_aligned16(cat) && epc_aligned16(z5) && epc_aligned16(scratch) && epc_aligned16(b5), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     h16_pack<1>(W5, 1024, 1, 0, 1, 256, 1024, 0, 4, scratch, st);
     float* stats = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (size_t)256 * 1024 * 2);
@@ -536,117 +536,41 @@ extern "C" int epc_h16_conv5_fwd(const void* cat, int cat_is_bf16, const float* 
     return EPC_OK;
 }
 
-extern "C" size_t epc_h16_assign_scratch_bytes(int num_clouds, int n_points, int per_cloud_operand) {
-    if (num_clouds <= 0 || n_points <= 0) return 0;
-    const size_t pack = (size_t)(per_cloud_operand ? num_clouds : 1) * 1024 * 64 * 2;
-    const size_t tiles = (size_t)num_clouds * ((n_points + 127) / 128), tiles96 = ((size_t)num_clouds * n_points + 95) / 96;
-    return pack + (tiles > tiles96 ? tiles : tiles96) * 3 * 64 * sizeof(float);   // (the shared-operand launch may tile the rows by 96)
-}
+// The entry points shared with train_head32.hip (train_head_common.h has their bodies): bf16 rows, one bf16 piece per operand
+struct H16Arith {
+    typedef u16 T;
+    static constexpr const char* NAME = "epc_h16";
+    static constexpr int P = 1, KSC_ASSIGN = 4, KSC_DX = 4, ASSIGN_SLOTS = 4, COL_TILES = 8, ASSIGN_PACK_BYTES = 2;
+};
 
-// za = rn (relu(bn(z5)) B): B = Wc (1024, 64) shared (per_cloud_operand = 0: the forward; rn and the batch moments of za are written when
-// their pointers are given) or B = dvlad (num_clouds, 1024, 64) (per_cloud_operand = 1: da of the backward).
+extern "C" size_t epc_h16_assign_scratch_bytes(int num_clouds, int n_points, int per_cloud_operand) {
+    return hx_assign_scratch_bytes<H16Arith>(num_clouds, n_points, per_cloud_operand);
+}
 extern "C" int epc_h16_assign(const void* z5, const float* mean5, const float* var5, const float* gamma5, const float* beta5, float eps,
                               const float* B, int per_cloud_operand, int num_clouds, int n_points, float* out, float* rn_out,
                               float* mean_out, float* var_out, void* scratch, size_t scratch_bytes, void* stream) {
-    EPC_CHECK_ARG(z5 && mean5 && var5 && gamma5 && beta5 && B && out && scratch, "null pointer");
-    EPC_CHECK_ARG(num_clouds > 0 && num_clouds <= 65535 && n_points > 0 && n_points % 32 == 0, "n_points must be a positive multiple of 32");
-    EPC_CHECK_ARG((mean_out == nullptr) == (var_out == nullptr), "mean_out and var_out come together");
-    EPC_CHECK_ARG(scratch_bytes >= epc_h16_assign_scratch_bytes(num_clouds, n_points, per_cloud_operand), "scratch too small (epc_h16_assign_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(z5) && h16_aligned16(scratch) && h16_aligned16(out), "tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = per_cloud_operand ? num_clouds : 1;
-    h16_pack<1>(B, 64, 1, (long)1024 * 64, nb, 1024, 64, 1, 4, scratch, st);
-    float* stats = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (size_t)nb * 1024 * 64 * 2);
-    const dim3 grid((n_points + 127) / 128, num_clouds);
-    const H16Bn bn{mean5, var5, gamma5, beta5, eps};
-    const long rows = (long)num_clouds * n_points;
-    if (!per_cloud_operand && rows < (1L << 31) && rows_tile_waves((int)rows, 4 * epc_device_cu_count()) == 3) {
-        // one operand for every row: the tiles need not respect the clouds -- 96-row workgroups where they spread evenly over the CUs
-        // (18 x 4096 rows: 768 of them, three per CU; 576 of 128 rows leave a quarter of the CUs a third more)
-        const int wgs = (int)((rows + 95) / 96);
-        hipLaunchKernelGGL((hx_rowgemm_kernel<2, true, u16, 1, 4, false, 3>), dim3(wgs, 1), dim3(192), 0, st, (const u16*)z5, (int)rows,
-                           (const u32x4*)scratch, 0L, bn, out, rn_out, mean_out ? stats : nullptr, HxBnb<u16>{});
-        if (mean_out) epc_moments_finalize_launch(stats, wgs, 64, (int)rows, 96, nullptr, mean_out, var_out, stream);
-        EPC_CHECK_LAUNCH();
-        return EPC_OK;
-    }
-    hipLaunchKernelGGL((hx_rowgemm_kernel<2, true, u16, 1, 4>), grid, dim3(256), 0, st, (const u16*)z5, n_points, (const u32x4*)scratch,
-                       per_cloud_operand ? (long)(1024 * 64 * 2 / 16) : 0L, bn, out, rn_out, mean_out ? stats : nullptr, HxBnb<u16>{});
-    if (mean_out) epc_moments_finalize_launch(stats, (int)(grid.x * grid.y), 64, num_clouds * n_points, 128, nullptr, mean_out, var_out, stream, n_points);
-    EPC_CHECK_LAUNCH();
-    return EPC_OK;
+    return hx_assign<H16Arith>((const u16*)z5, mean5, var5, gamma5, beta5, eps, B, per_cloud_operand, num_clouds, n_points, out, rn_out, mean_out,
+                               var_out, scratch, scratch_bytes, stream);
 }
 
-extern "C" size_t epc_h16_dx_scratch_bytes(void) { return (size_t)1024 * 256 * 2; }
-
-// dcat (rows, 256) f32 = dz5 (rows, 1024) bf16 times W5^T (W5: (256, 1024) f32, rounded to bf16 here)
+extern "C" size_t epc_h16_dx_scratch_bytes(void) { return hx_dx_scratch_bytes<H16Arith>(); }
 extern "C" int epc_h16_conv5_dx(const void* dz5, const float* W5, int rows, float* dcat, void* scratch, size_t scratch_bytes, void* stream) {
-    EPC_CHECK_ARG(dz5 && W5 && dcat && scratch, "null pointer");
-    EPC_CHECK_ARG(rows > 0 && rows % 32 == 0, "rows must be a positive multiple of 32");
-    EPC_CHECK_ARG(scratch_bytes >= epc_h16_dx_scratch_bytes(), "scratch too small (epc_h16_dx_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(dz5) && h16_aligned16(scratch) && h16_aligned16(dcat), "tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    h16_pack<1>(W5, 1, 1024, 0, 1, 1024, 256, 1, 4, scratch, st);      // B[k = output channel][n = input channel] = W5[n][k]
-    const H16Bn none{nullptr, nullptr, nullptr, nullptr, 0.f};
-    hipLaunchKernelGGL((hx_rowgemm_kernel<8, false, u16, 1, 4>), dim3((rows + 127) / 128, 1), dim3(256), 0, st, (const u16*)dz5, rows,
-                       (const u32x4*)scratch, 0L, none, dcat, (float*)nullptr, (float*)nullptr, HxBnb<u16>{});
-    EPC_CHECK_LAUNCH();
-    return EPC_OK;
+    return hx_conv5_dx<H16Arith>((const u16*)dz5, W5, rows, dcat, scratch, scratch_bytes, stream);
 }
-
-// epc_h16_bn_bwd_apply and epc_h16_conv5_dx in ONE pass: dz5 = gamma rstd (du - dbeta / rows - zhat dgamma / rows) is formed from du and z5 as
-// they stream, written once (dz5 may be du) for dW5's product, and multiplied with W5^T from registers: dcat (rows, 256) f32.
+// (epc_h16_bn_bwd_apply and epc_h16_conv5_dx in one pass; dz5 may be du)
 extern "C" int epc_h16_conv5_dx_bn(const void* du, const void* z5, const float* mean5, const float* var5, const float* gamma5, float eps,
                                    const float* dbeta, const float* dgamma, const float* W5, int rows, void* dz5, float* dcat, void* scratch,
                                    size_t scratch_bytes, void* stream) {
-    EPC_CHECK_ARG(du && z5 && mean5 && var5 && gamma5 && dbeta && dgamma && W5 && dz5 && dcat && scratch, "null pointer");
-    EPC_CHECK_ARG(rows > 0 && rows % 32 == 0, "rows must be a positive multiple of 32");
-    EPC_CHECK_ARG(scratch_bytes >= epc_h16_dx_scratch_bytes(), "scratch too small (epc_h16_dx_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(du) && h16_aligned16(z5) && h16_aligned16(dz5) && h16_aligned16(scratch) && h16_aligned16(dcat),
-                  "tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    h16_pack<1>(W5, 1, 1024, 0, 1, 1024, 256, 1, 4, scratch, st);      // B[k = output channel][n = input channel] = W5[n][k]
-    const H16Bn bn{mean5, var5, gamma5, nullptr, eps};
-    const HxBnb<u16> bnb{(const u16*)z5, dbeta, dgamma, 1.0f / rows, (u16*)dz5};
-    // 96- or 128-row workgroups, whichever leaves fewer rows on the busiest slot (two workgroups per CU: 235-248 registers a lane)
-    if (rows_tile_waves(rows, 2 * epc_device_cu_count()) == 3)
-        hipLaunchKernelGGL((hx_rowgemm_kernel<8, false, u16, 1, 4, true, 3>), dim3((rows + 95) / 96, 1), dim3(192), 0, st, (const u16*)du, rows,
-                       (const u32x4*)scratch, 0L, bn, dcat, (float*)nullptr, (float*)nullptr, bnb);
-    else
-        hipLaunchKernelGGL((hx_rowgemm_kernel<8, false, u16, 1, 4, true, 4>), dim3((rows + 127) / 128, 1), dim3(256), 0, st, (const u16*)du, rows,
-                       (const u32x4*)scratch, 0L, bn, dcat, (float*)nullptr, (float*)nullptr, bnb);
-    EPC_CHECK_LAUNCH();
-    return EPC_OK;
+    return hx_conv5_dx_bn<H16Arith>((const u16*)du, (const u16*)z5, mean5, var5, gamma5, eps, dbeta, dgamma, W5, rows, (u16*)dz5, dcat, scratch,
+                                    scratch_bytes, stream);
 }
 
-
-extern "C" size_t epc_h16_colgemm_scratch_bytes(int num_clouds, int n_points) {
-    if (num_clouds <= 0 || n_points <= 0) return 0;
-    return (size_t)num_clouds * h16_splits(num_clouds, n_points, 8) * 1024 * 64 * sizeof(float);
-}
-
-// out = relu(bn(z5))^T (rn C): per cloud (per_cloud = 1: out (num_clouds, 1024, 64), the VLAD aggregation with C = a) or over all rows
-// (per_cloud = 0: out (1024, 64), the cluster weights' gradient with C = dz).  C: (rows, 64) f32.
+extern "C" size_t epc_h16_colgemm_scratch_bytes(int num_clouds, int n_points) { return hx_colgemm_scratch_bytes<H16Arith>(num_clouds, n_points); }
 extern "C" int epc_h16_colgemm(const void* z5, const float* mean5, const float* var5, const float* gamma5, const float* beta5, float eps,
                                const float* C, const float* rn, int num_clouds, int n_points, int per_cloud, float* out, void* scratch,
                                size_t scratch_bytes, void* stream) {
-    EPC_CHECK_ARG(z5 && mean5 && var5 && gamma5 && beta5 && C && rn && out && scratch, "null pointer");
-    EPC_CHECK_ARG(num_clouds > 0 && n_points > 0 && n_points % 32 == 0 && (long)num_clouds * h16_splits(num_clouds, n_points, 8) <= 65535, "bad shape");
-    EPC_CHECK_ARG(scratch_bytes >= epc_h16_colgemm_scratch_bytes(num_clouds, n_points), "scratch too small (epc_h16_colgemm_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(z5) && h16_aligned16(scratch) && h16_aligned16(out), "tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int S = h16_splits(num_clouds, n_points, 8);
-    const int rows_per_wg = (n_points + S - 1) / S;
-    const H16Bn bn{mean5, var5, gamma5, beta5, eps};
-    hipLaunchKernelGGL((hx_colgemm_kernel<u16, 1>), dim3(8, num_clouds * S), dim3(256), 0, st, (const u16*)z5, bn, C, rn, rows_per_wg, n_points, S,
-                       (float*)scratch);
-    const long per = 1024 * 64;
-    if (per_cloud)
-        hipLaunchKernelGGL(h16_partial_reduce_kernel, dim3((unsigned)(per / 4 / 256), num_clouds), dim3(256), 0, st, (const float*)scratch, S, per, out);
-    else
-        hipLaunchKernelGGL(h16_partial_reduce_kernel, dim3((unsigned)(per / 4 / 256), 1), dim3(256), 0, st, (const float*)scratch, num_clouds * S, per, out);
-    EPC_CHECK_LAUNCH();
-    return EPC_OK;
+    return hx_colgemm<H16Arith>((const u16*)z5, mean5, var5, gamma5, beta5, eps, C, rn, num_clouds, n_points, per_cloud, out, scratch, scratch_bytes,
+                                stream);
 }
 
 extern "C" size_t epc_h16_df_tail_scratch_bytes(int num_clouds, int n_points) {
@@ -663,8 +587,8 @@ extern "C" int epc_h16_df_tail(const float* a, const float* dz, const float* dvl
     EPC_CHECK_ARG(num_clouds > 0 && num_clouds <= 65535 && n_points > 0 && n_points % 32 == 0 && (long)num_clouds * n_points * 1024 < (1L << 32),
                   "bad shape (n_points a multiple of 32; rows * 1024 < 2^32)");
     EPC_CHECK_ARG(scratch_bytes >= epc_h16_df_tail_scratch_bytes(num_clouds, n_points), "scratch too small (epc_h16_df_tail_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(a) && h16_aligned16(dz) && h16_aligned16(dvlad) && h16_aligned16(Wc) && h16_aligned16(z5) && h16_aligned16(du) &&
-                      h16_aligned16(scratch) && h16_aligned16(dbeta_dgamma),
+    EPC_CHECK_ARG(epc_aligned16(a) && epc_aligned16(dz) && epc_aligned16(dvlad) && epc_aligned16(Wc) && epc_aligned16(z5) && epc_aligned16(du) &&
+                      epc_aligned16(scratch) && epc_aligned16(dbeta_dgamma),
                   "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(h16_df_pack_kernel, dim3(16, num_clouds), dim3(256), 0, st, dvlad, Wc, (u32x4*)scratch);
@@ -682,7 +606,7 @@ extern "C" int epc_h16_bn_bwd_apply(const void* du, const void* z5, const float*
                                     void* stream) {
     EPC_CHECK_ARG(du && z5 && mean5 && var5 && gamma5 && beta5 && dbeta && dgamma && dz5, "null pointer");
     EPC_CHECK_ARG(rows > 0, "bad shape");
-    EPC_CHECK_ARG(h16_aligned16(du) && h16_aligned16(z5) && h16_aligned16(dz5), "tensors must be 16-byte aligned");
+    EPC_CHECK_ARG(epc_aligned16(du) && epc_aligned16(z5) && epc_aligned16(dz5), "tensors must be 16-byte aligned");
     const H16Bn bn{mean5, var5, gamma5, beta5, eps};
     hipLaunchKernelGGL(h16_bn_bwd_apply_kernel, dim3((rows + BA_ROWS - 1) / BA_ROWS), dim3(256), 0, (hipStream_t)stream, (const u32x4*)du,
                        (const u32x4*)z5, bn, dbeta, dgamma, 1.0f / rows, rows, (u32x4*)dz5);
@@ -707,17 +631,13 @@ extern "C" int epc_h16_conv5_dw(const void* cat, int cat_is_bf16, const void* dz
     EPC_CHECK_ARG(cat && dz5 && dW5 && scratch, "null pointer");
     EPC_CHECK_ARG(rows > 0 && (long)rows * 1024 < (1L << 32), "bad shape");
     EPC_CHECK_ARG(scratch_bytes >= epc_h16_conv5_dw_scratch_bytes(rows), "scratch too small (epc_h16_conv5_dw_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(cat) && h16_aligned16(dz5) && h16_aligned16(dW5) && h16_aligned16(scratch), "tensors must be 16-byte aligned");
+    EPC_CHECK_ARG(epc_aligned16(cat) && epc_aligned16(dz5) && epc_aligned16(dW5) && epc_aligned16(scratch), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int S = h16_dw5_splits(rows);
     const int rows_per_wg = ((rows + S - 1) / S + 63) / 64 * 64;
     const size_t lds = (size_t)2 * 2 * DW_STEP_U4 * sizeof(u32x4);     // 128 KB
     const void* fn = cat_is_bf16 ? reinterpret_cast<const void*>(h16_dw5_kernel<false>) : reinterpret_cast<const void*>(h16_dw5_kernel<true>);
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-        epc_set_error("epc_h16_conv5_dw: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    EPC_SET_DYN_LDS(fn, lds);
     if (cat_is_bf16)
         hipLaunchKernelGGL(h16_dw5_kernel<false>, dim3(4, S), dim3(512), lds, st, cat, (const u16*)dz5, rows, rows_per_wg, (float*)scratch);
     else

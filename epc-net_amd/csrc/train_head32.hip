@@ -346,7 +346,7 @@ extern "C" int epc_h32_conv5_fwd(const float* cat, const float* W5, const float*
     EPC_CHECK_ARG(cat && W5 && b5 && z5 && mean && var && scratch, "null pointer");
     EPC_CHECK_ARG(rows > 0 && rows % 32 == 0 && (long)rows * 1024 < (1L << 32), "rows must be a positive multiple of 32 (rows * 1024 < 2^32)");
     EPC_CHECK_ARG(scratch_bytes >= epc_h32_conv5_fwd_scratch_bytes(rows), "scratch too small (epc_h32_conv5_fwd_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(cat) && h16_aligned16(z5) && h16_aligned16(scratch), "tensors must be 16-byte aligned");
+    EPC_CHECK_ARG(epc_aligned16(cat) && epc_aligned16(z5) && epc_aligned16(scratch), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     u32x4* pack = (u32x4*)scratch;
     float* inv_col = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (size_t)256 * 1024 * 4);
@@ -362,116 +362,40 @@ extern "C" int epc_h32_conv5_fwd(const float* cat, const float* W5, const float*
     return EPC_OK;
 }
 
-extern "C" size_t epc_h32_assign_scratch_bytes(int num_clouds, int n_points, int per_cloud_operand) {
-    if (num_clouds <= 0 || n_points <= 0) return 0;
-    const size_t pack = (size_t)(per_cloud_operand ? num_clouds : 1) * 1024 * 64 * 2 * 3;
-    const size_t tiles = (size_t)num_clouds * ((n_points + 127) / 128), tiles96 = ((size_t)num_clouds * n_points + 95) / 96;
-    return pack + (tiles > tiles96 ? tiles : tiles96) * 3 * 64 * sizeof(float);   // (the shared-operand launch may tile the rows by 96)
-}
+// The entry points shared with train_head16.hip (train_head_common.h has their bodies): f32 rows, two bf16 pieces per operand (three
+// products); the assignment's scratch keeps the room of a three-piece pack
+struct H32Arith {
+    typedef float T;
+    static constexpr const char* NAME = "epc_h32";
+    static constexpr int P = 2, KSC_ASSIGN = 4, KSC_DX = 2, ASSIGN_SLOTS = 3, COL_TILES = 16, ASSIGN_PACK_BYTES = 6;
+};
 
-// epc_h16_assign on f32 rows: out (rows, 64) = rn (relu(bn(z5)) B), three products.  per_cloud_operand = 0: B = cluster_weights (the
-// forward's logits; rn_out / mean_out / var_out written when given); 1: B = dvlad (num_clouds, 1024, 64) (da).
+extern "C" size_t epc_h32_assign_scratch_bytes(int num_clouds, int n_points, int per_cloud_operand) {
+    return hx_assign_scratch_bytes<H32Arith>(num_clouds, n_points, per_cloud_operand);
+}
 extern "C" int epc_h32_assign(const float* z5, const float* mean5, const float* var5, const float* gamma5, const float* beta5, float eps,
                               const float* B, int per_cloud_operand, int num_clouds, int n_points, float* out, float* rn_out,
                               float* mean_out, float* var_out, void* scratch, size_t scratch_bytes, void* stream) {
-    EPC_CHECK_ARG(z5 && mean5 && var5 && gamma5 && beta5 && B && out && scratch, "null pointer");
-    EPC_CHECK_ARG(num_clouds > 0 && num_clouds <= 65535 && n_points > 0 && n_points % 32 == 0, "n_points must be a positive multiple of 32");
-    EPC_CHECK_ARG((mean_out == nullptr) == (var_out == nullptr), "mean_out and var_out come together");
-    EPC_CHECK_ARG(scratch_bytes >= epc_h32_assign_scratch_bytes(num_clouds, n_points, per_cloud_operand), "scratch too small (epc_h32_assign_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(z5) && h16_aligned16(scratch) && h16_aligned16(out), "tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = per_cloud_operand ? num_clouds : 1;
-    // two pieces (three products, 2^-16 per product): the logits are sums of 1024 products whose errors average out (5e-7 of a logit,
-    // measured against the float64 graph: tests/test_gpu_head_stream.py) -- the six-product form took 116 us against 93
-    float* stats = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (size_t)nb * 1024 * 64 * 2 * 3);
-    const dim3 grid((n_points + 127) / 128, num_clouds);
-    const H16Bn bn{mean5, var5, gamma5, beta5, eps};
-    h16_pack<2>(B, 64, 1, (long)1024 * 64, nb, 1024, 64, 1, 4, scratch, st);
-    const long rows = (long)num_clouds * n_points;
-    if (!per_cloud_operand && rows < (1L << 31) && rows_tile_waves((int)rows, 3 * epc_device_cu_count()) == 3) {
-        // one operand for every row: the tiles need not respect the clouds -- 96-row workgroups where they fill the CU's three slots evenly
-        // (18 x 4096 rows: 768 of them, three per CU; 576 of 128 rows leave a quarter of the CUs a third more)
-        const int wgs = (int)((rows + 95) / 96);
-        hipLaunchKernelGGL((hx_rowgemm_kernel<2, true, float, 2, 4, false, 3>), dim3(wgs, 1), dim3(192), 0, st, z5, (int)rows, (const u32x4*)scratch,
-                           0L, bn, out, rn_out, mean_out ? stats : nullptr, HxBnb<float>{});
-        if (mean_out) epc_moments_finalize_launch(stats, wgs, 64, (int)rows, 96, nullptr, mean_out, var_out, stream);
-        EPC_CHECK_LAUNCH();
-        return EPC_OK;
-    }
-    hipLaunchKernelGGL((hx_rowgemm_kernel<2, true, float, 2, 4>), grid, dim3(256), 0, st, z5, n_points, (const u32x4*)scratch,
-                       per_cloud_operand ? (long)(1024 * 64 * 2 * 2 / 16) : 0L, bn, out, rn_out, mean_out ? stats : nullptr, HxBnb<float>{});
-    if (mean_out) epc_moments_finalize_launch(stats, (int)(grid.x * grid.y), 64, num_clouds * n_points, 128, nullptr, mean_out, var_out, stream, n_points);
-    EPC_CHECK_LAUNCH();
-    return EPC_OK;
+    return hx_assign<H32Arith>(z5, mean5, var5, gamma5, beta5, eps, B, per_cloud_operand, num_clouds, n_points, out, rn_out, mean_out, var_out,
+                               scratch, scratch_bytes, stream);
 }
 
-extern "C" size_t epc_h32_colgemm_scratch_bytes(int num_clouds, int n_points) {
-    if (num_clouds <= 0 || n_points <= 0) return 0;
-    return (size_t)num_clouds * h16_splits(num_clouds, n_points, 16) * 1024 * 64 * sizeof(float);
-}
-
-// epc_h16_colgemm on f32 rows, two bf16 pieces per operand (three products): out = relu(bn(z5))^T (rn C)
+extern "C" size_t epc_h32_colgemm_scratch_bytes(int num_clouds, int n_points) { return hx_colgemm_scratch_bytes<H32Arith>(num_clouds, n_points); }
 extern "C" int epc_h32_colgemm(const float* z5, const float* mean5, const float* var5, const float* gamma5, const float* beta5, float eps,
                                const float* C, const float* rn, int num_clouds, int n_points, int per_cloud, float* out, void* scratch,
                                size_t scratch_bytes, void* stream) {
-    EPC_CHECK_ARG(z5 && mean5 && var5 && gamma5 && beta5 && C && rn && out && scratch, "null pointer");
-    EPC_CHECK_ARG(num_clouds > 0 && n_points > 0 && n_points % 32 == 0 && (long)num_clouds * h16_splits(num_clouds, n_points, 16) <= 65535, "bad shape");
-    EPC_CHECK_ARG(scratch_bytes >= epc_h32_colgemm_scratch_bytes(num_clouds, n_points), "scratch too small (epc_h32_colgemm_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(z5) && h16_aligned16(scratch) && h16_aligned16(out), "tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int S = h16_splits(num_clouds, n_points, 16);
-    const int rows_per_wg = (n_points + S - 1) / S;
-    const H16Bn bn{mean5, var5, gamma5, beta5, eps};
-    hipLaunchKernelGGL((hx_colgemm_kernel<float, 2>), dim3(16, num_clouds * S), dim3(256), 0, st, z5, bn, C, rn, rows_per_wg, n_points, S,
-                       (float*)scratch);
-    const long per = 1024 * 64;
-    if (per_cloud)
-        hipLaunchKernelGGL(h16_partial_reduce_kernel, dim3((unsigned)(per / 4 / 256), num_clouds), dim3(256), 0, st, (const float*)scratch, S, per, out);
-    else
-        hipLaunchKernelGGL(h16_partial_reduce_kernel, dim3((unsigned)(per / 4 / 256), 1), dim3(256), 0, st, (const float*)scratch, num_clouds * S, per, out);
-    EPC_CHECK_LAUNCH();
-    return EPC_OK;
+    return hx_colgemm<H32Arith>(z5, mean5, var5, gamma5, beta5, eps, C, rn, num_clouds, n_points, per_cloud, out, scratch, scratch_bytes, stream);
 }
 
-extern "C" size_t epc_h32_dx_scratch_bytes(void) { return (size_t)1024 * 256 * 2 * 2; }
-
-// dcat (rows, 256) f32 = dz5 (rows, 1024) f32 times W5^T, two bf16 pieces per operand (three products)
+extern "C" size_t epc_h32_dx_scratch_bytes(void) { return hx_dx_scratch_bytes<H32Arith>(); }
 extern "C" int epc_h32_conv5_dx(const float* dz5, const float* W5, int rows, float* dcat, void* scratch, size_t scratch_bytes, void* stream) {
-    EPC_CHECK_ARG(dz5 && W5 && dcat && scratch, "null pointer");
-    EPC_CHECK_ARG(rows > 0 && rows % 32 == 0, "rows must be a positive multiple of 32");
-    EPC_CHECK_ARG(scratch_bytes >= epc_h32_dx_scratch_bytes(), "scratch too small (epc_h32_dx_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(dz5) && h16_aligned16(scratch) && h16_aligned16(dcat), "tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    h16_pack<2>(W5, 1, 1024, 0, 1, 1024, 256, 1, 2, scratch, st);      // B[k = output channel][n = input channel] = W5[n][k]
-    const H16Bn none{nullptr, nullptr, nullptr, nullptr, 0.f};
-    hipLaunchKernelGGL((hx_rowgemm_kernel<8, false, float, 2, 2>), dim3((rows + 127) / 128, 1), dim3(256), 0, st, dz5, rows,
-                       (const u32x4*)scratch, 0L, none, dcat, (float*)nullptr, (float*)nullptr, HxBnb<float>{});
-    EPC_CHECK_LAUNCH();
-    return EPC_OK;
+    return hx_conv5_dx<H32Arith>(dz5, W5, rows, dcat, scratch, scratch_bytes, stream);
 }
-
-// epc_bn_apply_bwd_given and epc_h32_conv5_dx in ONE pass (epc_h16_conv5_dx_bn on f32 tensors, two bf16 pieces per operand)
+// (epc_bn_apply_bwd_given and epc_h32_conv5_dx in one pass; dz5 may be du)
 extern "C" int epc_h32_conv5_dx_bn(const float* du, const float* z5, const float* mean5, const float* var5, const float* gamma5, float eps,
                                    const float* dbeta, const float* dgamma, const float* W5, int rows, float* dz5, float* dcat, void* scratch,
                                    size_t scratch_bytes, void* stream) {
-    EPC_CHECK_ARG(du && z5 && mean5 && var5 && gamma5 && dbeta && dgamma && W5 && dz5 && dcat && scratch, "null pointer");
-    EPC_CHECK_ARG(rows > 0 && rows % 32 == 0, "rows must be a positive multiple of 32");
-    EPC_CHECK_ARG(scratch_bytes >= epc_h32_dx_scratch_bytes(), "scratch too small (epc_h32_dx_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(du) && h16_aligned16(z5) && h16_aligned16(dz5) && h16_aligned16(scratch) && h16_aligned16(dcat),
-                  "tensors must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    h16_pack<2>(W5, 1, 1024, 0, 1, 1024, 256, 1, 2, scratch, st);      // B[k = output channel][n = input channel] = W5[n][k]
-    const H16Bn bn{mean5, var5, gamma5, nullptr, eps};
-    const HxBnb<float> bnb{z5, dbeta, dgamma, 1.0f / rows, dz5};
-    // 96- or 128-row workgroups, whichever leaves fewer rows on the busiest slot (two workgroups per CU: 235-248 registers a lane)
-    if (rows_tile_waves(rows, 2 * epc_device_cu_count()) == 3)
-        hipLaunchKernelGGL((hx_rowgemm_kernel<8, false, float, 2, 2, true, 3>), dim3((rows + 95) / 96, 1), dim3(192), 0, st, du, rows,
-                       (const u32x4*)scratch, 0L, bn, dcat, (float*)nullptr, (float*)nullptr, bnb);
-    else
-        hipLaunchKernelGGL((hx_rowgemm_kernel<8, false, float, 2, 2, true, 4>), dim3((rows + 127) / 128, 1), dim3(256), 0, st, du, rows,
-                       (const u32x4*)scratch, 0L, bn, dcat, (float*)nullptr, (float*)nullptr, bnb);
-    EPC_CHECK_LAUNCH();
-    return EPC_OK;
+    return hx_conv5_dx_bn<H32Arith>(du, z5, mean5, var5, gamma5, eps, dbeta, dgamma, W5, rows, dz5, dcat, scratch, scratch_bytes, stream);
 }
 
 static int h32_dw5_splits(int rows) {
@@ -490,16 +414,12 @@ extern "C" int epc_h32_conv5_dw(const float* cat, const float* dz5, int rows, fl
     EPC_CHECK_ARG(cat && dz5 && dW5 && scratch, "null pointer");
     EPC_CHECK_ARG(rows > 0 && (long)rows * 1024 < (1L << 32), "bad shape");
     EPC_CHECK_ARG(scratch_bytes >= epc_h32_conv5_dw_scratch_bytes(rows), "scratch too small (epc_h32_conv5_dw_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(cat) && h16_aligned16(dz5) && h16_aligned16(dW5) && h16_aligned16(scratch), "tensors must be 16-byte aligned");
+    EPC_CHECK_ARG(epc_aligned16(cat) && epc_aligned16(dz5) && epc_aligned16(dW5) && epc_aligned16(scratch), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int S = h32_dw5_splits(rows);
     const int rows_per_wg = ((rows + S - 1) / S + 31) / 32 * 32;
     const size_t lds = (size_t)2 * 2 * DW32_STEP_U4 * sizeof(u32x4);     // 128 KB
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(h32_dw5_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-        epc_set_error("epc_h32_conv5_dw: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return EPC_EHIP;
-    }
+    EPC_SET_DYN_LDS(h32_dw5_kernel, lds);
     hipLaunchKernelGGL(h32_dw5_kernel, dim3(4, S), dim3(512), lds, st, cat, dz5, rows, rows_per_wg, (float*)scratch);
     const long per = 256 * 1024;
     hipLaunchKernelGGL(h16_partial_reduce_kernel, dim3((unsigned)(per / 4 / 256), 1), dim3(256), 0, st, (const float*)scratch, S, per, dW5);

@@ -3,7 +3,7 @@
 // column product with the rows as the contraction (hx_colgemm_kernel) and the ordered reduction of row-slice partials.  The kernels are
 // templates over the storage type of the (rows, 1024) tensor (u16 = bf16, float) and the number of bf16 pieces per operand.
 #pragma once
-#include "common.h"
+#include "train_common.h"
 
 typedef unsigned short u16;
 
@@ -22,23 +22,11 @@ __device__ __forceinline__ bf16x8 cvt8(const float (&v)[8]) {
     for (int j = 0; j < 8; ++j) p[j] = (__bf16)v[j];
     return p;
 }
-// P bf16 pieces of 8 values: p[0] = bf16(v), p[1] = bf16(v - p[0]), p[2] = bf16(v - p[0] - p[1])  (8 significant bits each)
+// bf16_prod<P> for P <= 2 as a loop over the piece sums: the same products in the same order.  Kept for hx_colgemm_kernel alone, whose
+// f32 two-piece instantiation sits at the register limit of two waves per SIMD and is allocated differently around the straight-line form.
 template <int P>
-__device__ __forceinline__ void hx_split(const float (&v)[8], bf16x8 (&p)[P]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float r = v[j];
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-            p[q][j] = (__bf16)r;
-            if (q + 1 < P) r -= (float)p[q][j];
-        }
-    }
-}
-// acc += the products of two P-piece operands whose piece indices sum to less than P, smallest terms first: P = 1 one product,
-// P = 2 three (2^-16 per product: the backward arithmetic of epc_gemm_f32_fast), P = 3 six (f32-accurate: epc_gemm_f32's)
-template <int P>
-__device__ __forceinline__ f32x16 hx_prod(const bf16x8 (&a)[P], const bf16x8 (&b)[P], f32x16 c) {
+__device__ __forceinline__ f32x16 hx_colgemm_prod(const bf16x8 (&a)[P], const bf16x8 (&b)[P], f32x16 c) {
+    static_assert(P <= 2, "for three pieces bf16_prod's order differs");
 #pragma unroll
     for (int sum = P - 1; sum >= 0; --sum)
 #pragma unroll
@@ -46,15 +34,6 @@ __device__ __forceinline__ f32x16 hx_prod(const bf16x8 (&a)[P], const bf16x8 (&b
     return c;
 }
 
-struct H16Affine {   // y = z s + t: the expression train_ops.hip's bn_value evaluates (same association, contracted to one FMA)
-    float s, t;
-};
-__device__ __forceinline__ H16Affine h16_affine(float mean, float var, float gamma, float beta, float eps) {
-    H16Affine a;
-    a.s = (1.0f / sqrtf(var + eps)) * gamma;
-    a.t = beta - mean * a.s;
-    return a;
-}
 struct H16Bn {
     const float *mean, *var, *gamma, *beta;
     float eps;
@@ -96,7 +75,7 @@ __global__ __launch_bounds__(256) void h16_pack_kernel(const float* __restrict__
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = src[(size_t)j * sk];
     bf16x8 p[P];
-    hx_split<P>(v, p);
+    bf16_split<P>(v, p);
     // entry e of the one-piece order becomes P consecutive 64-lane groups: [.. (e >> 6)][piece][lane]
     u32x4* dst = out + (size_t)blockIdx.y * per * P + (size_t)(e >> 6) * P * 64 + l;
 #pragma unroll
@@ -134,7 +113,7 @@ __device__ __forceinline__ void h16_merge_stats(const float (*w)[3][64], const b
 //   XFORM: T = relu(batch_norm(.)) per channel (conv5's BatchNorm from its batch moments; coefficients in LDS) and the row factor
 //          rn = rsqrt(max(sum_c u^2, 1e-12)) from the f32 values of u, applied to the accumulators: out = rn (u B).
 //          rn_out != null: rn is written.  stats != null: column statistics of out ([workgroups][3][32 NT], tile_rows = 128).
-//   P: bf16 pieces per operand (hx_prod): 1 = the bf16 arithmetic; 2 / 3 = three / six products on f32 operands.
+//   P: bf16 pieces per operand (bf16_prod): 1 = the bf16 arithmetic; 2 / 3 = three / six products on f32 operands.
 //   NT = 2: the assignment's product and its gradient (B = Wc / dvlad[cloud]);  NT = 8, no XFORM: dcat = dz5 W5^T.
 //   BNB (with NT = 8, no XFORM): A is not read but FORMED -- the last step of conv5's BatchNorm backward,
 //          dz5 = gamma rstd (du - dbeta / R - zhat dgamma / R)   (bn_apply_bwd_given_wide_kernel's / h16_bn_bwd_apply_kernel's expression),
@@ -228,7 +207,7 @@ __global__ __launch_bounds__(64 * NW, 2) void hx_rowgemm_kernel(typename HxAPtr<
     }
     if constexpr (XFORM) {
         for (int c = tid; c < 1024; c += 64 * NW) {
-            const H16Affine a = h16_affine(bn.mean[c], bn.var[c], bn.gamma[c], bn.beta[c], bn.eps);
+            const BnAffine a = bn_affine(bn.mean[c], bn.var[c], bn.gamma[c], bn.beta[c], bn.eps);
             coef[0][c] = a.s, coef[1][c] = a.t;
         }
     }
@@ -289,7 +268,7 @@ __global__ __launch_bounds__(64 * NW, 2) void hx_rowgemm_kernel(typename HxAPtr<
                     if constexpr (A32) {
                         *reinterpret_cast<float4*>(orow) = make_float4(dzv[0], dzv[1], dzv[2], dzv[3]);
                         *reinterpret_cast<float4*>(orow + 4) = make_float4(dzv[4], dzv[5], dzv[6], dzv[7]);
-                        hx_split<P>(dzv, afr[s]);
+                        bf16_split<P>(dzv, afr[s]);
                     } else {
                         u32x4 pk;
 #pragma unroll
@@ -340,14 +319,14 @@ __global__ __launch_bounds__(64 * NW, 2) void hx_rowgemm_kernel(typename HxAPtr<
                             ss += u[j] * u[j];
                         }
                     }
-                    hx_split<P>(u, a);
+                    bf16_split<P>(u, a);
                 }
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     bf16x8 b[P];
 #pragma unroll
                     for (int q = 0; q < P; ++q) b[q] = __builtin_bit_cast(bf16x8, Bs[buf][((s * NT + nt) * P + q) * 64 + lane]);
-                    acc[nt] = hx_prod<P>(a, b, acc[nt]);
+                    acc[nt] = bf16_prod<P>(a, b, acc[nt]);
                 }
             }
         }
@@ -420,7 +399,7 @@ __global__ __launch_bounds__(64 * NW, 2) void hx_rowgemm_kernel(typename HxAPtr<
 // channels (4 per lane and row: 256- or 512-byte runs) and a range of rows; the MFMA's A operand wants 8 consecutive ROWS of one channel
 // per lane, which is a register transposition of the 8 x 4 values a lane loads (free: the conversions write the fragments' elements
 // directly), with the BatchNorm coefficients of the lane's four channels in registers for the whole kernel.  C (rows, 64) f32 is read
-// lane-coalesced (one column per lane), scaled by rn and rounded / split.  P pieces per operand (hx_prod).  A k-step's values are
+// lane-coalesced (one column per lane), scaled by rn and rounded / split.  P pieces per operand (hx_colgemm_prod).  A k-step's values are
 // turned into fragments BEFORE the next step's loads are issued, so the two never hold registers together.  The four waves take a
 // quarter of the rows each and meet in LDS in a fixed order; the splits of a cloud (or of everything) are added by
 // h16_partial_reduce_kernel in ascending order: same bits every run.
@@ -446,7 +425,7 @@ __global__ __launch_bounds__(256, 2) void hx_colgemm_kernel(const TA* __restrict
 #pragma unroll
     for (int q = 0; q < CPL; ++q) {
         const int c = m0 + CPL * i + q;
-        const H16Affine a = h16_affine(bn.mean[c], bn.var[c], bn.gamma[c], bn.beta[c], bn.eps);
+        const BnAffine a = bn_affine(bn.mean[c], bn.var[c], bn.gamma[c], bn.beta[c], bn.eps);
         cs[q] = a.s, ct[q] = a.t;
     }
     f32x16 acc[CPL][2];
@@ -485,7 +464,7 @@ __global__ __launch_bounds__(256, 2) void hx_colgemm_kernel(const TA* __restrict
             float t[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) t[j] = cv[nt][j] * rv[j];
-            hx_split<P>(t, b[nt]);
+            bf16_split<P>(t, b[nt]);
         }
 #pragma unroll
         for (int q = 0; q < CPL; ++q) {
@@ -497,12 +476,12 @@ __global__ __launch_bounds__(256, 2) void hx_colgemm_kernel(const TA* __restrict
                 else z = (q & 1) ? bf_hi(q >> 1 ? zv[j].y : zv[j].x) : bf_lo(q >> 1 ? zv[j].y : zv[j].x);
                 u[j] = fmaxf(z * cs[q] + ct[q], 0.f);
             }
-            hx_split<P>(u, a[q]);
+            bf16_split<P>(u, a[q]);
         }
 #pragma unroll
         for (int q = 0; q < CPL; ++q)
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) acc[q][nt] = hx_prod<P>(a[q], b[nt], acc[q][nt]);
+            for (int nt = 0; nt < 2; ++nt) acc[q][nt] = hx_colgemm_prod<P>(a[q], b[nt], acc[q][nt]);
     }
     // waves 1, 2, 3 hand their accumulators down in turn: ((w0 + w1) + w2) + w3 -- a fixed order
     for (int w = 1; w < 4; ++w) {
@@ -578,4 +557,154 @@ static inline int h16_splits(int num_clouds, int n_points, int tiles) {
     }
     return best;
 }
-static inline bool h16_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
+
+// ----------------------------------------------------------------------------------------------------------------
+// The C entry points the two arithmetics share, written once: epc_h16_* (train_head16.hip) and epc_h32_* (train_head32.hip) forward
+// to these with their traits --
+//   T: storage type of the (rows, 1024) tensors;  P: bf16 pieces per operand;  KSC_ASSIGN / KSC_DX: k-steps per LDS chunk of the
+//   assignment's and of dcat's product;  ASSIGN_SLOTS: workgroups of the assignment co-resident on a CU;  COL_TILES: channel tiles of
+//   the column product (1024 / 128 or 1024 / 64);  ASSIGN_PACK_BYTES: bytes the assignment's scratch reserves per packed value (the
+//   pack itself takes 2 P);  NAME: the entry points' prefix, under which errors are reported.
+// ----------------------------------------------------------------------------------------------------------------
+// (EPC_CHECK_ARG / EPC_CHECK_LAUNCH under the entry point's name A::NAME "_" entry; a second %s in `msg` is A::NAME again)
+#define HX_CHECK_ARG(entry, cond, msg)                                          \
+    do {                                                                        \
+        if (!(cond)) {                                                          \
+            epc_set_error("%s_" entry ": " msg, A::NAME, A::NAME);              \
+            return EPC_EINVAL;                                                  \
+        }                                                                       \
+    } while (0)
+#define HX_CHECK_LAUNCH(entry)                                                                           \
+    do {                                                                                                 \
+        hipError_t e__ = hipGetLastError();                                                              \
+        if (e__ != hipSuccess) {                                                                         \
+            epc_set_error("%s_" entry ": launch failed: %s", A::NAME, hipGetErrorString(e__));           \
+            return EPC_EHIP;                                                                             \
+        }                                                                                                \
+    } while (0)
+
+template <typename A>
+static size_t hx_assign_scratch_bytes(int num_clouds, int n_points, int per_cloud_operand) {
+    if (num_clouds <= 0 || n_points <= 0) return 0;
+    const size_t pack = (size_t)(per_cloud_operand ? num_clouds : 1) * 1024 * 64 * A::ASSIGN_PACK_BYTES;
+    const size_t tiles = (size_t)num_clouds * ((n_points + 127) / 128), tiles96 = ((size_t)num_clouds * n_points + 95) / 96;
+    return pack + (tiles > tiles96 ? tiles : tiles96) * 3 * 64 * sizeof(float);   // (the shared-operand launch may tile the rows by 96)
+}
+
+// za = rn (relu(bn(z5)) B): B = Wc (1024, 64) shared (per_cloud_operand = 0: the forward's logits; rn and the batch moments of za are
+// written when their pointers are given) or B = dvlad (num_clouds, 1024, 64) (per_cloud_operand = 1: da of the backward).
+// (f32 rows: two pieces, three products at 2^-16 each -- the logits are sums of 1024 products whose errors average out, 5e-7 of a logit
+// measured against the float64 graph: tests/test_gpu_head_stream.py; the six-product form took 116 us against 93)
+template <typename A>
+static int hx_assign(const typename A::T* z5, const float* mean5, const float* var5, const float* gamma5, const float* beta5, float eps,
+                     const float* B, int per_cloud_operand, int num_clouds, int n_points, float* out, float* rn_out, float* mean_out,
+                     float* var_out, void* scratch, size_t scratch_bytes, void* stream) {
+    typedef typename A::T T;
+    HX_CHECK_ARG("assign", z5 && mean5 && var5 && gamma5 && beta5 && B && out && scratch, "null pointer");
+    HX_CHECK_ARG("assign", num_clouds > 0 && num_clouds <= 65535 && n_points > 0 && n_points % 32 == 0, "n_points must be a positive multiple of 32");
+    HX_CHECK_ARG("assign", (mean_out == nullptr) == (var_out == nullptr), "mean_out and var_out come together");
+    HX_CHECK_ARG("assign", scratch_bytes >= hx_assign_scratch_bytes<A>(num_clouds, n_points, per_cloud_operand),
+                 "scratch too small (%s_assign_scratch_bytes)");
+    HX_CHECK_ARG("assign", epc_aligned16(z5) && epc_aligned16(scratch) && epc_aligned16(out), "tensors must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = per_cloud_operand ? num_clouds : 1;
+    h16_pack<A::P>(B, 64, 1, (long)1024 * 64, nb, 1024, 64, 1, A::KSC_ASSIGN, scratch, st);
+    float* stats = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (size_t)nb * 1024 * 64 * A::ASSIGN_PACK_BYTES);
+    const dim3 grid((n_points + 127) / 128, num_clouds);
+    const H16Bn bn{mean5, var5, gamma5, beta5, eps};
+    const long rows = (long)num_clouds * n_points;
+    if (!per_cloud_operand && rows < (1L << 31) && rows_tile_waves((int)rows, A::ASSIGN_SLOTS * epc_device_cu_count()) == 3) {
+        // one operand for every row: the tiles need not respect the clouds -- 96-row workgroups where they spread evenly over the CUs' slots
+        // (18 x 4096 rows: 768 of them, three per CU; 576 of 128 rows leave a quarter of the CUs a third more)
+        const int wgs = (int)((rows + 95) / 96);
+        hipLaunchKernelGGL((hx_rowgemm_kernel<2, true, T, A::P, A::KSC_ASSIGN, false, 3>), dim3(wgs, 1), dim3(192), 0, st, z5, (int)rows,
+                           (const u32x4*)scratch, 0L, bn, out, rn_out, mean_out ? stats : nullptr, HxBnb<T>{});
+        if (mean_out) epc_moments_finalize_launch(stats, wgs, 64, (int)rows, 96, nullptr, mean_out, var_out, stream);
+        HX_CHECK_LAUNCH("assign");
+        return EPC_OK;
+    }
+    hipLaunchKernelGGL((hx_rowgemm_kernel<2, true, T, A::P, A::KSC_ASSIGN>), grid, dim3(256), 0, st, z5, n_points, (const u32x4*)scratch,
+                       per_cloud_operand ? (long)(1024 * 64 * 2 * A::P / 16) : 0L, bn, out, rn_out, mean_out ? stats : nullptr, HxBnb<T>{});
+    if (mean_out) epc_moments_finalize_launch(stats, (int)(grid.x * grid.y), 64, num_clouds * n_points, 128, nullptr, mean_out, var_out, stream, n_points);
+    HX_CHECK_LAUNCH("assign");
+    return EPC_OK;
+}
+
+template <typename A>
+static size_t hx_colgemm_scratch_bytes(int num_clouds, int n_points) {
+    if (num_clouds <= 0 || n_points <= 0) return 0;
+    return (size_t)num_clouds * h16_splits(num_clouds, n_points, A::COL_TILES) * 1024 * 64 * sizeof(float);
+}
+
+// out = relu(bn(z5))^T (rn C): per cloud (per_cloud = 1: out (num_clouds, 1024, 64), the VLAD aggregation with C = a) or over all rows
+// (per_cloud = 0: out (1024, 64), the cluster weights' gradient with C = dz).  C: (rows, 64) f32.
+template <typename A>
+static int hx_colgemm(const typename A::T* z5, const float* mean5, const float* var5, const float* gamma5, const float* beta5, float eps,
+                      const float* C, const float* rn, int num_clouds, int n_points, int per_cloud, float* out, void* scratch,
+                      size_t scratch_bytes, void* stream) {
+    HX_CHECK_ARG("colgemm", z5 && mean5 && var5 && gamma5 && beta5 && C && rn && out && scratch, "null pointer");
+    HX_CHECK_ARG("colgemm", num_clouds > 0 && n_points > 0 && n_points % 32 == 0 && (long)num_clouds * h16_splits(num_clouds, n_points, A::COL_TILES) <= 65535,
+                 "bad shape");
+    HX_CHECK_ARG("colgemm", scratch_bytes >= hx_colgemm_scratch_bytes<A>(num_clouds, n_points), "scratch too small (%s_colgemm_scratch_bytes)");
+    HX_CHECK_ARG("colgemm", epc_aligned16(z5) && epc_aligned16(scratch) && epc_aligned16(out), "tensors must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int S = h16_splits(num_clouds, n_points, A::COL_TILES);
+    const int rows_per_wg = (n_points + S - 1) / S;
+    const H16Bn bn{mean5, var5, gamma5, beta5, eps};
+    hipLaunchKernelGGL((hx_colgemm_kernel<typename A::T, A::P>), dim3(A::COL_TILES, num_clouds * S), dim3(256), 0, st, z5, bn, C, rn, rows_per_wg,
+                       n_points, S, (float*)scratch);
+    const long per = 1024 * 64;
+    if (per_cloud)
+        hipLaunchKernelGGL(h16_partial_reduce_kernel, dim3((unsigned)(per / 4 / 256), num_clouds), dim3(256), 0, st, (const float*)scratch, S, per, out);
+    else
+        hipLaunchKernelGGL(h16_partial_reduce_kernel, dim3((unsigned)(per / 4 / 256), 1), dim3(256), 0, st, (const float*)scratch, num_clouds * S, per, out);
+    HX_CHECK_LAUNCH("colgemm");
+    return EPC_OK;
+}
+
+template <typename A>
+static size_t hx_dx_scratch_bytes() { return (size_t)1024 * 256 * 2 * A::P; }
+
+// dcat (rows, 256) f32 = dz5 (rows, 1024) times W5^T (W5: (256, 1024) f32, rounded / split to bf16 pieces here)
+template <typename A>
+static int hx_conv5_dx(const typename A::T* dz5, const float* W5, int rows, float* dcat, void* scratch, size_t scratch_bytes, void* stream) {
+    typedef typename A::T T;
+    HX_CHECK_ARG("conv5_dx", dz5 && W5 && dcat && scratch, "null pointer");
+    HX_CHECK_ARG("conv5_dx", rows > 0 && rows % 32 == 0, "rows must be a positive multiple of 32");
+    HX_CHECK_ARG("conv5_dx", scratch_bytes >= hx_dx_scratch_bytes<A>(), "scratch too small (%s_dx_scratch_bytes)");
+    HX_CHECK_ARG("conv5_dx", epc_aligned16(dz5) && epc_aligned16(scratch) && epc_aligned16(dcat), "tensors must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    h16_pack<A::P>(W5, 1, 1024, 0, 1, 1024, 256, 1, A::KSC_DX, scratch, st);      // B[k = output channel][n = input channel] = W5[n][k]
+    const H16Bn none{nullptr, nullptr, nullptr, nullptr, 0.f};
+    hipLaunchKernelGGL((hx_rowgemm_kernel<8, false, T, A::P, A::KSC_DX>), dim3((rows + 127) / 128, 1), dim3(256), 0, st, dz5, rows,
+                       (const u32x4*)scratch, 0L, none, dcat, (float*)nullptr, (float*)nullptr, HxBnb<T>{});
+    HX_CHECK_LAUNCH("conv5_dx");
+    return EPC_OK;
+}
+
+// The last step of conv5's BatchNorm backward and hx_conv5_dx in ONE pass: dz5 = gamma rstd (du - dbeta / rows - zhat dgamma / rows) is
+// formed from du and z5 as they stream, written once (dz5 may be du) for dW5's product, and multiplied with W5^T from registers.
+template <typename A>
+static int hx_conv5_dx_bn(const typename A::T* du, const typename A::T* z5, const float* mean5, const float* var5, const float* gamma5, float eps,
+                          const float* dbeta, const float* dgamma, const float* W5, int rows, typename A::T* dz5, float* dcat, void* scratch,
+                          size_t scratch_bytes, void* stream) {
+    typedef typename A::T T;
+    HX_CHECK_ARG("conv5_dx_bn", du && z5 && mean5 && var5 && gamma5 && dbeta && dgamma && W5 && dz5 && dcat && scratch, "null pointer");
+    HX_CHECK_ARG("conv5_dx_bn", rows > 0 && rows % 32 == 0, "rows must be a positive multiple of 32");
+    HX_CHECK_ARG("conv5_dx_bn", scratch_bytes >= hx_dx_scratch_bytes<A>(), "scratch too small (%s_dx_scratch_bytes)");
+    HX_CHECK_ARG("conv5_dx_bn", epc_aligned16(du) && epc_aligned16(z5) && epc_aligned16(dz5) && epc_aligned16(scratch) && epc_aligned16(dcat),
+                 "tensors must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    h16_pack<A::P>(W5, 1, 1024, 0, 1, 1024, 256, 1, A::KSC_DX, scratch, st);      // B[k = output channel][n = input channel] = W5[n][k]
+    const H16Bn bn{mean5, var5, gamma5, nullptr, eps};
+    const HxBnb<T> bnb{z5, dbeta, dgamma, 1.0f / rows, dz5};
+    // 96- or 128-row workgroups, whichever leaves fewer rows on the busiest slot (two workgroups per CU: 235-248 registers a lane)
+    if (rows_tile_waves(rows, 2 * epc_device_cu_count()) == 3)
+        hipLaunchKernelGGL((hx_rowgemm_kernel<8, false, T, A::P, A::KSC_DX, true, 3>), dim3((rows + 95) / 96, 1), dim3(192), 0, st, du, rows,
+                           (const u32x4*)scratch, 0L, bn, dcat, (float*)nullptr, (float*)nullptr, bnb);
+    else
+        hipLaunchKernelGGL((hx_rowgemm_kernel<8, false, T, A::P, A::KSC_DX, true, 4>), dim3((rows + 127) / 128, 1), dim3(256), 0, st, du, rows,
+                           (const u32x4*)scratch, 0L, bn, dcat, (float*)nullptr, (float*)nullptr, bnb);
+    HX_CHECK_LAUNCH("conv5_dx_bn");
+    return EPC_OK;
+}

@@ -25,18 +25,6 @@ template <int P>
 struct HpFrag {
     bf16x8 p[P];
 };
-template <int P>
-__device__ __forceinline__ void hp_split(const float (&v)[8], HpFrag<P>& f) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float r = v[j];
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-            f.p[q][j] = (__bf16)r;
-            r -= (float)f.p[q][j];
-        }
-    }
-}
 // (the products: piece x of a with piece s - x of b for s = P - 1 .. 0, smallest terms first -- 1, 3 or 6 MFMAs, interleaved over two
 // accumulators in the kernels)
 
@@ -90,8 +78,8 @@ __global__ __launch_bounds__(256, 1) void hp_fwd_kernel(const float* __restrict_
             float v0[8], v1[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v0[j] = w2[ks][j].x, v1[j] = w2[ks][j].y;
-            hp_split<P>(v0, b[0]);
-            hp_split<P>(v1, b[1]);
+            bf16_split<P>(v0, b[0].p);
+            bf16_split<P>(v1, b[1].p);
         }
 #pragma unroll
         for (int mt = 0; mt < HP_MT; ++mt) {
@@ -99,7 +87,7 @@ __global__ __launch_bounds__(256, 1) void hp_fwd_kernel(const float* __restrict_
                 float v[8];
                 hp_ld8(hp_lds + (32 * mt + i) * HP_PITCH + 64 * wave + 16 * ks + 8 * h, v);
                 HpFrag<P> a;
-                hp_split<P>(v, a);
+                bf16_split<P>(v, a.p);
 #pragma unroll
                 for (int s = P - 1; s >= 0; --s)
 #pragma unroll
@@ -192,14 +180,14 @@ __global__ __launch_bounds__(256, 1) void hp_dx_kernel(const float* __restrict__
         HpFrag<P> b;
         {
             const float v[8] = {wr[ks][0].x, wr[ks][0].y, wr[ks][0].z, wr[ks][0].w, wr[ks][1].x, wr[ks][1].y, wr[ks][1].z, wr[ks][1].w};
-            hp_split<P>(v, b);
+            bf16_split<P>(v, b.p);
         }
         HpFrag<P> a[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             float v[8];
             hp_ld8(hp_lds + (32 * min(mt0 + q, MT - 1) + i) * HP_PITCH + 16 * ks + 8 * h, v);
-            hp_split<P>(v, a[q]);
+            bf16_split<P>(v, a[q].p);
         }
 #pragma unroll
         for (int s = P - 1; s >= 0; --s)
@@ -259,7 +247,7 @@ __global__ __launch_bounds__(256, 1) void hp_dw_kernel(const float* __restrict__
     for (int ks = 0; ks < 8; ++ks) {
         if (ks < KS) {
             HpFrag<P> a;
-            hp_split<P>(xr[ks], a);
+            bf16_split<P>(xr[ks], a.p);
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) {
                 float v0[8], v1[8];
@@ -269,8 +257,8 @@ __global__ __launch_bounds__(256, 1) void hp_dw_kernel(const float* __restrict__
                     v0[j] = d.x, v1[j] = d.y;
                 }
                 HpFrag<P> b0, b1;
-                hp_split<P>(v0, b0);
-                hp_split<P>(v1, b1);
+                bf16_split<P>(v0, b0.p);
+                bf16_split<P>(v1, b1.p);
 #pragma unroll
                 for (int s = P - 1; s >= 0; --s)
 #pragma unroll
@@ -297,26 +285,16 @@ extern "C" size_t epc_hidden_proj_scratch_bytes(int M, int K) {
     return M > 0 && K > 0 ? (size_t)(K / 256) * M * 256 * sizeof(float) : 0;
 }
 
-template <typename Kern>
-static int hp_set_lds(Kern kern, size_t lds, const char* who) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-        epc_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-        return EPC_EHIP;
-    }
-    return EPC_OK;
-}
 #define HP_LAUNCH(kern, grid, lds, ...)                                                                   \
     do {                                                                                                  \
-        int rc_ = EPC_OK;                                                                                 \
         if (pieces == 1) {                                                                                \
-            if ((rc_ = hp_set_lds(kern<1>, lds, __func__)) != EPC_OK) return rc_;                         \
+            EPC_SET_DYN_LDS(kern<1>, lds);                                                                \
             hipLaunchKernelGGL(kern<1>, grid, dim3(256), lds, st, __VA_ARGS__);                           \
         } else if (pieces == 2) {                                                                         \
-            if ((rc_ = hp_set_lds(kern<2>, lds, __func__)) != EPC_OK) return rc_;                         \
+            EPC_SET_DYN_LDS(kern<2>, lds);                                                                \
             hipLaunchKernelGGL(kern<2>, grid, dim3(256), lds, st, __VA_ARGS__);                           \
         } else {                                                                                          \
-            if ((rc_ = hp_set_lds(kern<3>, lds, __func__)) != EPC_OK) return rc_;                         \
+            EPC_SET_DYN_LDS(kern<3>, lds);                                                                \
             hipLaunchKernelGGL(kern<3>, grid, dim3(256), lds, st, __VA_ARGS__);                           \
         }                                                                                                 \
     } while (0)
@@ -328,7 +306,7 @@ extern "C" int epc_hidden_proj_fwd(const float* X, const float* W, int M, int K,
     EPC_CHECK_ARG(epc_hidden_proj_ok(M, K, 256), "shape not covered (epc_hidden_proj_ok)");
     EPC_CHECK_ARG(pieces >= 1 && pieces <= 3, "pieces must be 1, 2 or 3");
     EPC_CHECK_ARG(scratch_bytes >= epc_hidden_proj_scratch_bytes(M, K), "scratch too small (epc_hidden_proj_scratch_bytes)");
-    EPC_CHECK_ARG(h16_aligned16(X) && h16_aligned16(W) && h16_aligned16(Y) && h16_aligned16(scratch), "tensors must be 16-byte aligned");
+    EPC_CHECK_ARG(epc_aligned16(X) && epc_aligned16(W) && epc_aligned16(Y) && epc_aligned16(scratch), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int MT = (M + 31) / 32, S = K / 256;
     const size_t stage = (size_t)32 * MT * HP_PITCH * sizeof(float), meet = (size_t)4 * HP_MT * 16 * 2 * 64 * sizeof(float);
@@ -346,7 +324,7 @@ extern "C" int epc_hidden_proj_bwd(const float* X, const float* W, const float* 
     EPC_CHECK_ARG(X && W && dY, "null pointer");
     EPC_CHECK_ARG(epc_hidden_proj_ok(M, K, 256), "shape not covered (epc_hidden_proj_ok)");
     EPC_CHECK_ARG(pieces >= 1 && pieces <= 3, "pieces must be 1, 2 or 3");
-    EPC_CHECK_ARG(h16_aligned16(X) && h16_aligned16(W) && h16_aligned16(dY) && h16_aligned16(dX) && h16_aligned16(dW), "tensors must be 16-byte aligned");
+    EPC_CHECK_ARG(epc_aligned16(X) && epc_aligned16(W) && epc_aligned16(dY) && epc_aligned16(dX) && epc_aligned16(dW), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int MT = (M + 31) / 32;
     if (dX) {

@@ -13,7 +13,7 @@
 //
 // Arithmetic is plain f32 throughout (the reference trains in fp32).
 #include <type_traits>
-#include "common.h"
+#include "train_common.h"
 
 // ----------------------------------------------------------------------------------------------------------------
 // GEMM: 64x64 output tile per 256-thread workgroup (4 waves x one 32x32 MFMA tile), K in steps of 32 through LDS.
@@ -187,16 +187,6 @@ __global__ __launch_bounds__(256) void gemm_small_m_kernel(GemmArgs g) {
 // ----------------------------------------------------------------------------------------------------------------
 #define S_BK 32
 
-__device__ __forceinline__ void split8x3(const float (&v)[8], bf16x8& p0, bf16x8& p1, bf16x8& p2) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        p0[j] = (__bf16)v[j];
-        const float r1 = v[j] - (float)p0[j];
-        p1[j] = (__bf16)r1;
-        p2[j] = (__bf16)(r1 - (float)p1[j]);
-    }
-}
-
 // Staging is split in two so that the global loads of k-tile t+1 are in flight while the MFMAs of tile t run:
 // fetch_fragments() only loads (8 floats per lane-fragment, kept in registers), store_fragments() splits them into
 // bf16 pieces and writes the ready MFMA fragments.  PIECES = 3: f32-accurate (six products), 2: backward GEMMs (three
@@ -318,7 +308,7 @@ __device__ __forceinline__ void store_fragments(const float (&v)[(BLOCKS * 128) 
             dst[row >> 5][kg >> 1][0][l2] = __builtin_bit_cast(u32x4, p0);
         } else {
             bf16x8 p0, p1, p2;
-            split8x3(v[u], p0, p1, p2);
+            bf16_split(v[u], p0, p1, p2);
             dst[row >> 5][kg >> 1][0][l2] = __builtin_bit_cast(u32x4, p0);
             dst[row >> 5][kg >> 1][1][l2] = __builtin_bit_cast(u32x4, p1);
             if constexpr (PIECES == 3) dst[row >> 5][kg >> 1][2][l2] = __builtin_bit_cast(u32x4, p2);
@@ -831,17 +821,6 @@ int epc_moments_finalize_launch(const float* stats, int tiles, int N, int rows, 
 
 extern "C" int epc_gemm_stats_tiles(int M) { return M >= 128 ? (M + 127) / 128 : (M + 63) / 64; }
 
-struct BnAffine {  // y = z * s + t, the expression the forward and the backward mask must share bit for bit
-    float s, t;
-};
-__device__ __forceinline__ BnAffine bn_affine(float mean, float var, float gamma, float beta, float eps) {
-    BnAffine a;
-    a.s = (1.0f / sqrtf(var + eps)) * gamma;
-    a.t = beta - mean * a.s;
-    return a;
-}
-__device__ __forceinline__ float bn_value(float z, const BnAffine& a) { return z * a.s + a.t; }
-
 struct BnParams {   // a training-mode BatchNorm (+ReLU) applied to an operand AS IT IS LOADED: null mean = none
     const float *mean, *var, *gamma, *beta;
     float eps;
@@ -970,7 +949,7 @@ __global__ __launch_bounds__(256) void linear_stats64_kernel(const float* __rest
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] = src[(size_t)q * 64];
         bf16x8 p0, p1, p2;
-        split8x3(v, p0, p1, p2);
+        bf16_split(v, p0, p1, p2);
         Wf[nt][s4][0][l] = __builtin_bit_cast(u32x4, p0);
         Wf[nt][s4][1][l] = __builtin_bit_cast(u32x4, p1);
         Wf[nt][s4][2][l] = __builtin_bit_cast(u32x4, p2);
@@ -1014,7 +993,7 @@ __global__ __launch_bounds__(256) void linear_stats64_kernel(const float* __rest
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = 0.f;
             }
-            split8x3(v, a0[s4], a1[s4], a2[s4]);
+            bf16_split(v, a0[s4], a1[s4], a2[s4]);
         }
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
@@ -1025,7 +1004,7 @@ __global__ __launch_bounds__(256) void linear_stats64_kernel(const float* __rest
             for (int s4 = 0; s4 < 4; ++s4) {
                 const bf16x8 w0 = __builtin_bit_cast(bf16x8, Wf[nt][s4][0][lane]), w1 = __builtin_bit_cast(bf16x8, Wf[nt][s4][1][lane]),
                              w2 = __builtin_bit_cast(bf16x8, Wf[nt][s4][2][lane]);
-                acc = mfma_bf16(a2[s4], w0, acc);   // smallest terms first (gemm_split_kernel's order)
+                acc = mfma_bf16(a2[s4], w0, acc);   // smallest terms first (bf16_prod's order)
                 acc = mfma_bf16(a0[s4], w2, acc);
                 acc = mfma_bf16(a1[s4], w1, acc);
                 acc = mfma_bf16(a1[s4], w0, acc);
@@ -1794,23 +1773,6 @@ extern "C" int epc_bn_apply_bwd_given(const float* dy, const float* z, const flo
 // (128-B rows, 16-B chunks XOR-swizzled) and come back transposed by ds_read_b64_tr_b16: lane 4q + p of a 16-lane group
 // addresses row r0 + q, channels c0 + 4p .. + 3; lane i receives channel c0 + i of the four rows.  One image (8 KB: hi + lo)
 // per wave serves x, then dz.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-#define LB_IMG_BYTES 4096   // one piece: 32 rows x 128 B
-__device__ __forceinline__ int lb_img_off(int row, int chunk) {   // byte offset of 16-byte chunk `chunk` (0..7) of row `row`
-    return 128 * row + 16 * (chunk ^ (((row >> 1) & 1) << 2) ^ (((row >> 2) & 1) << 1));
-}
-// the A / B fragment (k = rows 16 s2 + 8 h .. + 7, m or n = channel 32 t + (lane & 31)) of one piece, read transposed
-__device__ __forceinline__ bf16x8 lb_tr_frag(const char* img, int t, int s2, int lane) {
-    const int g16 = lane >> 4, l16 = lane & 15, q = l16 >> 2, pp = l16 & 3;
-    const int chunk = 4 * t + 2 * (g16 & 1) + (pp >> 1);
-    const int r0 = 16 * s2 + 8 * (g16 >> 1);
-    typedef __attribute__((address_space(3))) s16x4* lds_ptr;
-    const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + lb_img_off(r0 + q, chunk) + 8 * (pp & 1)));
-    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + lb_img_off(r0 + 4 + q, chunk) + 8 * (pp & 1)));
-    const s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 __global__ __launch_bounds__(256, 2) void linear_bn_bwd64_kernel(
     const float* __restrict__ dy, const float* __restrict__ z, const float* __restrict__ x, const float* __restrict__ W,
@@ -1824,7 +1786,7 @@ __global__ __launch_bounds__(256, 2) void linear_bn_bwd64_kernel(
     __shared__ __attribute__((aligned(16))) float coef[6][64];          // s, t (mask), mean, k1, dbeta/rows, rstd dgamma/rows
     __shared__ __attribute__((aligned(16))) float xcoef[2][64];
     __shared__ u32x4 Wf[2][4][2][64];                                    // W as A fragments: [in tile][k-step][hi, lo][lane]
-    __shared__ __attribute__((aligned(16))) char img[4][2 * LB_IMG_BYTES];   // per wave: hi + lo image; at the end the parked dW partials
+    __shared__ __attribute__((aligned(16))) char img[4][2 * BF16_IMG_BYTES];   // per wave: hi + lo image; at the end the parked dW partials
     static_assert(sizeof(img) >= 2 * 4 * 16 * 64 * sizeof(float), "the parked partials alias the images");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 31, h = lane >> 5;
@@ -1869,9 +1831,9 @@ __global__ __launch_bounds__(256, 2) void linear_bn_bwd64_kernel(
         v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
     };
     auto put = [&](int s4, bf16x8 ph, bf16x8 pl) {   // the lane's row i, channels 16 s4 + 8 h .. + 7 = chunk 2 s4 + h
-        const int o = lb_img_off(i, 2 * s4 + h);
+        const int o = bf16_img_off(i, 2 * s4 + h);
         *reinterpret_cast<u32x4*>(my + o) = __builtin_bit_cast(u32x4, ph);
-        *reinterpret_cast<u32x4*>(my + LB_IMG_BYTES + o) = __builtin_bit_cast(u32x4, pl);
+        *reinterpret_cast<u32x4*>(my + BF16_IMG_BYTES + o) = __builtin_bit_cast(u32x4, pl);
     };
 
 #pragma unroll 1
@@ -1940,7 +1902,7 @@ __global__ __launch_bounds__(256, 2) void linear_bn_bwd64_kernel(
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) dh[nt][s2] = lb_tr_frag(my, nt, s2, lane), dl[nt][s2] = lb_tr_frag(my + LB_IMG_BYTES, nt, s2, lane);
+            for (int s2 = 0; s2 < 2; ++s2) dh[nt][s2] = bf16_tr_frag(my, nt, s2, lane), dl[nt][s2] = bf16_tr_frag(my + BF16_IMG_BYTES, nt, s2, lane);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // they are in registers: the image may be overwritten
         // ---- x (row layout) -> bf16 pieces -> image -> A fragments of dW (k = rows, m = in channel) ----
 #pragma unroll
@@ -1963,7 +1925,7 @@ __global__ __launch_bounds__(256, 2) void linear_bn_bwd64_kernel(
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 xh = lb_tr_frag(my, mt, s2, lane), xl = lb_tr_frag(my + LB_IMG_BYTES, mt, s2, lane);
+                const bf16x8 xh = bf16_tr_frag(my, mt, s2, lane), xl = bf16_tr_frag(my + BF16_IMG_BYTES, mt, s2, lane);
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     accW[mt][nt] = mfma_bf16(xl, dh[nt][s2], accW[mt][nt]);

@@ -1259,6 +1259,12 @@ def _scratch_bytes(nbytes, device):
     return buf, buf.numel() * 4
 
 
+def _head_entry(lib, h16):
+    """name -> the streamed head's entry point of that name in the mode's arithmetic (epc_h16_* on bf16 tensors, epc_h32_* on f32)."""
+    prefix = "epc_h16_" if h16 else "epc_h32_"
+    return lambda name: getattr(lib, prefix + name)
+
+
 class Conv5VladHead(torch.autograd.Function):
     """(vlad (B, 1024, 64), a_sum (B, 1, 64), mean5, var5, mean_c, var_c, z5, rn) from the backbone's output cat (rows, 256):
         z5 = cat W5 + b5;  u = relu(batch_norm_train(z5));  f = u rn (tf.nn.l2_normalize over the channels);
@@ -1278,6 +1284,7 @@ class Conv5VladHead(torch.autograd.Function):
         B = rows // N
         dev = cat.device
         h16 = mode == "bf16"
+        hx = _head_entry(lib, h16)
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         z5 = torch.empty((rows, 1024), dtype=torch.bfloat16 if h16 else torch.float32, device=dev)
         mean5, var5 = f32(1024), f32(1024)
@@ -1294,18 +1301,16 @@ class Conv5VladHead(torch.autograd.Function):
             L.check(lib.epc_h32_conv5_fwd(cat.data_ptr(), W5.data_ptr(), b5.data_ptr(), rows, z5.data_ptr(), mean5.data_ptr(),
                                           var5.data_ptr(), sc.data_ptr(), n, _st()))
         za, rn, mean_c, var_c = f32(rows, 64), f32(rows), f32(64), f32(64)
-        assign = lib.epc_h16_assign if h16 else lib.epc_h32_assign
-        sc, n = _scratch_bytes((lib.epc_h16_assign_scratch_bytes if h16 else lib.epc_h32_assign_scratch_bytes)(B, N, 0), dev)
-        L.check(assign(z5.data_ptr(), *bn5(), Wc.data_ptr(), 0, B, N, za.data_ptr(), rn.data_ptr(), mean_c.data_ptr(), var_c.data_ptr(),
-                       sc.data_ptr(), n, _st()))
+        sc, n = _scratch_bytes(hx("assign_scratch_bytes")(B, N, 0), dev)
+        L.check(hx("assign")(z5.data_ptr(), *bn5(), Wc.data_ptr(), 0, B, N, za.data_ptr(), rn.data_ptr(), mean_c.data_ptr(), var_c.data_ptr(),
+                             sc.data_ptr(), n, _st()))
         a, a_sum = f32(rows, 64), f32(B, 1, 64)
         parts = _splitk_ws(lib.epc_cloud_colsum64_partial_floats(B), dev)
         L.check(lib.epc_assign_softmax_fwd(za.data_ptr(), mean_c.data_ptr(), var_c.data_ptr(), gc.data_ptr(), btc.data_ptr(),
                                            float(epsc), B, N, a.data_ptr(), a_sum.data_ptr(), parts.data_ptr(), parts.numel(), _st()))
         vlad = f32(B, 1024, 64)
-        sc, n = _scratch_bytes((lib.epc_h16_colgemm_scratch_bytes if h16 else lib.epc_h32_colgemm_scratch_bytes)(B, N), dev)
-        L.check((lib.epc_h16_colgemm if h16 else lib.epc_h32_colgemm)(z5.data_ptr(), *bn5(), a.data_ptr(), rn.data_ptr(), B, N, 1,
-                                                                     vlad.data_ptr(), sc.data_ptr(), n, _st()))
+        sc, n = _scratch_bytes(hx("colgemm_scratch_bytes")(B, N), dev)
+        L.check(hx("colgemm")(z5.data_ptr(), *bn5(), a.data_ptr(), rn.data_ptr(), B, N, 1, vlad.data_ptr(), sc.data_ptr(), n, _st()))
         ctx.save_for_backward(lhs, W5, z5, mean5, var5, g5, bt5, rn, Wc, za, mean_c, var_c, gc, btc, a)
         ctx.eps5, ctx.epsc, ctx.n_points, ctx.h16 = float(eps5), float(epsc), N, h16
         ctx.mark_non_differentiable(mean5, var5, mean_c, var_c, z5, rn)
@@ -1318,6 +1323,7 @@ class Conv5VladHead(torch.autograd.Function):
         cat, W5, z5, mean5, var5, g5, bt5, rn, Wc, za, mean_c, var_c, gc, btc, a = ctx.saved_tensors
         rows = int(cat.shape[0])
         N, h16 = ctx.n_points, ctx.h16
+        hx = _head_entry(lib, h16)
         B = rows // N
         dev = cat.device
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -1327,18 +1333,16 @@ class Conv5VladHead(torch.autograd.Function):
         bn5 = (mean5.data_ptr(), var5.data_ptr(), g5.data_ptr(), bt5.data_ptr(), ctx.eps5)
         # da = f dvlad[cloud] (the a_sum gradient of every point's cloud is added inside the softmax backward)
         da = f32(rows, 64)
-        sc, n = _scratch_bytes((lib.epc_h16_assign_scratch_bytes if h16 else lib.epc_h32_assign_scratch_bytes)(B, N, 1), dev)
-        L.check((lib.epc_h16_assign if h16 else lib.epc_h32_assign)(z5.data_ptr(), *bn5, dvlad.data_ptr(), 1, B, N, da.data_ptr(), None,
-                                                                   None, None, sc.data_ptr(), n, _st()))
+        sc, n = _scratch_bytes(hx("assign_scratch_bytes")(B, N, 1), dev)
+        L.check(hx("assign")(z5.data_ptr(), *bn5, dvlad.data_ptr(), 1, B, N, da.data_ptr(), None, None, None, sc.data_ptr(), n, _st()))
         dz, dgc, dbtc, trow = f32(rows, 64), f32(64), f32(64), f32(rows)
         ws, wn = _ws(rows, 64, dev)
         L.check(lib.epc_assign_softmax_bwd(da.data_ptr(), dasum.contiguous().data_ptr() if dasum is not None else None, a.data_ptr(),
                                            za.data_ptr(), mean_c.data_ptr(), var_c.data_ptr(), gc.data_ptr(), btc.data_ptr(), ctx.epsc,
                                            B, N, dz.data_ptr(), dgc.data_ptr(), dbtc.data_ptr(), trow.data_ptr(), ws.data_ptr(), wn, _st()))
         dWc = f32(1024, 64)
-        sc, n = _scratch_bytes((lib.epc_h16_colgemm_scratch_bytes if h16 else lib.epc_h32_colgemm_scratch_bytes)(B, N), dev)
-        L.check((lib.epc_h16_colgemm if h16 else lib.epc_h32_colgemm)(z5.data_ptr(), *bn5, dz.data_ptr(), rn.data_ptr(), B, N, 0,
-                                                                     dWc.data_ptr(), sc.data_ptr(), n, _st()))
+        sc, n = _scratch_bytes(hx("colgemm_scratch_bytes")(B, N), dev)
+        L.check(hx("colgemm")(z5.data_ptr(), *bn5, dz.data_ptr(), rn.data_ptr(), B, N, 0, dWc.data_ptr(), sc.data_ptr(), n, _st()))
         # du = [f > 0] rn ([a | dz] [dvlad^T ; Wc^T] - f trow), the BatchNorm's column sums, then dz5 in place
         need_dx = bool(ctx.needs_input_grad[0])
         du = torch.empty_like(z5)
@@ -1366,8 +1370,8 @@ class Conv5VladHead(torch.autograd.Function):
             # dz5 = gamma rstd (du - dbeta / R - zhat dgamma / R) is formed INSIDE dcat's product as du and z5 stream, and written over du for
             # dW5's: one pass over the (rows, 1024) tensors instead of the apply pass + the product's own read
             dcat = f32(rows, 256)
-            sc, n = _scratch_bytes((lib.epc_h16_dx_scratch_bytes if h16 else lib.epc_h32_dx_scratch_bytes)(), dev)
-            L.check((lib.epc_h16_conv5_dx_bn if h16 else lib.epc_h32_conv5_dx_bn)(
+            sc, n = _scratch_bytes(hx("dx_scratch_bytes")(), dev)
+            L.check(hx("conv5_dx_bn")(
                 du.data_ptr(), z5.data_ptr(), mean5.data_ptr(), var5.data_ptr(), g5.data_ptr(), ctx.eps5, sums[0].data_ptr(), sums[1].data_ptr(),
                 W5.data_ptr(), rows, du.data_ptr(), dcat.data_ptr(), sc.data_ptr(), n, _st()))
         # dW5 = cat^T dz5, row slices added in a fixed order
