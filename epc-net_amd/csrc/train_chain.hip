@@ -23,6 +23,9 @@
 // (f32-accurate), backward three products on two pieces; template parameter 1 = one bf16 value per operand (BASELINE.json
 // configs[2]'s "bf16").  Layouts (rows x 64 f32, dense unless a stride is given) and the MFMA tile algebra are those of
 // linear_stats64_kernel / linear_bn_bwd64_kernel (train_ops.hip), which these kernels replace inside the step.
+// The stages of the two forward kernels -- weight staging, the neighbour gather, tile -> A fragments, the tile product with its
+// pivot-shifted moments, the waves' merge -- are defined ONCE, in train_chain_common.h (the gather in train_common.h), and are what
+// the persistent forward (train_chain_persist.hip) is built from as well.
 #include "train_chain_common.h"
 
 
@@ -69,19 +72,7 @@ __global__ __launch_bounds__(64 * CH_FWD_MAX_WAVES) void chain_fwd_linear_kernel
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) ch_ld8(g.zin + (size_t)row * 64 + 16 * s4 + 8 * h, zr[s4]);
     }
-    if (g.W) {   // B[k = in][n = out]: lane (n = 32 nt + i, k group h) of k-step s holds W[16 s + 8 h .. + 7][n]
-        for (int f = tid; f < 2 * 4 * 64; f += blockDim.x) {
-            const int l = f & 63, s4 = (f >> 6) & 3, nt = f >> 8;
-            const float* src = g.W + (size_t)(16 * s4 + 8 * (l >> 5)) * 64 + 32 * nt + (l & 31);
-            float v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = src[(size_t)q * 64];
-            bf16x8 p[PF];
-            bf16_split<PF>(v, p);
-#pragma unroll
-            for (int pc = 0; pc < PF; ++pc) Wf[nt][s4][pc][l] = __builtin_bit_cast(u32x4, p[pc]);
-        }
-    }
+    if (g.W) ch_stage_fwd_weights<PF>(g.W, Wf, tid);
     ch_bn_finish(g.bn, bnr, rows, g.eps, scratch, s_mean, s_var, coef);   // (its barriers also cover Wf)
 
     float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f}, piv[2] = {0.f, 0.f};
@@ -125,32 +116,9 @@ __global__ __launch_bounds__(64 * CH_FWD_MAX_WAVES) void chain_fwd_linear_kernel
             bf16_split<PF>(v, a[s4]);
         }
         if (!g.W) continue;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                bf16x8 w[PF];
-#pragma unroll
-                for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                acc = bf16_prod<PF>(a[s4], w, acc);
-            }
-            const float bv = nt ? b1 : b0;
-            if (tl == wave) piv[nt] = __shfl(acc[0], i);   // row `base` of the wave's first tile
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rr = base + mfma_row(r, h);
-                if (rr < rows) {
-                    const float v = acc[r];   // (statistics of the product WITHOUT the bias: the pooling adds it to the mean)
-                    const float d = v - piv[nt];
-                    s1[nt] += d;
-                    s2[nt] += d * d;
-                    g.z_out[(size_t)rr * 64 + 32 * nt + i] = v + bv;
-                }
-            }
-        }
+        // (the pivot: row `base` of the wave's first tile)
+        ch_tile_product<PF, false>(a, Wf, lane, base, rows, tl == wave, s1, s2, piv,
+                                   [&](int nt, int, int rr, float v) { g.z_out[(size_t)rr * 64 + 32 * nt + i] = v + (nt ? b1 : b0); });
         my_rows += min(32, rows - base);
     }
     if (!g.W) return;
@@ -160,9 +128,8 @@ __global__ __launch_bounds__(64 * CH_FWD_MAX_WAVES) void chain_fwd_linear_kernel
 // ----------------------------------------------------------------------------------------------------------------
 // FORWARD, gather layer (models/epc-net.py:70-76):  x = relu(bn0(z0)) formed as the rows are GATHERED (x is never written);
 //   xm = (sum over the point's selected neighbours of x) / k;  d = xm - x;  za = d Wa + ba  (+ moment partials of za).
-// 16 lanes x float4 per row, four points per wave-instruction, the first 20 rows of a list in flight at once, summed in list order
-// (neighbour_mean_kernel's order); rows with more than `cap` selected entries (exact ties: duplicated / zero-padded clouds) take
-// the exact scan.  d goes through a per-wave LDS tile into the MFMA's row layout.
+// 16 lanes x float4 per row, four points per wave-instruction; the walk over a point's list and its order are neighbour_mean_of's
+// (train_common.h), the one neighbour_mean_kernel runs on a written x.  d goes through a per-wave LDS tile into the MFMA's row layout.
 // ----------------------------------------------------------------------------------------------------------------
 struct ChFwdGatherArgs {
     const float* z0;
@@ -192,30 +159,17 @@ __global__ __launch_bounds__(64 * CH_GATHER_MAX_WAVES) void chain_fwd_gather_ker
     __shared__ __attribute__((aligned(16))) float sred[CH_GATHER_MAX_WAVES][3][64];
     __shared__ int snrows[CH_GATHER_MAX_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
-    const int i = lane & 31, h = lane >> 5;
+    const int i = lane & 31;
     const int p4 = lane >> 4, q = lane & 15;
     const int rows = g.rows;
     const int lb = xcd_contiguous_block(blockIdx.x, gridDim.x);   // a cloud's tiles behind ONE L2 (speed only)
     const int wg0 = lb * g.wg_rows, tiles = min(g.wg_rows, rows - wg0 + 31) / 32;
     const ChBnRegs bnr = ch_bn_begin(g.bn, rows, scratch);
-    for (int f = tid; f < 2 * 4 * 64; f += blockDim.x) {
-        const int l = f & 63, s4 = (f >> 6) & 3, nt = f >> 8;
-        const float* src = g.W + (size_t)(16 * s4 + 8 * (l >> 5)) * 64 + 32 * nt + (l & 31);
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = src[(size_t)u * 64];
-        bf16x8 p[PF];
-        bf16_split<PF>(v, p);
-#pragma unroll
-        for (int pc = 0; pc < PF; ++pc) Wf[nt][s4][pc][l] = __builtin_bit_cast(u32x4, p[pc]);
-    }
+    ch_stage_fwd_weights<PF>(g.W, Wf, tid);
     // (pooling writes mean / var from workgroup 0 of the DISPATCH order: any one workgroup will do)
     ch_bn_finish(g.bn, bnr, rows, g.eps, scratch, s_mean, s_var, coef);
     const float4 cs = *reinterpret_cast<const float4*>(&coef[0][4 * q]), ct = *reinterpret_cast<const float4*>(&coef[1][4 * q]);
-    auto act = [&](const float4& v) {   // relu(bn0(.)) of the lane's four channels: the forward's own expression
-        return make_float4(fmaxf(v.x * cs.x + ct.x, 0.f), fmaxf(v.y * cs.y + ct.y, 0.f), fmaxf(v.z * cs.z + ct.z, 0.f),
-                           fmaxf(v.w * cs.w + ct.w, 0.f));
-    };
+    auto act = [&](const float4& v) { return act4(v, cs, ct); };   // relu(bn0(.)) of the lane's four channels
     __syncthreads();   // every wave has its coefficients: the pooling slices may be overwritten by the staging tiles
     float* stg = reinterpret_cast<float*>(scratch) + wave * CH_STG_FLOATS;
     const float4* z4 = reinterpret_cast<const float4*>(g.z0);
@@ -231,84 +185,18 @@ __global__ __launch_bounds__(64 * CH_GATHER_MAX_WAVES) void chain_fwd_gather_ker
             const int pt = base + 4 * r8 + p4;
             float4 dd = make_float4(0.f, 0.f, 0.f, 0.f);
             if (pt < rows) {
-                const int cloud_base = (pt / g.n) * g.n;
-                const int c = g.cnt[pt];
-                float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                auto add = [&](const float4& v) {
-                    const float4 y = act(v);
-                    acc.x += y.x, acc.y += y.y, acc.z += y.z, acc.w += y.w;
-                };
-                if (c <= g.cap) {
-                    int m = 0;
-                    if (c >= 20 && g.cap % 4 == 0) {
-                        const int4* il = reinterpret_cast<const int4*>(g.idx + (size_t)pt * g.cap);
-                        int nb[20];
-#pragma unroll
-                        for (int m4 = 0; m4 < 5; ++m4) {
-                            const int4 tq = il[m4];
-                            nb[4 * m4] = tq.x, nb[4 * m4 + 1] = tq.y, nb[4 * m4 + 2] = tq.z, nb[4 * m4 + 3] = tq.w;
-                        }
-                        float4 v[20];
-#pragma unroll
-                        for (int u = 0; u < 20; ++u) v[u] = z4[(size_t)(cloud_base + nb[u]) * 16 + q];
-#pragma unroll
-                        for (int u = 0; u < 20; ++u) add(v[u]);
-                        m = 20;
-                    }
-                    for (; m < c; ++m) add(z4[(size_t)(cloud_base + g.idx[(size_t)pt * g.cap + m]) * 16 + q]);
-                } else {
-                    const float* pc = g.xyz + (size_t)cloud_base * 3;
-                    const int ii = pt - cloud_base;
-                    const float xi = pc[3 * ii], yi = pc[3 * ii + 1], zi = pc[3 * ii + 2];
-                    const float sqi = sq3(xi, yi, zi), kv = g.kth[pt];
-                    for (int j = 0; j < g.n; ++j) {
-                        const float xj = pc[3 * j], yj = pc[3 * j + 1], zj = pc[3 * j + 2];
-                        if (neg_sq_dist(sqi, xi, yi, zi, xj, yj, zj, sq3(xj, yj, zj)) >= kv) add(z4[(size_t)(cloud_base + j) * 16 + q]);
-                    }
-                }
-                acc.x /= g.kdiv, acc.y /= g.kdiv, acc.z /= g.kdiv, acc.w /= g.kdiv;
+                const float4 xm = neighbour_mean_of<size_t>(z4, g.xyz, g.idx, g.cnt, g.kth, g.cap, g.n, g.kdiv, pt, q, act);
                 const float4 own = act(z4[(size_t)pt * 16 + q]);
-                dd = make_float4(acc.x - own.x, acc.y - own.y, acc.z - own.z, acc.w - own.w);
-                reinterpret_cast<float4*>(g.xm)[(size_t)pt * 16 + q] = acc;
+                dd = make_float4(xm.x - own.x, xm.y - own.y, xm.z - own.z, xm.w - own.w);
+                reinterpret_cast<float4*>(g.xm)[(size_t)pt * 16 + q] = xm;
                 reinterpret_cast<float4*>(g.d)[(size_t)pt * 16 + q] = dd;
             }
             *reinterpret_cast<float4*>(stg + (4 * r8 + p4) * CH_STG_STRIDE + 4 * q) = dd;   // (rows past the end: zeros)
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // one wave: its own tile writes have landed before its reads
         bf16x8 a[4][PF];
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            float v[8];
-            ch_ld8(stg + i * CH_STG_STRIDE + 16 * s4 + 8 * h, v);
-            bf16_split<PF>(v, a[s4]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // in registers: the tile may be overwritten by the next round
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                bf16x8 w[PF];
-#pragma unroll
-                for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                acc = bf16_prod<PF>(a[s4], w, acc);
-            }
-            const float bv = nt ? b1 : b0;
-            if (tl == wave) piv[nt] = __shfl(acc[0], i);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rr = base + mfma_row(r, h);
-                if (rr < rows) {
-                    const float v = acc[r];
-                    const float dlt = v - piv[nt];
-                    s1[nt] += dlt;
-                    s2[nt] += dlt * dlt;
-                    g.z_out[(size_t)rr * 64 + 32 * nt + i] = v + bv;
-                }
-            }
-        }
+        ch_tile_frags<PF>(stg, lane, a);   // (in registers: the tile may be overwritten by the next round)
+        ch_tile_product<PF, false>(a, Wf, lane, base, rows, tl == wave, s1, s2, piv,
+                                   [&](int nt, int, int rr, float v) { g.z_out[(size_t)rr * 64 + 32 * nt + i] = v + (nt ? b1 : b0); });
         my_rows += min(32, rows - base);
     }
     ch_store_stats(s1, s2, piv, my_rows, sred, snrows, g.stats_out + (size_t)lb * 192);

@@ -1,5 +1,9 @@
 // Device helpers shared by the launch chain (train_chain.hip) and the persistent chain (train_chain_persist.hip): tile algebra,
-// the pooled training-mode BatchNorm, the moment / sum partials.  See train_chain.hip's header for the design.
+// the pooled training-mode BatchNorm, the moment / sum partials -- and ONE definition of each stage of the forward, from which
+// chain_fwd_gather_kernel, chain_fwd_linear_kernel and the phases of chain_fwd_persist_kernel are built: ch_stage_fwd_weights,
+// ch_tile_frags, ch_tile_product, act4, ch_merge_stats (the neighbour gather is neighbour_mean_of, train_common.h).  The two forms of
+// the forward owe each other the same products in the same arithmetic on the same operands; they get them by calling the same code.
+// See train_chain.hip's header for the design.
 #pragma once
 #include "train_common.h"
 
@@ -175,12 +179,14 @@ __device__ __forceinline__ void ch_pool_sums(const float* __restrict__ psums, in
 }
 
 // The moment partial of a workgroup from its waves' (sum, sum of squares, pivot, rows): wave 0 rebases the others onto its own pivot
-// in wave order (fixed order: registers, lane halves, waves) and stores [3][64] at `out`.
+// in wave order (fixed order: registers, lane halves, waves) and hands the partial's [3][64] values to store(k, column, value).
 //   sum (v - p0) = sum (v - pw) + n (pw - p0),  sum (v - p0)^2 = sum (v - pw)^2 + 2 (pw - p0) sum (v - pw) + n (pw - p0)^2
-// sred: [waves][3][64], snrows: [waves].  Called by every thread; contains the barrier.
-__device__ __forceinline__ void ch_store_stats(float (&s1)[2], float (&s2)[2], const float (&piv)[2], int my_rows, float (*sred)[3][64],
-                                               int* snrows, float* out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+// sred: [waves][3][64], snrows: [waves].  WAIT: every wave first waits for its own outstanding stores (the persistent chain posts the
+// partial as a signal that they are visible).  Called by every thread; contains the barrier.
+template <bool WAIT, typename STORE>
+__device__ __forceinline__ void ch_merge_stats(float (&s1)[2], float (&s2)[2], const float (&piv)[2], int my_rows, float (*sred)[3][64],
+                                               int* snrows, int tid, STORE store) {
+    const int lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
     const int i = lane & 31, h = lane >> 5;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
@@ -193,6 +199,7 @@ __device__ __forceinline__ void ch_store_stats(float (&s1)[2], float (&s2)[2], c
         sred[wave][2][i] = piv[0], sred[wave][2][32 + i] = piv[1];
     }
     if (lane == 0) snrows[wave] = my_rows;
+    if constexpr (WAIT) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
     if (wave == 0 && h == 0) {
 #pragma unroll
@@ -207,13 +214,98 @@ __device__ __forceinline__ void ch_store_stats(float (&s1)[2], float (&s2)[2], c
                     t2 += sred[w][1][c] + (2.0f * dp) * sred[w][0][c] + n_w * dp * dp;
                 }
             }
-            out[0 * 64 + c] = t1, out[1 * 64 + c] = t2, out[2 * 64 + c] = piv[nt];
+            store(0, c, t1), store(1, c, t2), store(2, c, piv[nt]);
         }
     }
+}
+// ... stored as plain floats [3][64] at `out`: the launch chain's partial
+__device__ __forceinline__ void ch_store_stats(float (&s1)[2], float (&s2)[2], const float (&piv)[2], int my_rows, float (*sred)[3][64],
+                                               int* snrows, float* out) {
+    ch_merge_stats<false>(s1, s2, piv, my_rows, sred, snrows, threadIdx.x, [&](int k, int c, float v) { out[k * 64 + c] = v; });
 }
 
 #define CH_STG_STRIDE 68   // floats per row of the staging tile (272 B: conflict-free float4 rows both ways)
 #define CH_STG_FLOATS (32 * CH_STG_STRIDE)
+
+// ---- the stages of the forward ---------------------------------------------------------------------------------------------
+// BatchNorm + ReLU of a lane's four channels, relu(v * s + t): the forward's own expression (bn_value's, train_common.h)
+__device__ __forceinline__ float4 act4(const float4& v, const float4& s, const float4& t) {
+    return make_float4(fmaxf(v.x * s.x + t.x, 0.f), fmaxf(v.y * s.y + t.y, 0.f), fmaxf(v.z * s.z + t.z, 0.f), fmaxf(v.w * s.w + t.w, 0.f));
+}
+
+// A (64, 64) weight W[k = in][n = out] as the forward's B fragments: lane (n = 32 nt + i, k group h) of k-step s holds
+// W[16 s + 8 h .. + 7][n], split into PF bf16 pieces -> Wf[nt][s][piece][lane] (LDS).  The caller's barrier makes them visible.
+template <int PF>
+__device__ __forceinline__ void ch_stage_fwd_weights(const float* W, u32x4 (*Wf)[4][PF][64], int tid) {
+    for (int f = tid; f < 2 * 4 * 64; f += blockDim.x) {
+        const int l = f & 63, s4 = (f >> 6) & 3, nt = f >> 8;
+        const float* src = W + (size_t)(16 * s4 + 8 * (l >> 5)) * 64 + 32 * nt + (l & 31);
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = src[(size_t)u * 64];
+        bf16x8 p[PF];
+        bf16_split<PF>(v, p);
+#pragma unroll
+        for (int pc = 0; pc < PF; ++pc) Wf[nt][s4][pc][l] = __builtin_bit_cast(u32x4, p[pc]);
+    }
+}
+
+// The wave's staging tile (32 rows x 64 f32, written in the row layout) -> its A fragments: lane (row i, k group h) of k-step s takes
+// channels 16 s + 8 h .. + 7 of row i, split into PF pieces.  Between two LDS waits of the one wave that owns the tile: its writes
+// have landed before the reads, and the reads are in registers before the caller overwrites the tile.
+template <int PF>
+__device__ __forceinline__ void ch_tile_frags(const float* tile, int lane, bf16x8 (&a)[4][PF]) {
+    const int i = lane & 31, h = lane >> 5;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+        float v[8];
+        ch_ld8(tile + i * CH_STG_STRIDE + 16 * s4 + 8 * h, v);
+        bf16_split<PF>(v, a[s4]);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// The 64 -> 64 product of a 32-row tile (A fragments a, rows base .. base + 31) with the staged weight, and its pivot-shifted moments:
+// per out tile nt, four k-steps of bf16_prod<PF> into a zeroed accumulator; take_pivot: piv[nt] = row `base` of the product, column
+// 32 nt + i (acc[0] of lane i); the rows < `rows` add v - piv, (v - piv)^2 to s1, s2 in register order, v being the product WITHOUT
+// the bias (the pooling adds it to the mean), and every element goes to emit(nt, r, global row, v) -- r the accumulator register, a
+// constant at every call: the element's row in the tile is mfma_row(r, h), and an address formed from the lane's own row and
+// mfma_row(r, 0) keeps immediate offsets.  PAST_END: the rows of the tile past the end of the tensor are emitted too -- an LDS tile
+// written whole, the sums by selects and no branch (the persistent chain's phases G and M; asked to test the row in their emit
+// instead, the launch kernels got the selects as well and 4 to 16 VGPRs more).
+template <int PF, bool PAST_END, typename EMIT>
+__device__ __forceinline__ void ch_tile_product(const bf16x8 (&a)[4][PF], const u32x4 (*Wf)[4][PF][64], int lane, int base, int rows,
+                                                bool take_pivot, float (&s1)[2], float (&s2)[2], float (&piv)[2], EMIT emit) {
+    const int i = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            bf16x8 w[PF];
+#pragma unroll
+            for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
+            acc = bf16_prod<PF>(a[s4], w, acc);
+        }
+        if (take_pivot) piv[nt] = __shfl(acc[0], i);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rr = base + mfma_row(r, h);
+            const float v = acc[r];
+            if (rr < rows) {
+                const float d = v - piv[nt];
+                s1[nt] += d;
+                s2[nt] += d * d;
+                if constexpr (!PAST_END) emit(nt, r, rr, v);
+            }
+            if constexpr (PAST_END) emit(nt, r, rr, v);
+        }
+    }
+}
+
 struct ChBnGiven {   // a BatchNorm with known batch moments (null mean: none)
     const float *mean, *var, *gamma, *beta;
 };

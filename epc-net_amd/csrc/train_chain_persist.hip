@@ -1,5 +1,7 @@
 // The FORWARD of the 64-channel backbone of the training step as ONE persistent launch (models/epc-net.py:66-134, utils/tf_util.py:454-519
-// in training mode) -- the forward launches of train_chain.hip with their kernel boundaries replaced by grid-wide barriers.  (The
+// in training mode) -- the forward launches of train_chain.hip with their kernel boundaries replaced by grid-wide barriers, built from
+// the same stage helpers (train_chain_common.h, train_common.h): phases G, M and H below form their operand, call ch_tile_product
+// with their own emit and post.  (The
 // backward was built the same way -- 16 barriers, the gradient handed from layer to layer in registers -- was parity-green and SLOWER
 // than its launches, 2.25 -> 2.41 ms per 22-cloud step: in a replayed graph a kernel boundary + the pooled prologue cost what a barrier
 // costs, ~8 us, so only traffic saved pays, and the backward's gather runs 61 us on 12 waves against 44 on 16.  DESIGN.md 4 has the
@@ -151,7 +153,7 @@ __device__ __forceinline__ bool pst_poll(const PstCtx& c, const pst_gran* src, i
 }
 
 // ---- moments through the barrier ------------------------------------------------------------------------------------------
-// Workgroup partials: granules [parts][3][64] (sum (v - p), sum (v - p)^2, pivot p of the product WITHOUT the bias: ch_store_stats);
+// Workgroup partials: granules [parts][3][64] (sum (v - p), sum (v - p)^2, pivot p of the product WITHOUT the bias: ch_merge_stats);
 // group partials: granules [8][3][64][2] -- A = sum (v - P), B = sum (v - P)^2, P = the pivot of the group's first block as doubles
 // in two halves.   sum (v - p0) = sum (v - pw) + n (pw - p0);   sum (v - p0)^2 = sum (v - pw)^2 + 2 (pw - p0) sum (v - pw) + n (pw - p0)^2
 // The group's first workgroup merges its group's partials in ascending row order; every workgroup then merges the group partials in
@@ -269,60 +271,13 @@ __device__ __forceinline__ void pst_exit(PstCtx& c) {
     }
 }
 
-// A workgroup's moment partial from its waves' (sum, sum of squares, pivot, rows) -- ch_store_stats -- POSTED: every wave first waits
+// A workgroup's moment partial from its waves' (sum, sum of squares, pivot, rows) -- ch_merge_stats -- POSTED: every wave first waits
 // for its own stores of the phase (the rows other workgroups will read are write-through: complete = visible), then wave 0 merges
 // the waves in wave order and stores the tagged granules.  sred: [waves][3][64] floats, snrows: [waves].  Contains a barrier.
 __device__ __forceinline__ void pst_post_stats(float (&s1)[2], float (&s2)[2], const float (&piv)[2], int my_rows, float (*sred)[3][64],
                                                int* snrows, pst_gran* out, unsigned tag) {
-    const int tid = pst_tid();
-    const int lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
-    const int i = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        s1[nt] += __shfl_xor(s1[nt], 32);
-        s2[nt] += __shfl_xor(s2[nt], 32);
-    }
-    if (wave > 0 && h == 0) {
-        sred[wave][0][i] = s1[0], sred[wave][0][32 + i] = s1[1];
-        sred[wave][1][i] = s2[0], sred[wave][1][32 + i] = s2[1];
-        sred[wave][2][i] = piv[0], sred[wave][2][32 + i] = piv[1];
-    }
-    if (lane == 0) snrows[wave] = my_rows;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (wave == 0 && h == 0) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int c = 32 * nt + i;
-            float t1 = s1[nt], t2 = s2[nt];
-            for (int w = 1; w < nw; ++w) {
-                const float n_w = (float)snrows[w];
-                if (n_w > 0.f) {
-                    const float dp = sred[w][2][c] - piv[nt];
-                    t1 += sred[w][0][c] + n_w * dp;
-                    t2 += sred[w][1][c] + (2.0f * dp) * sred[w][0][c] + n_w * dp * dp;
-                }
-            }
-            st_gran(out + 0 * 64 + c, __float_as_uint(t1), tag), st_gran(out + 1 * 64 + c, __float_as_uint(t2), tag);
-            st_gran(out + 2 * 64 + c, __float_as_uint(piv[nt]), tag);
-        }
-    }
-}
-
-// forward B fragments of a (64, 64) weight: lane (n = 32 nt + i, k group h) of k-step s holds W[16 s + 8 h .. + 7][n]
-template <int PF>
-__device__ __forceinline__ void pst_stage_fwd_weights(const float* W, u32x4 (*Wf)[4][PF][64]) {
-    for (int f = pst_tid(); f < 2 * 4 * 64; f += blockDim.x) {
-        const int l = f & 63, s4 = (f >> 6) & 3, nt = f >> 8;
-        const float* src = W + (size_t)(16 * s4 + 8 * (l >> 5)) * 64 + 32 * nt + (l & 31);
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = src[(size_t)u * 64];
-        bf16x8 p[PF];
-        bf16_split<PF>(v, p);
-#pragma unroll
-        for (int pc = 0; pc < PF; ++pc) Wf[nt][s4][pc][l] = __builtin_bit_cast(u32x4, p[pc]);
-    }
+    ch_merge_stats<true>(s1, s2, piv, my_rows, sred, snrows, pst_tid(),
+                         [&](int k, int c, float v) { st_gran(out + k * 64 + c, __float_as_uint(v), tag); });
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -427,7 +382,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
         }
         __syncthreads();   // (red is scratch: the polls may overwrite it)
     }
-    pst_stage_fwd_weights<PF>(g.a.blk[0].Wa, Wf);
+    ch_stage_fwd_weights<PF>(g.a.blk[0].Wa, Wf, pst_tid());
 
 #pragma unroll 1
     for (int b = 0; b < g.a.nblocks; ++b) {
@@ -447,10 +402,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
         for (int k = 0; k < 8; ++k) xmr[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (have) {
             const float4 cs = *reinterpret_cast<const float4*>(&coef[0][4 * q]), ct = *reinterpret_cast<const float4*>(&coef[1][4 * q]);
-            auto act = [&](const float4& v) {   // relu(bn0(.)) of the lane's four channels: the forward's own expression
-                return make_float4(fmaxf(v.x * cs.x + ct.x, 0.f), fmaxf(v.y * cs.y + ct.y, 0.f), fmaxf(v.z * cs.z + ct.z, 0.f),
-                                   fmaxf(v.w * cs.w + ct.w, 0.f));
-            };
+            auto act = [&](const float4& v) { return act4(v, cs, ct); };   // relu(bn0(.)) of the lane's four channels
             const float4* z4 = reinterpret_cast<const float4*>(B.z0);
             // (Round 6: the next iteration's count and first 16 entries requested under this iteration's rows -- what took chain_bwd_gather
             // from 37 to 27 us -- measured 291 us against 280 here: 4 registers over the 168 of twelve waves, and this loop's three round
@@ -459,93 +411,27 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
             for (int r8 = 0; r8 < 8; ++r8) {
                 const int pt = base + 4 * r8 + p4;
                 float4 dd = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (pt < rows) {
-                    const int cloud_base = (pt / g.a.n) * g.a.n;
-                    const int c = g.a.cnt[pt];
-                    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                    auto add = [&](const float4& v) {
-                        const float4 y = act(v);
-                        acc.x += y.x, acc.y += y.y, acc.z += y.z, acc.w += y.w;
-                    };
-                    if (c <= g.a.cap) {
-                        int m = 0;
-                        if (c >= 20 && g.a.cap % 4 == 0) {
-                            const int4* il = reinterpret_cast<const int4*>(g.a.idx + (size_t)pt * g.a.cap);
-                            int nb[20];
-#pragma unroll
-                            for (int m4 = 0; m4 < 5; ++m4) {
-                                const int4 tq = il[m4];
-                                nb[4 * m4] = tq.x, nb[4 * m4 + 1] = tq.y, nb[4 * m4 + 2] = tq.z, nb[4 * m4 + 3] = tq.w;
-                            }
-                            float4 v[20];
-#pragma unroll
-                            for (int u = 0; u < 20; ++u) v[u] = z4[(unsigned)(cloud_base + nb[u]) * 16u + (unsigned)q];   // (32-bit offsets: rows * 16 < 2^32)
-#pragma unroll
-                            for (int u = 0; u < 20; ++u) add(v[u]);
-                            m = 20;
-                        }
-                        for (; m < c; ++m) add(z4[(size_t)(cloud_base + g.a.idx[(size_t)pt * g.a.cap + m]) * 16 + q]);
-                    } else {
-                        const float* pc = g.a.xyz + (size_t)cloud_base * 3;
-                        const int ii = pt - cloud_base;
-                        const float xi = pc[3 * ii], yi = pc[3 * ii + 1], zi = pc[3 * ii + 2];
-                        const float sqi = sq3(xi, yi, zi), kv = g.a.kth[pt];
-                        for (int j = 0; j < g.a.n; ++j) {
-                            const float xj = pc[3 * j], yj = pc[3 * j + 1], zj = pc[3 * j + 2];
-                            if (neg_sq_dist(sqi, xi, yi, zi, xj, yj, zj, sq3(xj, yj, zj)) >= kv) add(z4[(size_t)(cloud_base + j) * 16 + q]);
-                        }
-                    }
-                    acc.x /= g.kdiv, acc.y /= g.kdiv, acc.z /= g.kdiv, acc.w /= g.kdiv;
+                if (pt < rows) {   // (32-bit offsets for the rows in flight: rows * 16 < 2^32)
+                    const float4 xm = neighbour_mean_of<unsigned>(z4, g.a.xyz, g.a.idx, g.a.cnt, g.a.kth, g.a.cap, g.a.n, g.kdiv, pt, q, act);
                     const float4 own = act(z4[(size_t)pt * 16 + q]);
-                    dd = make_float4(acc.x - own.x, acc.y - own.y, acc.z - own.z, acc.w - own.w);
+                    dd = make_float4(xm.x - own.x, xm.y - own.y, xm.z - own.z, xm.w - own.w);
 #pragma unroll
                     for (int k = 0; k < 8; ++k)
-                        if (r8 == k) xmr[k] = acc;   // (r8 is wave-uniform: selects, no dynamic register index)
+                        if (r8 == k) xmr[k] = xm;   // (r8 is wave-uniform: selects, no dynamic register index)
                     reinterpret_cast<float4*>(B.d)[(size_t)pt * 16 + q] = dd;
                 }
                 *reinterpret_cast<float4*>(tile + (4 * r8 + p4) * CH_STG_STRIDE + 4 * q) = dd;   // (rows past the end: zeros)
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // one wave: its own tile writes have landed before its reads
             bf16x8 a[4][PF];
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                float v[8];
-                ch_ld8(tile + i * CH_STG_STRIDE + 16 * s4 + 8 * h, v);
-                bf16_split<PF>(v, a[s4]);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // in registers: the tile takes za next
+            ch_tile_frags<PF>(tile, lane, a);   // (in registers: the tile takes za next)
             const float b0 = B.ba ? B.ba[i] : 0.f, b1 = B.ba ? B.ba[32 + i] : 0.f;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) {
-                    bf16x8 w[PF];
-#pragma unroll
-                    for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                    acc = bf16_prod<PF>(a[s4], w, acc);
-                }
-                const float bv = nt ? b1 : b0;
-                piv[nt] = __shfl(acc[0], i);   // row `base`
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int rl4 = (r & 3) + 8 * (r >> 2), rl = rl4 + 4 * h, rr = base + rl;
-                    const float v = acc[r];
-                    if (rr < rows) {
-                        const float dlt = v - piv[nt];
-                        s1[nt] += dlt;
-                        s2[nt] += dlt * dlt;
-                    }
-                    tile[rl * CH_STG_STRIDE + 32 * nt + i] = v + bv;
-                }
-            }
+            ch_tile_product<PF, true>(a, Wf, lane, base, rows, true, s1, s2, piv,
+                                      [&](int nt, int r, int, float v) { tile[mfma_row(r, h) * CH_STG_STRIDE + 32 * nt + i] = v + (nt ? b1 : b0); });
             my_rows = min(32, rows - base);
         }
         pst_post_stats(s1, s2, piv, my_rows, sred, snrows, stats_of(phase) + (size_t)cx.lb * 192, pst_tag(cx, phase));
         if (have) store_tile_rows(B.za);       // (after the post: under the barrier)
-        pst_stage_fwd_weights<PF>(B.Wb, Wf);   // (every wave is past its products: pst_post_stats' barrier) -- under the wait
+        ch_stage_fwd_weights<PF>(B.Wb, Wf, pst_tid());   // (every wave is past its products: pst_post_stats' barrier) -- under the wait
         // ================= barrier: za's moments =================
         if (!barrier_moments(B.ba, B.gamma_a, B.beta_a, B.mean_a, B.var_a)) { poison(); return; }
         // ================= phase M =================
@@ -565,36 +451,12 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // in registers: the tile takes zb next
             const float b0 = B.bb ? B.bb[i] : 0.f, b1 = B.bb ? B.bb[32 + i] : 0.f;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) {
-                    bf16x8 w[PF];
-#pragma unroll
-                    for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                    acc = bf16_prod<PF>(a[s4], w, acc);
-                }
-                const float bv = nt ? b1 : b0;
-                piv[nt] = __shfl(acc[0], i);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int rl4 = (r & 3) + 8 * (r >> 2), rl = rl4 + 4 * h, rr = base + rl;
-                    const float v = acc[r];
-                    if (rr < rows) {
-                        const float dlt = v - piv[nt];
-                        s1[nt] += dlt;
-                        s2[nt] += dlt * dlt;
-                    }
-                    tile[rl * CH_STG_STRIDE + 32 * nt + i] = v + bv;
-                }
-            }
+            ch_tile_product<PF, true>(a, Wf, lane, base, rows, true, s1, s2, piv,
+                                      [&](int nt, int r, int, float v) { tile[mfma_row(r, h) * CH_STG_STRIDE + 32 * nt + i] = v + (nt ? b1 : b0); });
         }
         pst_post_stats(s1, s2, piv, my_rows, sred, snrows, stats_of(phase) + (size_t)cx.lb * 192, pst_tag(cx, phase));
         if (have) store_tile_rows(B.zb);
-        if (B.W0_next) pst_stage_fwd_weights<PF>(B.W0_next, Wf);
+        if (B.W0_next) ch_stage_fwd_weights<PF>(B.W0_next, Wf, pst_tid());
         // ================= barrier: zb's moments =================
         if (!barrier_moments(B.bb, B.gamma_b, B.beta_b, B.mean_b, B.var_b)) { poison(); return; }
         // ================= phase H =================
@@ -605,51 +467,19 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
             for (int r8 = 0; r8 < 8; ++r8) {
                 const int rl = 4 * r8 + p4, pt = base + rl;
                 const float4 z = *reinterpret_cast<const float4*>(tile + rl * CH_STG_STRIDE + 4 * q);
-                float4 v;
-                v.x = fmaxf(z.x * cs.x + ct.x, 0.f), v.y = fmaxf(z.y * cs.y + ct.y, 0.f), v.z = fmaxf(z.z * cs.z + ct.z, 0.f),
-                v.w = fmaxf(z.w * cs.w + ct.w, 0.f);
+                float4 v = act4(z, cs, ct);
                 v.x += xmr[r8].x, v.y += xmr[r8].y, v.z += xmr[r8].z, v.w += xmr[r8].w;
                 if (pt >= rows) v = make_float4(0.f, 0.f, 0.f, 0.f);
                 *reinterpret_cast<float4*>(tile + rl * CH_STG_STRIDE + 4 * q) = v;   // (the concat's slice leaves from here after the post)
             }
             if (B.W0_next) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 bf16x8 a[4][PF];
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) {
-                    float v[8];
-                    ch_ld8(tile + i * CH_STG_STRIDE + 16 * s4 + 8 * h, v);
-                    bf16_split<PF>(v, a[s4]);
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                ch_tile_frags<PF>(tile, lane, a);
                 const float b0 = B.b0_next ? B.b0_next[i] : 0.f, b1 = B.b0_next ? B.b0_next[32 + i] : 0.f;
-                float* zlane = B.z0_next + (size_t)(base + 4 * h) * 64 + i;
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    f32x16 acc;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-                    for (int s4 = 0; s4 < 4; ++s4) {
-                        bf16x8 w[PF];
-#pragma unroll
-                        for (int pc = 0; pc < PF; ++pc) w[pc] = __builtin_bit_cast(bf16x8, Wf[nt][s4][pc][lane]);
-                        acc = bf16_prod<PF>(a[s4], w, acc);
-                    }
-                    const float bv = nt ? b1 : b0;
-                    piv[nt] = __shfl(acc[0], i);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rl4 = (r & 3) + 8 * (r >> 2), rr = base + rl4 + 4 * h;
-                        if (rr < rows) {
-                            const float v = acc[r];
-                            const float dlt = v - piv[nt];
-                            s1[nt] += dlt;
-                            s2[nt] += dlt * dlt;
-                            st_wt1(zlane + rl4 * 64 + 32 * nt, v + bv);   // gathered by OTHER workgroups after the barrier
-                        }
-                    }
-                }
+                float* zlane = B.z0_next + (size_t)(base + 4 * h) * 64 + i;   // (the lane's first row: its stores take immediate offsets)
+                ch_tile_product<PF, false>(a, Wf, lane, base, rows, true, s1, s2, piv, [&](int nt, int r, int, float v) {
+                    st_wt1(zlane + mfma_row(r, 0) * 64 + 32 * nt, v + (nt ? b1 : b0));   // gathered by OTHER workgroups after the barrier
+                });
             }
         }
         if (B.W0_next) pst_post_stats(s1, s2, piv, my_rows, sred, snrows, stats_of(phase) + (size_t)cx.lb * 192, pst_tag(cx, phase));
@@ -671,7 +501,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the tile is read: the next block's gather stages d in it
         }
-        if (B.W0_next) pst_stage_fwd_weights<PF>(g.a.blk[b + 1].Wa, Wf);
+        if (B.W0_next) ch_stage_fwd_weights<PF>(g.a.blk[b + 1].Wa, Wf, pst_tid());
     }
     pst_exit(cx);
 }

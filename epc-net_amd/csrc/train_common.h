@@ -76,6 +76,62 @@ __device__ __forceinline__ bf16x8 bf16_tr_frag(const char* img, int t, int s2, i
     return __builtin_bit_cast(bf16x8, v);
 }
 
+// The neighbour mean of point `pt` (models/epc-net.py:70-72) for one lane's four channels 4 q .. 4 q + 3 of the (rows, 64) tensor z4:
+// (sum over the point's selected neighbours of act(row)) / kdiv.  `act` is what is applied to a row as it is loaded: the identity for
+// a tensor that exists (neighbour_mean_kernel), relu(bn0(.)) for the chain's gathers, where x is never written.  THE ORDER of the
+// additions is part of the result, and every caller gets this one:
+//   * a list of at most `cap` entries (cnt <= cap): when it has 20 or more and cap % 4 == 0, its first 20 entries come as five int4
+//     index loads, their 20 rows are in flight at once (the one-at-a-time loop chains 20 dependent (index, row) round trips; every
+//     ordinary row has at least 20) and are added in list order; then the tail, one entry at a time, in list order;
+//   * more than `cap` selected entries (exact ties: duplicated / zero-padded clouds): the exact scan over the cloud's points j in
+//     ascending order with the selection's own test, -|p_i - p_j|^2 >= kth.
+// OFF is the offset type of the 20 rows in flight: size_t, or unsigned where the caller knows rows * 16 < 2^32 (the persistent chain).
+// (The point's own row, act(z4[pt * 16 + q]) for d = xm - x, is the caller's one line: loaded in here and returned beside the mean it
+// cost the persistent chain 8 VGPRs, 153 -> 161 of its 168.)
+struct NbIdentity {
+    __device__ __forceinline__ float4 operator()(const float4& v) const { return v; }
+};
+template <typename OFF, typename ACT>
+__device__ __forceinline__ float4 neighbour_mean_of(const float4* z4, const float* xyz, const int32_t* idx, const int32_t* cnt,
+                                                    const float* kth, int cap, int n, float kdiv, int pt, int q, ACT act) {
+    const int cloud_base = (pt / n) * n;
+    const int c = cnt[pt];
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto add = [&](const float4& v) {
+        const float4 y = act(v);
+        acc.x += y.x, acc.y += y.y, acc.z += y.z, acc.w += y.w;
+    };
+    if (c <= cap) {
+        int m = 0;
+        if (c >= 20 && cap % 4 == 0) {
+            const int4* il = reinterpret_cast<const int4*>(idx + (size_t)pt * cap);
+            int nb[20];
+#pragma unroll
+            for (int m4 = 0; m4 < 5; ++m4) {
+                const int4 tq = il[m4];
+                nb[4 * m4] = tq.x, nb[4 * m4 + 1] = tq.y, nb[4 * m4 + 2] = tq.z, nb[4 * m4 + 3] = tq.w;
+            }
+            float4 v[20];
+#pragma unroll
+            for (int u = 0; u < 20; ++u) v[u] = z4[(OFF)(cloud_base + nb[u]) * (OFF)16 + (OFF)q];
+#pragma unroll
+            for (int u = 0; u < 20; ++u) add(v[u]);
+            m = 20;
+        }
+        for (; m < c; ++m) add(z4[(size_t)(cloud_base + idx[(size_t)pt * cap + m]) * 16 + q]);
+    } else {
+        const float* pc = xyz + (size_t)cloud_base * 3;
+        const int ii = pt - cloud_base;
+        const float xi = pc[3 * ii], yi = pc[3 * ii + 1], zi = pc[3 * ii + 2];
+        const float sqi = sq3(xi, yi, zi), kv = kth[pt];
+        for (int j = 0; j < n; ++j) {
+            const float xj = pc[3 * j], yj = pc[3 * j + 1], zj = pc[3 * j + 2];
+            if (neg_sq_dist(sqi, xi, yi, zi, xj, yj, zj, sq3(xj, yj, zj)) >= kv) add(z4[(size_t)(cloud_base + j) * 16 + q]);
+        }
+    }
+    return make_float4(acc.x / kdiv, acc.y / kdiv, acc.z / kdiv, acc.w / kdiv);
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------
 static inline bool epc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

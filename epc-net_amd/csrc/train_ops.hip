@@ -2145,10 +2145,9 @@ extern "C" int epc_linear_smallk_dw(const float* x, const float* dy, int rows, i
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// Neighbour mean over the kNN index lists (64 channels): forward gather, backward scatter (f32 atomics).
-// Rows with more than `cap` selected entries take the exact scan (same rule as the fused block kernel).
+// Neighbour mean over the kNN index lists (64 channels), 16 lanes x float4 per point: neighbour_mean_of (train_common.h) on the
+// tensor as it stands.  (Its transpose is a gather as well: epc_neighbour_mean_diff_bwd_gather_sum.)
 // ----------------------------------------------------------------------------------------------------------------
-template <bool BWD>
 __global__ __launch_bounds__(256) void neighbour_mean_kernel(const float* __restrict__ src, const float* __restrict__ xyz,
                                                              const int32_t* __restrict__ idx,
                                                              const int32_t* __restrict__ cnt,
@@ -2159,65 +2158,12 @@ __global__ __launch_bounds__(256) void neighbour_mean_kernel(const float* __rest
     const int t = xcd_contiguous_block(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
     const int g = t >> 4, q = t & 15;
     if (g >= total_points) return;
-    const int cloud_base = (g / n) * n;
     const float4* s4 = reinterpret_cast<const float4*>(src);
-    const int c = cnt[g];
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 mine;
-    if (BWD) {
-        mine = s4[(size_t)g * 16 + q];
-        mine.x /= kdiv, mine.y /= kdiv, mine.z /= kdiv, mine.w /= kdiv;
-    }
-    auto visit = [&](int j) {
-        if (BWD) {
-            float* d = dst + ((size_t)(cloud_base + j) * 16 + q) * 4;
-            atomicAdd(d + 0, mine.x);
-            atomicAdd(d + 1, mine.y);
-            atomicAdd(d + 2, mine.z);
-            atomicAdd(d + 3, mine.w);
-        } else {
-            const float4 v = s4[(size_t)(cloud_base + j) * 16 + q];
-            acc.x += v.x, acc.y += v.y, acc.z += v.z, acc.w += v.w;
-        }
-    };
-    if (c <= cap) {
-        int m = 0;
-        if (!BWD && c >= 20 && cap % 4 == 0) {
-            // the first 20 entries (every ordinary row has at least 20): five int4 index loads, then all 20 row loads in flight
-            // at once, added in ascending order -- the one-at-a-time loop below chains 20 dependent (index, row) round trips
-            const int4* il = reinterpret_cast<const int4*>(idx + (size_t)g * cap);
-            int nb[20];
-#pragma unroll
-            for (int m4 = 0; m4 < 5; ++m4) {
-                const int4 tq = il[m4];
-                nb[4 * m4] = tq.x, nb[4 * m4 + 1] = tq.y, nb[4 * m4 + 2] = tq.z, nb[4 * m4 + 3] = tq.w;
-            }
-            float4 v[20];
-#pragma unroll
-            for (int u = 0; u < 20; ++u) v[u] = s4[(size_t)(cloud_base + nb[u]) * 16 + q];
-#pragma unroll
-            for (int u = 0; u < 20; ++u) acc.x += v[u].x, acc.y += v[u].y, acc.z += v[u].z, acc.w += v[u].w;
-            m = 20;
-        }
-        for (; m < c; ++m) visit(idx[(size_t)g * cap + m]);
-    } else {
-        const float* pc = xyz + (size_t)cloud_base * 3;
-        const int i = g - cloud_base;
-        const float xi = pc[3 * i], yi = pc[3 * i + 1], zi = pc[3 * i + 2];
-        const float sqi = sq3(xi, yi, zi), kv = kth[g];
-        for (int j = 0; j < n; ++j) {
-            const float xj = pc[3 * j], yj = pc[3 * j + 1], zj = pc[3 * j + 2];
-            if (neg_sq_dist(sqi, xi, yi, zi, xj, yj, zj, sq3(xj, yj, zj)) >= kv) visit(j);
-        }
-    }
-    if (!BWD) {
-        acc.x /= kdiv, acc.y /= kdiv, acc.z /= kdiv, acc.w /= kdiv;
-        reinterpret_cast<float4*>(dst)[(size_t)g * 16 + q] = acc;
-        if (diff) {   // xm - x (models/epc-net.py:72), written by the same launch
-            const float4 own = s4[(size_t)g * 16 + q];
-            reinterpret_cast<float4*>(diff)[(size_t)g * 16 + q] =
-                make_float4(acc.x - own.x, acc.y - own.y, acc.z - own.z, acc.w - own.w);
-        }
+    const float4 xm = neighbour_mean_of<size_t>(s4, xyz, idx, cnt, kth, cap, n, kdiv, g, q, NbIdentity());
+    reinterpret_cast<float4*>(dst)[(size_t)g * 16 + q] = xm;
+    if (diff) {   // xm - x (models/epc-net.py:72), written by the same launch
+        const float4 own = s4[(size_t)g * 16 + q];
+        reinterpret_cast<float4*>(diff)[(size_t)g * 16 + q] = make_float4(xm.x - own.x, xm.y - own.y, xm.z - own.z, xm.w - own.w);
     }
 }
 
@@ -2227,7 +2173,7 @@ extern "C" int epc_neighbour_mean_fwd(const float* x, const float* xyz, const in
     EPC_CHECK_ARG(x && xyz && idx && cnt && kth && xm, "null pointer");
     EPC_CHECK_ARG(num_clouds > 0 && n > 0 && knn > 0 && cap >= EPC_KNN_SELECT, "bad shape");
     const long total = (long)num_clouds * n;
-    hipLaunchKernelGGL(neighbour_mean_kernel<false>, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(neighbour_mean_kernel, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, x, xyz, idx, cnt, kth, cap, (int)total, n, (float)knn, xm, nullptr);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
@@ -2240,7 +2186,7 @@ extern "C" int epc_neighbour_mean_diff_fwd(const float* x, const float* xyz, con
     EPC_CHECK_ARG(x && xyz && idx && cnt && kth && xm && diff, "null pointer");
     EPC_CHECK_ARG(num_clouds > 0 && n > 0 && knn > 0 && cap >= EPC_KNN_SELECT, "bad shape");
     const long total = (long)num_clouds * n;
-    hipLaunchKernelGGL(neighbour_mean_kernel<false>, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(neighbour_mean_kernel, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, x, xyz, idx, cnt, kth, cap, (int)total, n, (float)knn, xm, diff);
     EPC_CHECK_LAUNCH();
     return EPC_OK;

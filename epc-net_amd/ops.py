@@ -754,11 +754,6 @@ def chain_persist_check(device=None):
             L.check(rc)
 
 
-def chain_ok(rows):
-    """The fused backbone chain (ProxyConvChain) covers both GEMM arithmetics of the step and any row count."""
-    return rows >= 1
-
-
 class ProxyConvChain(torch.autograd.Function):
     """The whole 64-channel backbone behind conv1's product as ONE autograd node on the fused chain launches of
     csrc/train_chain.hip (models/epc-net.py:66-134 in training mode): for block b = 1 .. nblocks
@@ -796,33 +791,45 @@ class ProxyConvChain(torch.autograd.Function):
         assert z01.shape[1] == 64 and rows == graph.num_clouds * graph.n
         dev = z01.device
         blocks = ProxyConvChain._split(nblocks, [p.contiguous() if p is not None else None for p in params])
-        P = lib.epc_chain_parts(rows)
         width = 64 * nblocks
         new = lambda: torch.empty((rows, 64), dtype=torch.float32, device=dev)
         vec = lambda: torch.empty(64, dtype=torch.float32, device=dev)
-        stats = lambda: torch.empty(P * 192, dtype=torch.float32, device=dev)
-        ptr = lambda t: t.data_ptr() if t is not None else None
         cat = torch.empty((rows, width), dtype=torch.float32, device=dev)
         # the bf16 head (Conv5VladHead, mode "bf16") reads the concat as bf16: written beside the f32 tensor by the launches that form it
         # (``want_bf16``: the caller knows that the bf16 streamed head is what consumes the concat; the copy is an OUTPUT of the node,
         # handed on explicitly -- tf_util.proxyconv_backbone -> conv1d_l2_normalized -> LazyConv5Features -> Conv5VladHead)
         cat16 = torch.empty((rows, width), dtype=torch.bfloat16, device=dev) if want_bf16 else None
-        g = graph
+        # per block, both forms of the forward: the next block's z0 (none after the last), d, za, zb and the six batch moments
+        z0s = [z01] + [new() for _ in range(nblocks - 1)] + [None]
+        tens = [(new(), new(), new()) for _ in range(nblocks)]
+        moms = [tuple(vec() for _ in range(6)) for _ in range(nblocks)]
         if CHAIN_PERSIST_FWD and nblocks <= L.EPC_CHAIN_MAX_BLOCKS and lib.epc_chain_persist_ok(rows):
-            saved, outs = ProxyConvChain._forward_persistent(lib, z01, g, k, eps, nblocks, pieces_fwd, blocks, cat, cat16)
-            ctx.save_for_backward(cat, *saved, *[p for p in params])
-            ctx.graph, ctx.k, ctx.eps, ctx.nblocks = graph, int(k), float(eps), int(nblocks)
-            ctx.pieces_bwd, ctx.n_params = int(pieces_bwd), len(params)
-            ctx.mark_non_differentiable(*outs, *([cat16] if cat16 is not None else []))
-            ctx.set_materialize_grads(False)
-            return (cat,) + tuple(outs) + (cat16,)
-        st0 = stats()
-        L.check(lib.epc_chain_stats(z01.data_ptr(), rows, st0.data_ptr(), _st()))
-        z0, in_stats, in_bias = z01, st0, None
+            ProxyConvChain._launch_persistent(lib, graph, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16)
+        else:
+            ProxyConvChain._launch_chain(lib, graph, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16)
         saved, outs = [], []
+        for b in range(nblocks):
+            (d, za, zb), (m0, v0, ma, va, mb, vb) = tens[b], moms[b]
+            saved += [z0s[b], d, za, zb, m0, v0, ma, va, mb, vb]
+            outs += ([z0s[b]] if b > 0 else []) + [m0, v0, za, ma, va, zb, mb, vb]      # (block 1's z0 is the input itself)
+        ctx.save_for_backward(cat, *saved, *[p for p in params])
+        ctx.graph, ctx.k, ctx.eps, ctx.nblocks = graph, int(k), float(eps), int(nblocks)
+        ctx.pieces_bwd, ctx.n_params = int(pieces_bwd), len(params)
+        ctx.mark_non_differentiable(*outs, *([cat16] if cat16 is not None else []))
+        ctx.set_materialize_grads(False)
+        return (cat,) + tuple(outs) + (cat16,)
+
+    @staticmethod
+    def _launch_chain(lib, g, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16):
+        """The forward as the launch chain: z01's moment partials, then gather, mid and head (or tail) per block."""
+        rows, width, dev, nblocks = int(cat.shape[0]), int(cat.shape[1]), cat.device, len(blocks)
+        stats = lambda: torch.empty(lib.epc_chain_parts(rows) * 192, dtype=torch.float32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        in_stats, in_bias = stats(), None
+        L.check(lib.epc_chain_stats(z0s[0].data_ptr(), rows, in_stats.data_ptr(), _st()))
         for b, (W0, b0, g0, bt0, Wa, ba, ga, bta, Wb, bb, gb, btb) in enumerate(blocks):
-            m0, v0, ma, va, mb, vb = vec(), vec(), vec(), vec(), vec(), vec()
-            xm, d, za, zb = new(), new(), new(), new()
+            z0, z0n, (d, za, zb), (m0, v0, ma, va, mb, vb) = z0s[b], z0s[b + 1], tens[b], moms[b]
+            xm = torch.empty_like(d)      # (the persistent kernel keeps the neighbour means in registers)
             st_a, st_b = stats(), stats()
             L.check(lib.epc_chain_fwd_gather(z0.data_ptr(), in_stats.data_ptr(), ptr(in_bias), m0.data_ptr(), v0.data_ptr(),
                                              g0.data_ptr(), bt0.data_ptr(), float(eps), g.xyz.data_ptr(), g.idx.data_ptr(),
@@ -834,33 +841,18 @@ class ProxyConvChain(torch.autograd.Function):
                                              st_b.data_ptr(), rows, int(pieces_fwd), _st()))
             slice_ptr = cat.data_ptr() + 4 * 64 * b
             slice16 = cat16.data_ptr() + 2 * 64 * b if cat16 is not None else None
-            if b + 1 < nblocks:
-                W0n, b0n = blocks[b + 1][0], blocks[b + 1][1]
-                z0n, st0n = new(), stats()
-                L.check(lib.epc_chain_fwd_linear(zb.data_ptr(), st_b.data_ptr(), ptr(bb), mb.data_ptr(), vb.data_ptr(), gb.data_ptr(),
-                                                 btb.data_ptr(), float(eps), xm.data_ptr(), slice_ptr, width, slice16, W0n.data_ptr(),
-                                                 ptr(b0n), z0n.data_ptr(), st0n.data_ptr(), rows, int(pieces_fwd), _st()))
-            else:
-                z0n, st0n, b0n = None, None, None
-                L.check(lib.epc_chain_fwd_linear(zb.data_ptr(), st_b.data_ptr(), ptr(bb), mb.data_ptr(), vb.data_ptr(), gb.data_ptr(),
-                                                 btb.data_ptr(), float(eps), xm.data_ptr(), slice_ptr, width, slice16, None, None, None,
-                                                 None, rows, int(pieces_fwd), _st()))
-            saved += [z0, d, za, zb, m0, v0, ma, va, mb, vb]
-            outs += ([z0] if b > 0 else []) + [m0, v0, za, ma, va, zb, mb, vb]      # (block 1's z0 is the input itself)
-            z0, in_stats, in_bias = z0n, st0n, b0n
-        ctx.save_for_backward(cat, *saved, *[p for p in params])
-        ctx.graph, ctx.k, ctx.eps, ctx.nblocks = graph, int(k), float(eps), int(nblocks)
-        ctx.pieces_bwd, ctx.n_params = int(pieces_bwd), len(params)
-        ctx.mark_non_differentiable(*outs, *([cat16] if cat16 is not None else []))
-        ctx.set_materialize_grads(False)
-        return (cat,) + tuple(outs) + (cat16,)
+            # head: the block's output into its slice of the concat and, before the last block's tail, the next block's leading conv
+            W0n, b0n = (blocks[b + 1][0], blocks[b + 1][1]) if b + 1 < nblocks else (None, None)
+            st0n = stats() if z0n is not None else None
+            L.check(lib.epc_chain_fwd_linear(zb.data_ptr(), st_b.data_ptr(), ptr(bb), mb.data_ptr(), vb.data_ptr(), gb.data_ptr(),
+                                             btb.data_ptr(), float(eps), xm.data_ptr(), slice_ptr, width, slice16, ptr(W0n),
+                                             ptr(b0n), ptr(z0n), ptr(st0n), rows, int(pieces_fwd), _st()))
+            in_stats, in_bias = st0n, b0n
 
     @staticmethod
-    def _forward_persistent(lib, z01, g, k, eps, nblocks, pieces_fwd, blocks, cat, cat16):
-        """The whole forward as one launch (epc_chain_fwd_persist); returns (saved, outs) in forward()'s order."""
-        rows, dev = int(z01.shape[0]), z01.device
-        new = lambda: torch.empty((rows, 64), dtype=torch.float32, device=dev)
-        vec = lambda: torch.empty(64, dtype=torch.float32, device=dev)
+    def _launch_persistent(lib, g, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16):
+        """The whole forward as one launch (epc_chain_fwd_persist)."""
+        nblocks = len(blocks)
         ptr = lambda t: t.data_ptr() if t is not None else None
         a = L.ChainFwdArgs()
         a.nblocks = nblocks
@@ -868,27 +860,18 @@ class ProxyConvChain(torch.autograd.Function):
         a.cap, a.num_clouds, a.n, a.knn = L.EPC_KNN_CAP, g.num_clouds, g.n, int(k)
         a.cat, a.cat_bf16 = cat.data_ptr(), ptr(cat16)
         a.eps = float(eps)
-        a.workspace, a.spin_ticks = chain_workspace(dev).data_ptr(), int(CHAIN_SPIN_TICKS)
-        saved, outs = [], []
-        z0 = z01
+        a.workspace, a.spin_ticks = chain_workspace(cat.device).data_ptr(), int(CHAIN_SPIN_TICKS)
         for b, (W0, b0, g0, bt0, Wa, ba, ga, bta, Wb, bb, gb, btb) in enumerate(blocks):
-            m0, v0, ma, va, mb, vb = vec(), vec(), vec(), vec(), vec(), vec()
-            d, za, zb = new(), new(), new()
             nxt = blocks[b + 1] if b + 1 < nblocks else None
-            z0n = new() if nxt is not None else None
             B = a.blk[b]
             B.gamma0, B.beta0, B.in_bias = g0.data_ptr(), bt0.data_ptr(), (ptr(b0) if b > 0 else None)
             B.Wa, B.ba, B.gamma_a, B.beta_a = Wa.data_ptr(), ptr(ba), ga.data_ptr(), bta.data_ptr()
             B.Wb, B.bb, B.gamma_b, B.beta_b = Wb.data_ptr(), ptr(bb), gb.data_ptr(), btb.data_ptr()
             B.W0_next, B.b0_next = (nxt[0].data_ptr(), ptr(nxt[1])) if nxt is not None else (None, None)
-            B.z0, B.z0_next = z0.data_ptr(), ptr(z0n)
-            B.mean0, B.var0, B.mean_a, B.var_a, B.mean_b, B.var_b = (t.data_ptr() for t in (m0, v0, ma, va, mb, vb))
-            B.d, B.za, B.zb = d.data_ptr(), za.data_ptr(), zb.data_ptr()
-            saved += [z0, d, za, zb, m0, v0, ma, va, mb, vb]
-            outs += ([z0] if b > 0 else []) + [m0, v0, za, ma, va, zb, mb, vb]
-            z0 = z0n
+            B.z0, B.z0_next = z0s[b].data_ptr(), ptr(z0s[b + 1])
+            B.mean0, B.var0, B.mean_a, B.var_a, B.mean_b, B.var_b = (t.data_ptr() for t in moms[b])
+            B.d, B.za, B.zb = (t.data_ptr() for t in tens[b])
         L.check(lib.epc_chain_fwd_persist(ctypes.byref(a), int(pieces_fwd), _st()))
-        return saved, outs
 
     @staticmethod
     def backward(ctx, dcat, *_unused):

@@ -324,7 +324,7 @@ def proxyconv_backbone(point_cloud, graph, k, nblocks, bn_decay=None, is_trainin
     from .. import ops
     B, N, cin = (int(v) for v in point_cloud.shape)
     rows = B * N
-    if not (is_training and USE_CHAIN and ops.chain_ok(rows)):
+    if not (is_training and USE_CHAIN):
         outs, inp = [], point_cloud
         for b in range(1, nblocks + 1):
             x = conv1d(inp, 64, 1, padding='VALID', stride=1, bn=True, is_training=is_training, scope='conv%d' % b, bn_decay=bn_decay)
