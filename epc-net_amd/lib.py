@@ -1,4 +1,10 @@
-"""ctypes binding of ``libepcnet_hip.so`` (declarations: ``include/epcnet.h``).
+"""ctypes binding of ``libepcnet_hip.so``, derived from ``include/epcnet.h`` at import.
+
+The header is the one definition of the C boundary: ``parse_header`` reads every declaration, ``#define EPC_*`` and the
+``epc_status`` enum out of it, and this module sets ``restype`` / ``argtypes`` of every entry point, the ``EPC_*`` module
+attributes, ``STATUS_NAMES`` and ``EXPORTS`` from the result.  Anything the reader does not understand is an exception at
+import, never a skipped line.  Only the three structures are mirrored by hand (tests/test_host_cpu.py checks their layout
+against the compiler).
 
 There is NO fallback: if the shared library has not been built (``python -c "import __graft_entry__ as g;
 g.build()"`` or ``make -C epc-net_amd/csrc``) importing this module raises, and every op raises ``EpcNetError``
@@ -10,61 +16,70 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_size_t, c_void_p
+import re
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_void_p
 
 import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EPCNET_LIB: load another build of the same library instead (how two builds are compared, e.g. scripts/ab_block.sh)
 LIB_PATH = os.environ.get("EPCNET_LIB") or os.path.join(_HERE, "libepcnet_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "epcnet.h")
 
-EPC_OK = 0
-EPC_ARCH_EPC_NET = 0
-EPC_ARCH_EPC_NET_L = 1
-EPC_KNN_SELECT = 20
-EPC_KNN_CAP = 32
-EPC_ERANGE = -5
-STATUS_NAMES = {0: "EPC_OK", -1: "EPC_EINVAL", -2: "EPC_ENOMEM", -3: "EPC_EHIP", -4: "EPC_ENOTFOUND", -5: "EPC_ERANGE"}
-# epc_cfg.precision (include/epcnet.h): f32-equivalent arithmetic (conv layers scaled split-fp16 x3, assignment / aggregate
-# split-bf16 x3, f32 tensors in HBM except the 3-byte `feat` map) / the f16 + f6 fast arithmetic (either model)
-EPC_PRECISION_F32 = 0
-EPC_PRECISION_FAST = 1
-PRECISION_IDS = {"f32": EPC_PRECISION_F32, "fast": EPC_PRECISION_FAST}
-# per-cloud status bits (a flagged cloud's descriptor is NaN)
-EPC_STATUS_NONFINITE_INPUT = 1
-EPC_STATUS_FP16_RANGE = 2
+_SCALARS = {"int": c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "float": c_float,
+            "size_t": ctypes.c_size_t, "int32_t": c_int32, "uint32_t": ctypes.c_uint32}
 
-# every symbol include/epcnet.h declares (tests check the library exports exactly these)
-EXPORTS = [
-    "epc_last_error", "epc_version", "epc_net_packed_bytes", "epc_net_pack_weights", "epc_net_workspace_bytes",
-    "epc_net_forward", "epc_net_forward_overlapped", "epc_net_last_status", "epc_conv5_assign_f32_fwd",
-    "epc_vlad_aggregate_f32_fwd", "epc_knn_topk", "epc_knn_topk_conv1", "epc_knn_topk_form", "epc_knn_topk_conv1_form", "epc_knn_mask", "epc_conv1_fwd", "epc_proxyconv_block_fwd",
-    "epc_conv5_assign_fwd", "epc_vlad_aggregate_fwd", "epc_vlad_head_workspace_bytes", "epc_vlad_head_fwd",
-    "epc_conv5_maxpool_fwd", "epc_conv5_maxpool_f16_fwd", "epc_fc_head_fwd", "epc_pairwise_topk", "epc_pairwise_topk_workspace_bytes",
-    "epc_pairwise_topk_ws", "epc_net_packed_offset",
-    "epc_profile_create", "epc_profile_destroy", "epc_net_forward_profiled", "epc_profile_elapsed_ms",
-    "epc_morton_sort",
-    "epc_gemm_f32", "epc_gemm_f32_fast", "epc_gemm_bf16", "epc_gemm_splitk_det", "epc_linear_bn_bwd64", "epc_linear_bn_bwd64_ex", "epc_linear_stats64", "epc_linear_stats64_bn", "epc_bn_apply_add_fwd", "epc_neighbour_mean_diff_bwd_gather_sum", "epc_linear_smallk_fwd", "epc_linear_smallk_dw", "epc_linear_smallk_dw_partial_floats", "epc_linear_bn_bwd64_partial_floats", "epc_gemm_stats_tiles", "epc_gemm_f32_stats", "epc_gemm_f16x3_stats", "epc_gemm_bf16_stats", "epc_neighbour_mean_diff_fwd", "epc_neighbour_mean_diff_bwd_gather", "epc_bn_relu_rownorm_fwd", "epc_bn_relu_rownorm_bwd", "epc_bn_relu_rownorm_bwd_partial_floats", "epc_vlad_normalize_fwd", "epc_vlad_normalize_bwd",
-    "epc_lazy_quadruplet_loss_fwd", "epc_lazy_quadruplet_loss_bwd", "epc_colreduce_workspace_bytes", "epc_col_moments", "epc_col_sum", "epc_bn_apply_fwd", "epc_bn_apply_bwd",
-    "epc_neighbour_mean_fwd", "epc_knn_transpose", "epc_neighbour_mean_bwd_gather", "epc_rownorm_fwd", "epc_rownorm_bwd", "epc_softmax64_fwd",
-    "epc_softmax64_bwd", "epc_softmax64_bwd_bcast", "epc_cloud_colsum64_partial_floats",
-    "epc_assign_softmax_fwd", "epc_assign_softmax_bwd", "epc_gate_fwd",
-    "epc_chain_parts", "epc_chain_stats", "epc_chain_fwd_linear", "epc_chain_fwd_gather", "epc_chain_bwd_linear",
-    "epc_chain_bwd_gather", "epc_chain_sums", "epc_chain_bn_bwd", "epc_chain_dw_sum", "epc_knn_overflow_lists",
-    "epc_chain_persist_ok", "epc_chain_persist_workspace_bytes", "epc_chain_persist_init", "epc_chain_fwd_persist", "epc_chain_persist_status", "epc_chain_persist_reset",
-    "epc_vlad_df_packed_bytes", "epc_vlad_df", "epc_vlad_df_tail_partial_floats", "epc_vlad_df_tail", "epc_bn_apply_bwd_given", "epc_gate_bwd", "epc_sq_err_partial_floats", "epc_sq_err_fwd", "epc_sq_err_bwd", "epc_adam_step", "epc_adam_step_dev", "epc_ema_update", "epc_adam_multi", "epc_ema_multi", "epc_crc32c",
-    "epc_h16_conv5_fwd_scratch_bytes", "epc_h16_conv5_fwd", "epc_h16_assign_scratch_bytes", "epc_h16_assign",
-    "epc_h16_colgemm_scratch_bytes", "epc_h16_colgemm", "epc_h16_df_tail_scratch_bytes", "epc_h16_df_tail", "epc_h16_bn_bwd_apply",
-    "epc_h16_dx_scratch_bytes", "epc_h16_conv5_dx", "epc_h16_conv5_dx_bn", "epc_h16_conv5_dw_scratch_bytes", "epc_h16_conv5_dw", "epc_h16_expand", "epc_gemm_splitk_det_b16",
-    "epc_h32_conv5_fwd_scratch_bytes", "epc_h32_conv5_fwd", "epc_h32_assign_scratch_bytes", "epc_h32_assign",
-    "epc_h32_colgemm_scratch_bytes", "epc_h32_colgemm", "epc_h32_dx_scratch_bytes", "epc_h32_conv5_dx", "epc_h32_conv5_dx_bn", "epc_h32_conv5_dw_scratch_bytes", "epc_h32_conv5_dw",
-    "epc_hidden_proj_ok", "epc_hidden_proj_scratch_bytes", "epc_hidden_proj_fwd", "epc_hidden_proj_bwd",
-    "epc_maxpool_points_fwd", "epc_maxpool_points_bwd", "epc_vlad_w2_grad", "epc_group_sum_fwd", "epc_group_sum_bwd",
-    "epc_hidden_tail_ok", "epc_hidden_tail_fwd", "epc_hidden_tail_bwd",
-    "epc_bank_record_bytes", "epc_bank_store", "epc_bank_assemble",
-]
-EPC_NUM_STAGES = 10
+
+def parse_header(text: str):
+    """``(functions, constants, status)`` of the text of include/epcnet.h: ``functions[name] = (return type, [parameter
+    types])`` in header order, as C type names without ``const`` and spaces around ``*`` -- a key of ``_SCALARS``, or any
+    type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME> <integer>``; ``status``:
+    the members of ``enum epc_status``.  Raises ValueError on whatever it does not understand."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)         # extern "C" { and its }
+    constants = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(EPC_\w+)[ \t]+(.*?)[ \t]*$", text, flags=re.M)}
+    enum = re.search(r"typedef\s+enum\s+epc_status\s*\{(.*?)\}", text, flags=re.S)
+    if not enum:
+        raise ValueError("epcnet.h: no enum epc_status")
+    status = {n.strip(): int(v, 0) for n, v in (m.split("=") for m in enum.group(1).split(","))}
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"typedef\s+(struct|enum)\s+\w+\s*(\{[^{}]*\})?\s*\w+\s*;", " ", text)
+
+    def ctype(t):
+        return re.sub(r"\s*\*\s*", "*", " ".join(re.sub(r"\bconst\b", " ", t).split()))
+
+    functions = {}
+    for decl in text.split(";"):
+        if not decl.strip():
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\b(epc_\w+)\s*\((.*)\)\s*", decl, flags=re.S)
+        if not m or m.group(2) in functions:
+            raise ValueError("epcnet.h: not a declaration, or a second one of its name: %r" % " ".join(decl.split()))
+        ret, name, params = ctype(m.group(1)), m.group(2), []
+        if ret not in _SCALARS and ret != "char*":
+            raise ValueError("epcnet.h: %s: unknown return type %r" % (name, ret))
+        for p in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            pm = re.fullmatch(r"\s*(.*[\s*])\w+\s*", p, flags=re.S)                # the type, then the parameter's name
+            if not pm or (ctype(pm.group(1)) not in _SCALARS and "*" not in pm.group(1)):
+                raise ValueError("epcnet.h: %s: unknown parameter type in %r" % (name, " ".join(p.split())))
+            params.append(ctype(pm.group(1)))
+        functions[name] = (ret, params)
+    return functions, constants, status
+
+
+if not os.path.exists(HEADER_PATH):
+    raise ImportError(
+        "%s is missing: the binding is derived from the library's header (keep include/ beside the package).  "
+        "There is no second copy of the declarations." % HEADER_PATH)
+with open(HEADER_PATH) as _f:
+    _functions, _constants, _status = parse_header(_f.read())
+globals().update(_constants, **_status)     # EPC_OK, EPC_EINVAL, EPC_KNN_CAP, EPC_PRECISION_FAST, EPC_NUM_STAGES ... as module attributes
+# every symbol include/epcnet.h declares, in its order (tests check the library exports exactly these)
+EXPORTS = list(_functions)
+STATUS_NAMES = {v: n for n, v in _status.items()}
+PRECISION_IDS = {"f32": _constants["EPC_PRECISION_F32"], "fast": _constants["EPC_PRECISION_FAST"]}
 STAGE_NAMES = ["sort", "knn", "conv1", "block1", "block2", "block3", "block4", "conv5", "aggregate", "head"]
+assert len(STAGE_NAMES) == _constants["EPC_NUM_STAGES"]
 
 
 class EpcNetError(RuntimeError):
@@ -80,122 +95,7 @@ class EpcCfg(ctypes.Structure):
                 ("micro_batch", c_int32), ("precision", c_int32)]
 
 
-if not os.path.exists(LIB_PATH):
-    raise ImportError(
-        "%s is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()' or "
-        "make -C epc-net_amd/csrc).  There is no CPU fallback." % LIB_PATH)
-
-_lib = ctypes.CDLL(LIB_PATH)
-
 _P = c_void_p
-_lib.epc_last_error.restype = c_char_p
-_lib.epc_last_error.argtypes = []
-_lib.epc_version.restype = c_int
-_lib.epc_crc32c.restype = ctypes.c_uint32
-_lib.epc_crc32c.argtypes = [ctypes.c_uint32, c_void_p, c_size_t]
-_lib.epc_net_packed_bytes.restype = c_size_t
-_lib.epc_net_packed_bytes.argtypes = [POINTER(EpcCfg)]
-_lib.epc_net_packed_offset.restype = c_size_t
-_lib.epc_net_packed_offset.argtypes = [POINTER(EpcCfg), c_int]
-_lib.epc_net_pack_weights.argtypes = [POINTER(EpcCfg), POINTER(c_char_p), POINTER(_P), c_int, _P, c_size_t, _P]
-_lib.epc_net_workspace_bytes.restype = c_size_t
-_lib.epc_net_workspace_bytes.argtypes = [POINTER(EpcCfg), c_int]
-_lib.epc_net_forward.argtypes = [POINTER(EpcCfg), _P, _P, c_int, _P, _P, c_size_t, _P]
-_lib.epc_net_forward_overlapped.argtypes = [POINTER(EpcCfg), _P, _P, c_int, _P, _P, c_size_t, _P, POINTER(_P), c_int]
-_lib.epc_knn_topk.argtypes = [_P, c_int, c_int, c_int, _P, _P, _P, _P]
-_lib.epc_knn_topk_conv1.argtypes = [_P, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, _P]
-_lib.epc_knn_topk_form.argtypes = [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P]
-_lib.epc_knn_topk_conv1_form.argtypes = [_P, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P]
-_lib.epc_net_last_status.argtypes = [POINTER(EpcCfg), _P, c_int, POINTER(c_int32), _P]
-_lib.epc_knn_mask.argtypes = [_P, _P, c_int, c_int, _P, _P]
-_lib.epc_conv1_fwd.argtypes = [_P, _P, c_int, _P, _P, _P]
-_lib.epc_proxyconv_block_fwd.argtypes = [_P, _P, _P, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P,
-                                         c_int, c_int, _P, _P, _P, _P]
-_lib.epc_conv5_assign_fwd.argtypes = [_P, c_int, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]
-_lib.epc_conv5_assign_f32_fwd.argtypes = [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P]
-_lib.epc_vlad_aggregate_fwd.argtypes = [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P]
-_lib.epc_vlad_aggregate_f32_fwd.argtypes = _lib.epc_vlad_aggregate_fwd.argtypes
-_lib.epc_vlad_head_workspace_bytes.restype = c_size_t
-_lib.epc_vlad_head_workspace_bytes.argtypes = [c_int, c_int]
-_lib.epc_vlad_head_fwd.argtypes = [_P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]
-_lib.epc_conv5_maxpool_fwd.argtypes = [_P, c_int, _P, c_int, c_int, _P, _P]
-_lib.epc_conv5_maxpool_f16_fwd.argtypes = _lib.epc_conv5_maxpool_fwd.argtypes
-_lib.epc_fc_head_fwd.argtypes = [_P, _P, c_int, _P, _P, _P]
-_lib.epc_pairwise_topk.argtypes = [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P]
-_lib.epc_pairwise_topk_workspace_bytes.restype = c_size_t
-_lib.epc_pairwise_topk_workspace_bytes.argtypes = [c_int, c_int]
-_lib.epc_pairwise_topk_ws.argtypes = [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]
-_lib.epc_morton_sort.argtypes = [_P, c_int, c_int, _P, _P, _P]
-from ctypes import c_long  # noqa: E402
-_lib.epc_gemm_f32.argtypes = [_P, _P, _P, _P, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_int, c_int, c_long,
-                              c_long, c_long, c_int, c_int, _P]
-_lib.epc_gemm_f32_fast.argtypes = _lib.epc_gemm_f32.argtypes
-_lib.epc_gemm_stats_tiles.argtypes = [c_int]
-_lib.epc_gemm_f32_stats.argtypes = [_P, _P, _P, _P, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_int, _P, c_size_t, _P, _P, _P]
-_lib.epc_gemm_f16x3_stats.argtypes = [_P, _P, _P, _P, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_int, c_int, c_int, _P, c_size_t, _P, _P, _P]
-_lib.epc_gemm_bf16.argtypes = _lib.epc_gemm_f32.argtypes
-_lib.epc_gemm_bf16_stats.argtypes = _lib.epc_gemm_f32_stats.argtypes
-_lib.epc_gemm_splitk_det.argtypes = _lib.epc_gemm_f32.argtypes[:-1] + [c_int, _P, c_size_t, _P]
-_lib.epc_linear_smallk_fwd.argtypes = [_P, _P, _P, c_int, c_int, c_int, _P, _P]
-_lib.epc_linear_smallk_dw_partial_floats.restype = c_size_t
-_lib.epc_linear_smallk_dw_partial_floats.argtypes = [c_int, c_int]
-_lib.epc_linear_smallk_dw.argtypes = [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]
-_lib.epc_linear_stats64.argtypes = [_P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]
-_lib.epc_linear_stats64_bn.argtypes = [_P, _P, _P, _P, _P, c_float, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]
-_lib.epc_linear_bn_bwd64_ex.argtypes = [_P] * 12 + [c_float, c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]
-_lib.epc_bn_apply_add_fwd.argtypes = [_P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P]
-_lib.epc_neighbour_mean_diff_bwd_gather_sum.argtypes = [_P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P]
-_lib.epc_linear_bn_bwd64_partial_floats.restype = c_size_t
-_lib.epc_linear_bn_bwd64_partial_floats.argtypes = [c_int]
-_lib.epc_linear_bn_bwd64.argtypes = [_P] * 8 + [c_float, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]
-_lib.epc_bn_relu_rownorm_fwd.argtypes = [_P, _P, _P, _P, _P, c_float, c_int, c_int, _P, _P, _P]
-_lib.epc_bn_relu_rownorm_bwd_partial_floats.restype = c_size_t
-_lib.epc_bn_relu_rownorm_bwd_partial_floats.argtypes = [c_int]
-_lib.epc_bn_relu_rownorm_bwd.argtypes = [_P] * 7 + [c_float, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]
-_lib.epc_vlad_normalize_fwd.argtypes = [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]
-_lib.epc_vlad_normalize_bwd.argtypes = [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]
-_lib.epc_lazy_quadruplet_loss_fwd.argtypes = [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, _P]
-_lib.epc_lazy_quadruplet_loss_bwd.argtypes = [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]
-_lib.epc_colreduce_workspace_bytes.restype = c_size_t
-_lib.epc_colreduce_workspace_bytes.argtypes = [c_int, c_int]
-_lib.epc_col_moments.argtypes = [_P, c_int, c_int, _P, _P, _P, c_size_t, _P]
-_lib.epc_col_sum.argtypes = [_P, c_int, c_int, _P, _P, c_size_t, _P]
-_lib.epc_bn_apply_fwd.argtypes = [_P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P]
-_lib.epc_bn_apply_bwd.argtypes = [_P, _P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]
-_lib.epc_neighbour_mean_fwd.argtypes = [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]
-_lib.epc_neighbour_mean_diff_fwd.argtypes = [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]
-_lib.epc_neighbour_mean_diff_bwd_gather.argtypes = [_P, _P, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P]
-_lib.epc_knn_transpose.argtypes = [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P]
-_lib.epc_neighbour_mean_bwd_gather.argtypes = [_P, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P]
-_lib.epc_rownorm_fwd.argtypes = [_P, c_int, c_int, _P, _P, _P]
-_lib.epc_rownorm_bwd.argtypes = [_P, _P, _P, c_int, c_int, _P, _P]
-_lib.epc_softmax64_fwd.argtypes = [_P, c_int, _P, _P]
-_lib.epc_softmax64_bwd.argtypes = [_P, _P, c_int, _P, _P]
-_lib.epc_softmax64_bwd_bcast.argtypes = [_P, _P, c_int, _P, c_int, _P, _P]
-_lib.epc_cloud_colsum64_partial_floats.argtypes = [c_int]
-_lib.epc_cloud_colsum64_partial_floats.restype = ctypes.c_size_t
-_lib.epc_assign_softmax_fwd.argtypes = [_P, _P, _P, _P, _P, c_float, c_int, c_int, _P, _P, _P, ctypes.c_size_t, _P]
-_lib.epc_assign_softmax_bwd.argtypes = [_P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int, c_int, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
-_lib.epc_vlad_df_tail_partial_floats.argtypes = [c_int, c_int]
-_lib.epc_vlad_df_tail_partial_floats.restype = ctypes.c_size_t
-_lib.epc_vlad_df_tail.argtypes = [_P, _P, _P, _P, c_int, c_int, c_int, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, ctypes.c_size_t, _P]
-_lib.epc_bn_apply_bwd_given.argtypes = [_P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int, c_int, _P, _P]
-_lib.epc_gate_fwd.argtypes = [_P, _P, ctypes.c_long, _P, _P]
-_lib.epc_gate_bwd.argtypes = [_P, _P, _P, ctypes.c_long, _P, _P, _P]
-_lib.epc_hidden_tail_ok.argtypes = [c_int, c_int, c_int]
-_lib.epc_hidden_tail_fwd.argtypes = [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, c_float, c_float] + [_P] * 9 + [_P]
-_lib.epc_hidden_tail_bwd.argtypes = [_P, _P, c_int, c_int, c_int] + [_P] * 10 + [c_float, c_int] + [_P] * 7
-_lib.epc_chain_parts.argtypes = [c_int]
-_lib.epc_chain_stats.argtypes = [_P, c_int, _P, _P]
-_lib.epc_chain_fwd_linear.argtypes = [_P] * 7 + [c_float, _P, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P]
-_lib.epc_chain_fwd_gather.argtypes = [_P] * 7 + [c_float, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P]
-_lib.epc_chain_bwd_linear.argtypes = [_P, c_int] + [_P] * 5 + [c_float, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, _P] + \
-    [_P] * 6 + [c_int, c_int, _P]
-_lib.epc_chain_bwd_gather.argtypes = [_P, _P, c_int] + [_P] * 7 + [c_int, c_int, c_int] + [_P] * 5 + [c_float, _P, _P, _P]
-_lib.epc_chain_sums.argtypes = [_P, c_int] + [_P] * 5 + [c_float, c_int, _P, _P]
-_lib.epc_chain_bn_bwd.argtypes = [_P] * 6 + [c_float, _P, _P, _P, c_int, _P, _P]
-_lib.epc_chain_dw_sum.argtypes = [c_int, _P, _P, c_int, _P]
-EPC_CHAIN_MAX_BLOCKS = 4
 
 
 class ChainFwdBlock(ctypes.Structure):
@@ -207,89 +107,24 @@ class ChainFwdBlock(ctypes.Structure):
 
 class ChainFwdArgs(ctypes.Structure):
     """``struct epc_chain_fwd_args`` of include/epcnet.h."""
-    _fields_ = [("blk", ChainFwdBlock * EPC_CHAIN_MAX_BLOCKS), ("nblocks", c_int), ("xyz", _P), ("idx", _P), ("cnt", _P), ("kth", _P),
-                ("cap", c_int), ("num_clouds", c_int), ("n", c_int), ("knn", c_int), ("cat", _P), ("cat_bf16", _P), ("eps", c_float),
-                ("workspace", _P), ("spin_ticks", ctypes.c_longlong)]
+    _fields_ = [("blk", ChainFwdBlock * _constants["EPC_CHAIN_MAX_BLOCKS"]), ("nblocks", c_int), ("xyz", _P), ("idx", _P), ("cnt", _P),
+                ("kth", _P), ("cap", c_int), ("num_clouds", c_int), ("n", c_int), ("knn", c_int), ("cat", _P), ("cat_bf16", _P),
+                ("eps", c_float), ("workspace", _P), ("spin_ticks", ctypes.c_longlong)]
 
 
-_lib.epc_chain_persist_ok.argtypes = [c_int]
-_lib.epc_chain_persist_workspace_bytes.restype = c_size_t
-_lib.epc_chain_persist_workspace_bytes.argtypes = []
-_lib.epc_chain_persist_init.argtypes = [_P, _P]
-_lib.epc_chain_fwd_persist.argtypes = [POINTER(ChainFwdArgs), c_int, _P]
-_lib.epc_chain_persist_status.argtypes = [_P, _P]
-_lib.epc_chain_persist_reset.argtypes = [_P, _P]
-_lib.epc_knn_overflow_lists.argtypes = [_P, c_int, c_int, c_int, _P, _P, _P]
-_lib.epc_vlad_df_packed_bytes.restype = c_size_t
-_lib.epc_vlad_df_packed_bytes.argtypes = [c_int, c_int]
-_lib.epc_vlad_df.argtypes = [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P, _P]
-_lib.epc_sq_err_partial_floats.restype = c_size_t
-_lib.epc_sq_err_partial_floats.argtypes = [c_long]
-_lib.epc_sq_err_fwd.argtypes = [_P, _P, c_long, c_int, _P, _P, c_size_t, _P]
-_lib.epc_sq_err_bwd.argtypes = [_P, _P, c_long, c_int, _P, _P, _P]
-_lib.epc_adam_step.argtypes = [_P, _P, _P, _P, c_long, c_float, c_float, c_float, c_float, c_int, _P]
-_lib.epc_adam_step_dev.argtypes = [_P, _P, _P, _P, c_long, _P, c_float, c_float, c_float, _P]
-_lib.epc_ema_update.argtypes = [_P, _P, c_long, c_float, _P, _P]
-_lib.epc_adam_multi.argtypes = [c_int, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_int, _P, _P]
-_lib.epc_ema_multi.argtypes = [c_int, _P, _P, _P, _P, c_float, c_float, _P, _P]
-_lib.epc_h16_conv5_fwd_scratch_bytes.restype = c_size_t
-_lib.epc_h16_conv5_fwd_scratch_bytes.argtypes = [c_int]
-_lib.epc_h16_conv5_fwd.argtypes = [_P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]
-_lib.epc_h16_assign_scratch_bytes.restype = c_size_t
-_lib.epc_h16_assign_scratch_bytes.argtypes = [c_int, c_int, c_int]
-_lib.epc_h16_assign.argtypes = [_P, _P, _P, _P, _P, c_float, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]
-_lib.epc_h16_colgemm_scratch_bytes.restype = c_size_t
-_lib.epc_h16_colgemm_scratch_bytes.argtypes = [c_int, c_int]
-_lib.epc_h16_colgemm.argtypes = [_P, _P, _P, _P, _P, c_float, _P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]
-_lib.epc_h16_df_tail_scratch_bytes.restype = c_size_t
-_lib.epc_h16_df_tail_scratch_bytes.argtypes = [c_int, c_int]
-_lib.epc_h16_df_tail.argtypes = [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, c_size_t, _P]
-_lib.epc_h16_bn_bwd_apply.argtypes = [_P, _P, _P, _P, _P, _P, c_float, _P, _P, c_int, _P, _P]
-_lib.epc_h16_dx_scratch_bytes.restype = c_size_t
-_lib.epc_h16_dx_scratch_bytes.argtypes = []
-_lib.epc_h16_conv5_dx.argtypes = [_P, _P, c_int, _P, _P, c_size_t, _P]
-_lib.epc_h16_conv5_dx_bn.argtypes = [_P, _P, _P, _P, _P, c_float, _P, _P, _P, c_int, _P, _P, _P, c_size_t, _P]
-_lib.epc_h16_conv5_dw_scratch_bytes.restype = c_size_t
-_lib.epc_h16_conv5_dw_scratch_bytes.argtypes = [c_int]
-_lib.epc_h16_conv5_dw.argtypes = [_P, c_int, _P, c_int, _P, _P, c_size_t, _P]
-_lib.epc_h16_expand.argtypes = [_P, _P, _P, _P, _P, c_float, _P, c_int, _P, _P]
-_lib.epc_gemm_splitk_det_b16.argtypes = _lib.epc_gemm_splitk_det.argtypes
-_lib.epc_h32_conv5_fwd_scratch_bytes.restype = c_size_t
-_lib.epc_h32_conv5_fwd_scratch_bytes.argtypes = [c_int]
-_lib.epc_h32_conv5_fwd.argtypes = [_P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]
-_lib.epc_h32_assign_scratch_bytes.restype = c_size_t
-_lib.epc_h32_assign_scratch_bytes.argtypes = [c_int, c_int, c_int]
-_lib.epc_h32_assign.argtypes = _lib.epc_h16_assign.argtypes
-_lib.epc_h32_colgemm_scratch_bytes.restype = c_size_t
-_lib.epc_h32_colgemm_scratch_bytes.argtypes = [c_int, c_int]
-_lib.epc_h32_colgemm.argtypes = _lib.epc_h16_colgemm.argtypes
-_lib.epc_h32_dx_scratch_bytes.restype = c_size_t
-_lib.epc_h32_dx_scratch_bytes.argtypes = []
-_lib.epc_h32_conv5_dx.argtypes = _lib.epc_h16_conv5_dx.argtypes
-_lib.epc_h32_conv5_dx_bn.argtypes = _lib.epc_h16_conv5_dx_bn.argtypes
-_lib.epc_h32_conv5_dw_scratch_bytes.restype = c_size_t
-_lib.epc_h32_conv5_dw_scratch_bytes.argtypes = [c_int]
-_lib.epc_h32_conv5_dw.argtypes = [_P, _P, c_int, _P, _P, c_size_t, _P]
-_lib.epc_hidden_proj_ok.argtypes = [c_int, c_int, c_int]
-_lib.epc_hidden_proj_scratch_bytes.restype = c_size_t
-_lib.epc_hidden_proj_scratch_bytes.argtypes = [c_int, c_int]
-_lib.epc_hidden_proj_fwd.argtypes = [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]
-_lib.epc_hidden_proj_bwd.argtypes = [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P]
-_lib.epc_maxpool_points_fwd.argtypes = [_P, c_int, c_int, c_int, _P, _P, _P]
-_lib.epc_maxpool_points_bwd.argtypes = [_P, _P, c_int, c_int, c_int, _P, _P]
-_lib.epc_vlad_w2_grad.argtypes = [_P, _P, c_int, c_int, c_int, _P, _P]
-_lib.epc_group_sum_fwd.argtypes = [_P, c_int, c_int, c_int, _P, _P]
-_lib.epc_group_sum_bwd.argtypes = [_P, c_int, c_int, c_int, _P, _P]
-_lib.epc_bank_record_bytes.restype = c_size_t
-_lib.epc_bank_record_bytes.argtypes = [c_int, c_int]
-_lib.epc_bank_store.argtypes = [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
-_lib.epc_bank_assemble.argtypes = [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
-_lib.epc_profile_create.argtypes = [POINTER(_P)]
-_lib.epc_profile_destroy.argtypes = [_P]
-_lib.epc_net_forward_profiled.argtypes = [POINTER(EpcCfg), _P, _P, c_int, _P, _P, c_size_t, _P, _P]
-_lib.epc_profile_elapsed_ms.argtypes = [_P, POINTER(c_float)]
-for _name in EXPORTS:
-    getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
+if not os.path.exists(LIB_PATH):
+    raise ImportError(
+        "%s is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()' or "
+        "make -C epc-net_amd/csrc).  There is no CPU fallback." % LIB_PATH)
+
+_lib = ctypes.CDLL(LIB_PATH)
+
+# a pointer to a structure mirrored above keeps its type check; every other pointer is a void*
+_POINTERS = {"epc_cfg*": POINTER(EpcCfg), "epc_chain_fwd_args*": POINTER(ChainFwdArgs)}
+for _name, (_ret, _params) in _functions.items():
+    _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
+    _fn.restype = c_char_p if _ret == "char*" else _SCALARS[_ret]
+    _fn.argtypes = [_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
 
 
 def lib() -> ctypes.CDLL:
@@ -297,7 +132,7 @@ def lib() -> ctypes.CDLL:
 
 
 def check(status: int) -> None:
-    if status != EPC_OK:
+    if status != _status["EPC_OK"]:
         raise EpcNetError(status, (_lib.epc_last_error() or b"").decode("utf-8", "replace"))
 
 
@@ -314,7 +149,7 @@ def ptr(t) -> int:
 
 def micro_batch_of(cfg: "EpcCfg", num_clouds: int) -> int:
     """Clouds per internal pass (mirrors micro_batch() of csrc/pipeline.hip)."""
-    mb = cfg.micro_batch if cfg.micro_batch > 0 else (64 if cfg.arch == EPC_ARCH_EPC_NET else 256)
+    mb = cfg.micro_batch if cfg.micro_batch > 0 else (64 if cfg.arch == _constants["EPC_ARCH_EPC_NET"] else 256)
     return max(1, min(int(num_clouds), int(mb)))
 
 

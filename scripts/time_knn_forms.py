@@ -1,11 +1,10 @@
 """GPU box: epc_knn_topk in its one-lane and four-lane forms (epc_knn_topk_form) at several batch sizes of Hilbert-ordered
 4096-point clouds; checks that the two forms write identical outputs."""
-import ctypes, os, sys, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-lib = ctypes.CDLL(os.environ.get("EPCNET_LIB") or os.path.join(ROOT, "epc-net_amd", "libepcnet_hip.so"))
-P = ctypes.c_void_p
-lib.epc_knn_topk_form.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P, ctypes.c_int, P]
-lib.epc_morton_sort.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P, P]
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import bench
+lib = bench.pkg("lib").lib()
 dev = torch.device("cuda:0")
 N = 4096
 st = torch.cuda.current_stream().cuda_stream

@@ -36,6 +36,89 @@ def test_library_exports_every_declared_symbol():
     assert "split-fp16" in header and "3-byte" in header and "epc_net_forward_status" not in header
 
 
+def test_built_library_defines_exactly_the_declared_symbols():
+    """What DESIGN.md states: the header's declarations = the unmangled `T epc_*` symbols `nm -D` shows of the built library."""
+    import subprocess
+    L = H.pkg("lib")
+    rocm_bin = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path=rocm_bin)
+    assert nm, "neither nm nor llvm-nm found"
+    out = subprocess.run([nm, "-D", "--defined-only", L.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    defined = re.findall(r"^[0-9a-f]+ T (epc_\w+)$", out, flags=re.M)
+    assert len(defined) == len(set(defined)) == len(L.EXPORTS)
+    assert set(defined) == set(L.EXPORTS), set(defined) ^ set(L.EXPORTS)
+
+
+def test_binding_signatures_match_the_header():
+    """restype / argtypes as lib.py derived them from include/epcnet.h, against expectations typed here from READING the header:
+    one entry per class of type (a wrong width truncates silently: a c_int for the GEMM's `long` strides, a missing restype on a
+    `size_t ..._bytes` function)."""
+    from ctypes import POINTER, c_char_p, c_float, c_int, c_long, c_size_t, c_uint32, c_void_p
+    L = H.pkg("lib")
+    P, i, l, f = c_void_p, c_int, c_long, c_float
+    want = {
+        "epc_last_error": (c_char_p, []),                                             # const char* epc_last_error(void)
+        "epc_crc32c": (c_uint32, [c_uint32, P, c_size_t]),
+        "epc_gemm_f32": (i, [P, P, P, P, i, i, i, l, l, l, l, i, i, l, l, l, i, i, P]),   # sAm sAk sBk sBn .. bA bB bC are long
+        "epc_sq_err_partial_floats": (c_size_t, [l]),
+        "epc_net_forward": (i, [POINTER(L.EpcCfg), P, P, i, P, P, c_size_t, P]),
+        "epc_hidden_tail_fwd": (i, [P, i, i, i, P, P, P, P, P, f, f, f, P, P, P, P, P, P, P, P, P, P]),   # eps, bessel1, bessel2
+        "epc_chain_fwd_persist": (i, [POINTER(L.ChainFwdArgs), i, P]),
+        "epc_chain_persist_workspace_bytes": (c_size_t, []),                          # (void)
+        "epc_adam_multi": (i, [i, P, P, P, P, P, f, f, f, f, i, P, P]),               # float* const* w ... const long* n
+    }
+    for name, (restype, argtypes) in want.items():
+        fn = getattr(L.lib(), name)
+        assert fn.restype == restype, (name, fn.restype)
+        assert list(fn.argtypes) == argtypes, (name, fn.argtypes)
+    for name in L.EXPORTS:                                                            # nothing is left at ctypes' defaults
+        assert getattr(L.lib(), name).argtypes is not None and getattr(L.lib(), name).restype is not None, name
+
+
+def test_header_reader_refuses_what_it_does_not_understand():
+    L = H.pkg("lib")
+    enum = "typedef enum epc_status { EPC_OK = 0, EPC_EINVAL = -1 } epc_status;\n#define EPC_KNN_CAP 32 /* slots */\n"
+    good = enum + "int epc_a(const float* x, long n, void* stream);\nsize_t epc_b(void); /* bytes */\n"
+    functions, constants, status = L.parse_header(good)
+    assert functions == {"epc_a": ("int", ["float*", "long", "void*"]), "epc_b": ("size_t", [])}
+    assert list(functions) == ["epc_a", "epc_b"] and constants == {"EPC_KNN_CAP": 32} and status == {"EPC_OK": 0, "EPC_EINVAL": -1}
+    for bad in (good.replace("long n", "double n"),                  # an unknown parameter type
+                good.replace("long n", "long"),                      # a parameter without a name
+                good.replace("size_t epc_b", "ssize_t epc_b"),       # an unknown return type
+                good.replace("size_t epc_b", "stray size_t epc_b"),  # text between two declarations
+                good.replace("size_t epc_b", "stray; size_t epc_b"),
+                good + "int epc_a(int n);\n",                        # one name, two declarations
+                good.replace("32", "(32)"),                          # a constant that is not an integer literal
+                good + "}\n"):                                       # text after the last declaration
+        with pytest.raises(ValueError):
+            L.parse_header(bad)
+
+
+def test_mirrored_struct_layouts_match_the_compiler(tmp_path):
+    """EpcCfg, ChainFwdBlock and ChainFwdArgs of lib.py against sizeof / offsetof of include/epcnet.h's structs as gcc lays them out
+    (a field name the header does not have fails to compile)."""
+    import ctypes
+    import subprocess
+    L = H.pkg("lib")
+    structs = (("epc_cfg", L.EpcCfg), ("epc_chain_fwd_block", L.ChainFwdBlock), ("epc_chain_fwd_args", L.ChainFwdArgs))
+    lines = ['#include <stdio.h>', '#include "epcnet.h"', "int main(void) {"]
+    for cname, cls in structs:
+        lines.append('    printf("%%zu\\n", sizeof(%s));' % cname)
+        lines += ['    printf("%%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (cname, f[0], cname, f[0]) for f in cls._fields_]
+    (tmp_path / "layout.c").write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o",
+                        str(tmp_path / "layout")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.split("\n")
+    want = []
+    for _, cls in structs:
+        want.append("%d" % ctypes.sizeof(cls))
+        want += ["%d %d" % (getattr(cls, f[0]).offset, getattr(cls, f[0]).size) for f in cls._fields_]
+    assert got == want + [""]
+    assert len(L.ChainFwdBlock._fields_) == 24 and len(L.ChainFwdArgs._fields_) == 15      # every member of the header's structs is mirrored
+    assert ctypes.sizeof(L.ChainFwdArgs) == (4 * 24 + 12) * 8                            # 96 block pointers + 12 eight-byte slots
+
+
 def test_cfg_struct_layout_and_sizes():
     import ctypes
     L, E = H.pkg("lib"), H.pkg("engine")
