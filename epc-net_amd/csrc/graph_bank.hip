@@ -8,6 +8,7 @@
 //   epc_bank_store          what epc_morton_sort -> epc_knn_topk -> epc_knn_transpose + epc_knn_overflow_lists leave for a batch of
 //                           clouds -> records (16-bit cloud-local indices; refused, never truncated, when a value does not fit)
 //   epc_bank_assemble       ids (device) -> the batch tensors in exactly the layout the training kernels read (32-bit, re-based)
+//   epc_bank_gather_infer   ids (device) -> what the inference pipeline holds after its sort and kNN launches (16-bit lists as stored)
 //
 // Record of a cloud of n points, cap slots per list (n % 8 == 0, cap % 8 == 0), in 16-byte chunks, every section 16-byte aligned:
 //   chunk 0           int32 {ovf_cnt, rlist_used, n, cap}
@@ -166,6 +167,67 @@ __global__ __launch_bounds__(BANK_THREADS) void bank_assemble_kernel(const uint4
     }
 }
 
+// ---- gather for inference: grid (slabs, T); the sections the inference pipeline reads, as they are stored ------------------------------
+// sorted xyz, kth, cnt and the u16 neighbour lists of record ids[t] -> slot t of the inference workspace: 5 n / 4 + n cap / 8 chunks per
+// cloud, each read once and written once (4096 points at cap = 32: 344 KB each way, against ~0.55 MB in and ~1.0 MB out of the assemble
+// kernel: no rdeg / roff / rlist / ovf, nothing widened).  The workgroups (0, t) additionally form slot t's status word from the record's
+// coordinates with the test the kNN kernel applies to them ((x x + y y) + z z finite), so the word is written whole by one thread: no
+// atomics, and the conv1 launch that follows may OR its EPC_STATUS_FP16_RANGE into it.
+__global__ __launch_bounds__(BANK_THREADS) void bank_gather_infer_kernel(const uint4* __restrict__ bank, long rec_chunks, int num_records,
+                                                                         const int32_t* __restrict__ ids, int n, int cap,
+                                                                         float* __restrict__ xyz, float* __restrict__ kth,
+                                                                         int32_t* __restrict__ cnt, unsigned short* __restrict__ idx,
+                                                                         int32_t* __restrict__ status) {
+    const int t = blockIdx.y;
+    const int id = ids[t];
+    const BankLayout L = bank_layout(n, cap);
+    const uint4* __restrict__ rec = bank + (size_t)(id < 0 || id >= num_records ? 0 : id) * rec_chunks;
+    bool bad = id < 0 || id >= num_records;
+    if (!bad) {   // a record of another shape (a bank built for other clouds) is no record of this call either
+        const int4 head = *reinterpret_cast<const int4*>(rec);
+        bad = head.z != n || head.w != cap;
+    }
+    const size_t row0 = (size_t)t * n;
+    const unsigned q4 = (unsigned)n / 4, low = 5 * q4, total = low + (L.rlist - L.idx);
+    const unsigned stride = gridDim.x * BANK_THREADS;
+    uint4* __restrict__ dx = reinterpret_cast<uint4*>(xyz + row0 * 3);
+    uint4* __restrict__ dk = reinterpret_cast<uint4*>(kth + row0);
+    uint4* __restrict__ dc = reinterpret_cast<uint4*>(cnt + row0);
+    uint4* __restrict__ di = reinterpret_cast<uint4*>(idx + row0 * cap);
+    if (bad) {
+        // no record is read: NaN coordinates, an empty graph whose every list entry is row 0, and the status of a non-finite cloud
+        const unsigned qn = 0x7fc00000u;
+        for (unsigned p = blockIdx.x * BANK_THREADS + threadIdx.x; p < total; p += stride) {
+            if (p < 3 * q4) dx[p] = make_uint4(qn, qn, qn, qn);
+            else if (p < 4 * q4) dk[p - 3 * q4] = make_uint4(0, 0, 0, 0);
+            else if (p < low) dc[p - 4 * q4] = make_uint4(0, 0, 0, 0);
+            else di[p - low] = make_uint4(0, 0, 0, 0);
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) status[t] = EPC_STATUS_NONFINITE_INPUT;
+        return;
+    }
+    for (unsigned p = blockIdx.x * BANK_THREADS + threadIdx.x; p < total; p += stride) {
+        if (p < 3 * q4) dx[p] = rec[L.xyz + p];
+        else if (p < 4 * q4) dk[p - 3 * q4] = rec[L.kth + (p - 3 * q4)];
+        else if (p < low) dc[p - 4 * q4] = rec[L.cnt + (p - 4 * q4)];
+        else di[p - low] = rec[L.idx + (p - low)];
+    }
+    if (blockIdx.x == 0) {
+        // thread u takes the points 4 u .. 4 u + 3 (three chunks), + 1024, ...
+        bool nonfinite = false;
+        for (unsigned u = threadIdx.x; u < q4; u += BANK_THREADS) {
+            const uint4 a = rec[L.xyz + 3 * u], b = rec[L.xyz + 3 * u + 1], c = rec[L.xyz + 3 * u + 2];
+            const float f[12] = {__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w),
+                                 __uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w),
+                                 __uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z), __uint_as_float(c.w)};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) nonfinite |= !(sq3(f[3 * j], f[3 * j + 1], f[3 * j + 2]) <= 3.4028234664e38f);
+        }
+        const int any = __syncthreads_or(nonfinite);
+        if (threadIdx.x == 0) status[t] = any ? EPC_STATUS_NONFINITE_INPUT : 0;
+    }
+}
+
 // ---- store, pass 1: does every meaningful value of the batch fit its record?  status[0] = 1 otherwise (plain stores of one value) ------
 // Checked per cloud c: cnt in [0, n]; the first min(cnt, cap) entries of every idx row in [0, n); the transposed lists PACKED in point
 // order inside the cloud's segment as epc_knn_transpose leaves them (roff[0] = c n cap, roff[j + 1] = roff[j] + rdeg[j], rdeg >= 0, the
@@ -320,6 +382,22 @@ extern "C" int epc_bank_assemble(const void* bank, int num_records, const int32_
     const BankLayout L = bank_layout(n, cap);
     hipLaunchKernelGGL(bank_assemble_kernel, dim3(bank_slabs(num_ids, L.end), (unsigned)num_ids), dim3(BANK_THREADS), 0,
                        (hipStream_t)stream, reinterpret_cast<const uint4*>(bank), (long)L.end, num_records, ids, n, cap, o, status, poison);
+    EPC_CHECK_LAUNCH();
+    return EPC_OK;
+}
+
+extern "C" int epc_bank_gather_infer(const void* bank, int num_records, const int32_t* ids, int num_ids, int n, int cap, float* xyz,
+                                     float* kth, int32_t* cnt, void* idx_u16, int32_t* status, void* stream) {
+    EPC_CHECK_ARG(bank_shape_ok(n, cap), "unsupported record shape (n a multiple of 8 in [8, 65536], cap a multiple of 8 in [20, 64])");
+    EPC_CHECK_ARG(bank && ids && status && epc_aligned16(bank) && num_records > 0, "null / unaligned bank, ids or status");
+    EPC_CHECK_ARG(num_ids > 0 && num_ids <= 65535, "bad number of ids");
+    EPC_CHECK_ARG(xyz && kth && cnt && idx_u16 && epc_aligned16(xyz) && epc_aligned16(kth) && epc_aligned16(cnt) && epc_aligned16(idx_u16),
+                  "null / unaligned tensor");
+    const BankLayout L = bank_layout(n, cap);
+    const unsigned moved = 5 * ((unsigned)n / 4) + (L.rlist - L.idx);
+    hipLaunchKernelGGL(bank_gather_infer_kernel, dim3(bank_slabs(num_ids, moved), (unsigned)num_ids), dim3(BANK_THREADS), 0,
+                       (hipStream_t)stream, reinterpret_cast<const uint4*>(bank), (long)L.end, num_records, ids, n, cap, xyz, kth, cnt,
+                       reinterpret_cast<unsigned short*>(idx_u16), status);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
 }

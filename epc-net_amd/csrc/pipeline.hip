@@ -133,21 +133,39 @@ static int mark(epc_profile* prof, int boundary, void* stream) {
     return EPC_OK;
 }
 
+// The pointers into the workspace that both halves of a pass use
+struct PassBufs {
+    int32_t *idx, *cnt, *status;
+    float *kth, *cat;
+    float* xs[2];
+    void* xs16[2];
+    bool f16;
+};
+
+static PassBufs pass_bufs(const epc_cfg* cfg, char* ws, const WsLayout& w) {
+    PassBufs b;
+    b.idx = (int32_t*)(ws + w.idx);
+    b.cnt = (int32_t*)(ws + w.cnt);
+    b.kth = (float*)(ws + w.kth);
+    b.status = (int32_t*)(ws + w.status);
+    b.cat = (float*)(ws + w.cat);
+    b.f16 = fast_path(cfg);
+    b.xs[0] = b.f16 ? nullptr : (float*)(ws + w.xa);
+    b.xs[1] = b.f16 ? nullptr : (float*)(ws + w.xb);
+    b.xs16[0] = b.f16 ? (void*)(ws + w.xa16) : nullptr;
+    b.xs16[1] = b.f16 ? (void*)(ws + w.xb16) : nullptr;
+    return b;
+}
+
+static int forward_tail(const epc_cfg* cfg, const char* pk, const float* pc, int idx_u16, int nc, float* o, char* ws, const WsLayout& w,
+                        void* stream, epc_profile* prof);
+
 // One pass: xyz of `nc` <= micro_batch clouds -> descriptors, every launch on `stream`, every intermediate in `ws`.
 static int forward_pass(const epc_cfg* cfg, const char* pk, const float* pc, int nc, float* o, char* ws,
                         const WsLayout& w, void* stream, epc_profile* prof) {
     const int n = cfg->num_points;
-    const int nblocks = cfg->arch == EPC_ARCH_EPC_NET ? 4 : 2;
-    const int ccat = 64 * nblocks;
-    int32_t* idx = (int32_t*)(ws + w.idx);
-    int32_t* cnt = (int32_t*)(ws + w.cnt);
-    float* kth = (float*)(ws + w.kth);
-    float* xs[2] = {(float*)(ws + w.xa), (float*)(ws + w.xb)};
-    const bool f16 = fast_path(cfg);
-    int32_t* status = (int32_t*)(ws + w.status);
-    void* xs16[2] = {f16 ? (void*)(ws + w.xa16) : nullptr, f16 ? (void*)(ws + w.xb16) : nullptr};
-    if (f16) xs[0] = xs[1] = nullptr;
-    float* cat = (float*)(ws + w.cat);
+    const PassBufs b = pass_bufs(cfg, ws, w);
+    int32_t* status = b.status;
 
     TRY(mark(prof, EPC_STAGE_SORT, stream));
     if (n <= 16384) {  // descriptors are permutation-invariant: run the whole pipeline on the Z-ordered cloud
@@ -165,8 +183,25 @@ static int forward_pass(const epc_cfg* cfg, const char* pk, const float* pc, int
     // kNN graph + conv1 in one launch (the kNN workgroup already holds the cloud in LDS); a stage profile therefore
     // reports conv1 inside the kNN stage
     const int idx_u16 = n <= 8192;   // 2-byte neighbour lists wherever the LDS kNN kernel runs
-    TRY(epc_knn_topk_conv1(pc, nc, n, EPC_KNN_CAP, idx, idx_u16, cnt, kth, pk + epc_net_packed_offset(cfg, 0), xs[0], xs16[0],
+    TRY(epc_knn_topk_conv1(pc, nc, n, EPC_KNN_CAP, b.idx, idx_u16, b.cnt, b.kth, pk + epc_net_packed_offset(cfg, 0), b.xs[0], b.xs16[0],
                            status, stream));
+    return forward_tail(cfg, pk, pc, idx_u16, nc, o, ws, w, stream, prof);
+}
+
+// The rest of a pass, from the point where the workspace holds the (sorted) cloud `pc`, its graph (idx, cnt, kth), conv1's rows and
+// the status words: the blocks, conv5, aggregate / max-pool and the head.  ONE definition for every way the graph got there
+// (forward_pass: sort + kNN; epc_net_forward_bank: the records of a cloud bank).
+static int forward_tail(const epc_cfg* cfg, const char* pk, const float* pc, int idx_u16, int nc, float* o, char* ws, const WsLayout& w,
+                        void* stream, epc_profile* prof) {
+    const int n = cfg->num_points;
+    const int nblocks = cfg->arch == EPC_ARCH_EPC_NET ? 4 : 2;
+    const int ccat = 64 * nblocks;
+    const PassBufs pb = pass_bufs(cfg, ws, w);
+    int32_t *idx = pb.idx, *cnt = pb.cnt, *status = pb.status;
+    float *kth = pb.kth, *cat = pb.cat;
+    float* const* xs = pb.xs;
+    void* const* xs16 = pb.xs16;
+    const bool f16 = pb.f16;
     for (int b = 1; b <= nblocks; ++b) {
         TRY(mark(prof, EPC_STAGE_BLOCK1 + b - 1, stream));
         const int has_next = b < nblocks;
@@ -254,6 +289,39 @@ extern "C" int epc_net_forward_profiled(const epc_cfg* cfg, const void* packed, 
         const int nc = (num_clouds - c0) < mb ? (num_clouds - c0) : mb;
         TRY(forward_pass(cfg, (const char*)packed, xyz + (size_t)c0 * n * 3, nc, out + (size_t)c0 * cfg->output_dim,
                          (char*)workspace, w, stream, prof));
+    }
+    return EPC_OK;
+}
+
+// Inference from the records of a cloud bank (csrc/graph_bank.hip): per pass ONE gather launch puts the sorted clouds, their graphs
+// and the status words where sort + kNN would have left them, conv1 runs as its standalone launch (the same conv1_quad, the same
+// range test), and the pass continues with forward_tail.
+extern "C" int epc_net_forward_bank(const epc_cfg* cfg, const void* packed, const void* bank, int num_records, int bank_n, int bank_cap,
+                                    const int32_t* ids, int num_ids, float* out, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    EPC_CHECK_ARG(epc_net_packed_bytes(cfg) != 0, "unsupported configuration");
+    EPC_CHECK_ARG(packed && bank && ids && out, "null pointer");
+    EPC_CHECK_ARG(num_ids >= 0 && num_records > 0, "bad shape");
+    EPC_CHECK_ARG(cfg->num_points == bank_n, "the bank's records hold clouds of another size than cfg->num_points");
+    EPC_CHECK_ARG(bank_n <= 8192 && bank_cap == EPC_KNN_CAP && epc_bank_record_bytes(bank_n, bank_cap) != 0,
+                  "records of at most 8192 points with EPC_KNN_CAP list slots");
+    if (num_ids == 0) return EPC_OK;
+    const int mb = micro_batch(cfg, num_ids);
+    const WsLayout w = ws_layout(cfg, mb);
+    if (!workspace || workspace_bytes < w.total) {
+        epc_set_error("epc_net_forward_bank: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+        return EPC_ENOMEM;
+    }
+    const int n = cfg->num_points;
+    const char* pk = (const char*)packed;
+    char* ws = (char*)workspace;
+    const PassBufs b = pass_bufs(cfg, ws, w);
+    float* sorted = (float*)(ws + w.sorted);
+    for (int c0 = 0; c0 < num_ids; c0 += mb) {
+        const int nc = (num_ids - c0) < mb ? (num_ids - c0) : mb;
+        TRY(epc_bank_gather_infer(bank, num_records, ids + c0, nc, n, EPC_KNN_CAP, sorted, b.kth, b.cnt, b.idx, b.status, stream));
+        TRY(epc_conv1_launch(sorted, pk + epc_net_packed_offset(cfg, 0), nc * n, b.xs[0], b.xs16[0], b.status, n, stream));
+        TRY(forward_tail(cfg, pk, sorted, 1, nc, out + (size_t)c0 * cfg->output_dim, ws, w, stream, nullptr));
     }
     return EPC_OK;
 }

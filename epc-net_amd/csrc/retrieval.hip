@@ -13,6 +13,61 @@
 // k-nearest list.  Database sizes on this path are 10^2..10^4 rows (Oxford runs hold ~400 submaps each).
 #include "train_common.h"
 
+// exact squared distance sum_c (q_c - d_c)^2: sequential over c, one rounding per operation.  ONE definition for every kernel under the
+// bit-for-bit contract of epc_pairwise_topk (the first form, the re-rank and the fallback of the workspace form, the mining distances)
+__device__ __forceinline__ float exact_d2(const float* __restrict__ q, const float* __restrict__ row, int dim) {
+    float acc = 0.f;
+    for (int c = 0; c < dim; c += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(row + c);
+        const float4 u = *reinterpret_cast<const float4*>(q + c);
+        const float e0 = u.x - v.x, e1 = u.y - v.y, e2 = u.z - v.z, e3 = u.w - v.w;
+        acc += e0 * e0;
+        acc += e1 * e1;
+        acc += e2 * e2;
+        acc += e3 * e3;
+    }
+    return acc;
+}
+
+// lexicographic (value, index) minimum over the wave
+__device__ __forceinline__ void wave_argmin(float& best, int& bi) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ov < best || (ov == best && oi < bi)) {
+            best = ov;
+            bi = oi;
+        }
+    }
+}
+
+// One wave: the k smallest of the `num` squared distances d2 (LDS; consumed) in ascending (value, position) order -> idx, dist of one
+// query.  Fewer than k entries at a finite distance (NaN / Inf query or rows -- the descriptors of flagged clouds -- or num < k): no such
+// neighbour, index -1 at distance +Inf.  `map` (optional): mapped[r] = map[idx[r]], -1 where idx[r] is -1 (the mining form's row ids).
+__device__ __forceinline__ void topk_rounds(float* d2, int num, int k, int lane, int32_t* __restrict__ idx, float* __restrict__ dist,
+                                            const int32_t* __restrict__ map, int32_t* __restrict__ mapped) {
+    for (int r = 0; r < k; ++r) {
+        float best = INFINITY;
+        int bi = 0x7fffffff;
+        for (int d = lane; d < num; d += 64) {
+            const float v = d2[d];
+            if (v < best) {  // ascending d within a lane: strict < keeps the lower index on ties
+                best = v;
+                bi = d;
+            }
+        }
+        wave_argmin(best, bi);
+        if (lane == 0) {
+            idx[r] = bi < num ? bi : -1;
+            dist[r] = sqrtf(best);
+            if (map) mapped[r] = bi < num ? map[bi] : -1;
+            if (bi < num) d2[bi] = INFINITY;
+        }
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(64) void pairwise_topk_kernel(const float* __restrict__ db, int num_db,
                                                            const float* __restrict__ queries, int dim, int k,
                                                            int32_t* __restrict__ idx, float* __restrict__ dist) {
@@ -24,47 +79,11 @@ __global__ __launch_bounds__(64) void pairwise_topk_kernel(const float* __restri
     for (int c = lane; c < dim; c += 64) qv[c] = queries[(size_t)qi * dim + c];
     __syncthreads();
     for (int d = lane; d < num_db; d += 64) {
-        const float* row = db + (size_t)d * dim;
-        float acc = 0.f;
-        for (int c = 0; c < dim; c += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(row + c);
-            const float e0 = qv[c] - v.x, e1 = qv[c + 1] - v.y, e2 = qv[c + 2] - v.z, e3 = qv[c + 3] - v.w;
-            acc += e0 * e0;
-            acc += e1 * e1;
-            acc += e2 * e2;
-            acc += e3 * e3;
-        }
+        const float acc = exact_d2(qv, db + (size_t)d * dim, dim);
         d2[d] = acc <= 3.0e38f ? acc : INFINITY;   // NaN / overflow: never selected
     }
     __syncthreads();
-    for (int r = 0; r < k; ++r) {
-        float best = INFINITY;
-        int bi = 0x7fffffff;
-        for (int d = lane; d < num_db; d += 64) {
-            const float v = d2[d];
-            if (v < best) {  // ascending d within a lane: strict < keeps the lower index on ties
-                best = v;
-                bi = d;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float ov = __shfl_xor(best, off);
-            const int oi = __shfl_xor(bi, off);
-            if (ov < best || (ov == best && oi < bi)) {
-                best = ov;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            // fewer than k rows at a finite distance (NaN / Inf query or database rows -- the descriptors of flagged clouds):
-            // no such neighbour, index -1 at distance +Inf
-            idx[(size_t)qi * k + r] = bi < num_db ? bi : -1;
-            dist[(size_t)qi * k + r] = sqrtf(best);
-            if (bi < num_db) d2[bi] = INFINITY;
-        }
-        __syncthreads();
-    }
+    topk_rounds(d2, num_db, k, lane, idx + (size_t)qi * k, dist + (size_t)qi * k, nullptr, nullptr);
 }
 
 extern "C" int epc_pairwise_topk(const float* database, int num_db, const float* queries, int num_q, int dim,
@@ -152,34 +171,6 @@ __global__ __launch_bounds__(256) void pairdist_gemm_kernel(const float* __restr
                 }
             }
         }
-}
-
-// exact squared distance, the arithmetic of pairwise_topk_kernel (sequential over c, one rounding per operation)
-__device__ __forceinline__ float exact_d2(const float* __restrict__ q, const float* __restrict__ row, int dim) {
-    float acc = 0.f;
-    for (int c = 0; c < dim; c += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(row + c);
-        const float4 u = *reinterpret_cast<const float4*>(q + c);
-        const float e0 = u.x - v.x, e1 = u.y - v.y, e2 = u.z - v.z, e3 = u.w - v.w;
-        acc += e0 * e0;
-        acc += e1 * e1;
-        acc += e2 * e2;
-        acc += e3 * e3;
-    }
-    return acc;
-}
-
-// lexicographic (value, index) minimum over the wave
-__device__ __forceinline__ void wave_argmin(float& best, int& bi) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(best, off);
-        const int oi = __shfl_xor(bi, off);
-        if (ov < best || (ov == best && oi < bi)) {
-            best = ov;
-            bi = oi;
-        }
-    }
 }
 
 // One wave per query: the kc = min(k + RT_EXTRA, nd) smallest entries of its row of S in (value, index) order, their exact
@@ -437,5 +428,71 @@ extern "C" int epc_pairwise_topk_ws(const float* database, int num_db, const flo
                            idx + (size_t)q0 * k, dist + (size_t)q0 * k);
         EPC_CHECK_LAUNCH();
     }
+    return EPC_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Mining form (train.py:857-869: KDTree over the sampled negatives' cached descriptors): every query against ITS OWN list of
+// table rows, named by id.  Two launches: the distances, grid (candidate slabs, queries), one lane per candidate gathering its
+// row from the table (so one query against 4000 rows is 63 workgroups' work, not one wave's); then one wave per query over the
+// LDS copy of its distances -- topk_rounds, the selection of epc_pairwise_topk.
+// ---------------------------------------------------------------------------------------------------------------------
+#define MINE_SLAB 64
+#define MINE_MAX_CAND 16384
+
+__global__ __launch_bounds__(MINE_SLAB) void mine_dist_kernel(const float* __restrict__ table, int num_rows, int dim,
+                                                              const float* __restrict__ queries, const int32_t* __restrict__ cand,
+                                                              const int32_t* __restrict__ cand_count, int max_cand,
+                                                              float* __restrict__ d2) {
+    const int qi = blockIdx.y;
+    const int count = min(max(cand_count[qi], 0), max_cand);
+    const int p = blockIdx.x * MINE_SLAB + threadIdx.x;
+    if (p >= count) return;
+    const int id = cand[(size_t)qi * max_cand + p];
+    float v = INFINITY;                                  // an id outside the table: never selected, nothing loaded
+    if (id >= 0 && id < num_rows) {
+        v = exact_d2(queries + (size_t)qi * dim, table + (size_t)id * dim, dim);
+        if (!(v <= 3.0e38f)) v = INFINITY;               // NaN / overflow: never selected
+    }
+    d2[(size_t)qi * max_cand + p] = v;
+}
+
+__global__ __launch_bounds__(64) void mine_select_kernel(const float* __restrict__ d2, const int32_t* __restrict__ cand,
+                                                         const int32_t* __restrict__ cand_count, int max_cand, int k,
+                                                         int32_t* __restrict__ pos, int32_t* __restrict__ ids,
+                                                         float* __restrict__ dist) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x, qi = blockIdx.x;
+    const int count = min(max(cand_count[qi], 0), max_cand);
+    for (int d = lane; d < count; d += 64) lds[d] = d2[(size_t)qi * max_cand + d];
+    __syncthreads();
+    topk_rounds(lds, count, k, lane, pos + (size_t)qi * k, dist + (size_t)qi * k, cand + (size_t)qi * max_cand, ids + (size_t)qi * k);
+}
+
+extern "C" size_t epc_mine_topk_workspace_bytes(int num_q, int max_cand) {
+    if (num_q <= 0 || max_cand <= 0) return 0;
+    return rt_align((size_t)num_q * max_cand * sizeof(float));
+}
+
+extern "C" int epc_mine_topk(const float* table, int num_rows, int dim, const float* queries, int num_q, const int32_t* cand,
+                             const int32_t* cand_count, int max_cand, int k, int32_t* pos, int32_t* ids, float* dist, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    EPC_CHECK_ARG(table && queries && cand && cand_count && pos && ids && dist && workspace, "null pointer");
+    EPC_CHECK_ARG(epc_aligned16(table) && epc_aligned16(queries), "table and queries must be 16-byte aligned");
+    EPC_CHECK_ARG(dim > 0 && dim % 4 == 0, "descriptor dim must be a multiple of 4");
+    EPC_CHECK_ARG(k > 0 && k + RT_EXTRA <= RT_MAXC, "need 0 < k <= 56");
+    EPC_CHECK_ARG(num_rows > 0 && num_q >= 0 && num_q <= 65535 && max_cand > 0 && max_cand <= MINE_MAX_CAND,
+                  "need num_rows > 0, 0 <= num_q <= 65535, 0 < max_cand <= 16384");
+    if (num_q == 0) return EPC_OK;
+    EPC_CHECK_ARG(workspace_bytes >= epc_mine_topk_workspace_bytes(num_q, max_cand), "workspace below epc_mine_topk_workspace_bytes");
+    hipStream_t st = (hipStream_t)stream;
+    float* d2 = (float*)workspace;
+    const size_t lds_bytes = (size_t)max_cand * sizeof(float);
+    EPC_SET_DYN_LDS(mine_select_kernel, MINE_MAX_CAND * sizeof(float));
+    hipLaunchKernelGGL(mine_dist_kernel, dim3((max_cand + MINE_SLAB - 1) / MINE_SLAB, num_q), dim3(MINE_SLAB), 0, st, table, num_rows, dim,
+                       queries, cand, cand_count, max_cand, d2);
+    hipLaunchKernelGGL(mine_select_kernel, dim3(num_q), dim3(64), lds_bytes, st, d2, cand, cand_count, max_cand, k, pos, ids, dist);
+    EPC_CHECK_LAUNCH();
     return EPC_OK;
 }

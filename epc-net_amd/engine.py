@@ -190,6 +190,29 @@ class InferenceEngine:
         return out
 
 
+    def forward_bank(self, bank, ids: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The descriptors of the records ``ids`` of an ``ops.CloudBank`` -> (len(ids), FEATURE_OUTPUT_DIM), bit-identical to
+        ``forward(xyz[ids])`` on the clouds that were added (include/epcnet.h: epc_net_forward_bank): no upload, no sort, no kNN --
+        the records hold them.  ``ids``: a contiguous int32 DEVICE tensor, read when the kernels run (repeats and any order allowed;
+        a captured graph replays with whatever the buffer then holds).  An id outside the bank gives a NaN descriptor and the
+        status word EPC_STATUS_NONFINITE_INPUT.  One stream, passes of the micro-batch; ``last_status`` answers for this call too."""
+        if not torch.is_tensor(ids) or not ids.is_cuda or ids.dtype != torch.int32 or not ids.is_contiguous():
+            raise L.EpcNetError(-1, "forward_bank: ids must be a contiguous int32 tensor on the ROCm device (no CPU fallback)")
+        L.require_gpu()
+        if len(bank) == 0:
+            raise L.EpcNetError(-1, "forward_bank: the bank is empty")
+        nc = int(ids.numel())
+        cfg = self.cfg_for(bank.n)
+        packed = self.packed(cfg)
+        if out is None:
+            out = torch.empty((nc, cfg.output_dim), dtype=torch.float32, device=ids.device)
+        ws = self.workspace(cfg, max(nc, 1), ids.device)
+        self._last_cfg = cfg
+        self._last_overlap = None
+        L.check(L.lib().epc_net_forward_bank(ctypes.byref(cfg), packed.data_ptr(), bank.records.data_ptr(), len(bank), bank.n, bank.cap,
+                                             ids.data_ptr(), nc, L.ptr(out), ws.data_ptr(), ws.numel(), L.current_stream()))
+        return out
+
     def last_status(self, xyz_or_count) -> "list[int]":
         """Per-cloud EPC_STATUS_* words of the last pass of the most recent ``forward`` call on this engine's own
         workspace (include/epcnet.h: epc_net_last_status; synchronises the stream).  A non-zero word = that cloud's

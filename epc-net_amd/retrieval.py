@@ -2,7 +2,9 @@
 
   get_latent_vectors   evaluate.py:351-452  (the reference feeds ONE cloud per sess.run, :86-90; here any batch size --
                        in inference every cloud's descriptor is independent, so batching changes nothing but speed)
+  latent_vectors_bank  train.py:871-965     the same from the records of a cloud bank, by record id (epc_net_forward_bank)
   knn_search           evaluate.py:463,481  sklearn KDTree(database).query(q, k=25) -> epc_pairwise_topk on the GPU
+  mine_topk            train.py:857-869     the hard-negative KDTree query over rows named by id (epc_mine_topk)
   get_recall           evaluate.py:455-537  recall@1..25, top-1 % recall, top-1 similarity for one (m, n) run pair
   evaluate_runs        evaluate.py:293-332  average over all ordered pairs m != n
   evaluate_sharded     evaluate.py:293-332 end to end over the ranks of a process group (BASELINE.json configs[4]):
@@ -44,6 +46,50 @@ def latent_vectors_device(engine, clouds, batch_size: int = 64, device: Optional
         chunk = torch.as_tensor(clouds[i:i + batch_size], dtype=torch.float32).to(dev, non_blocking=True)
         engine.forward(chunk, out=out[i:i + chunk.shape[0]])
     return out
+
+
+def latent_vectors_bank(engine, bank, ids: Optional[torch.Tensor] = None, batch_size: int = 64) -> torch.Tensor:
+    """``latent_vectors_device`` for the clouds of an ``ops.CloudBank`` (train.py:871-965 without the upload, the sort and the kNN the
+    records already hold): the descriptors of the records ``ids`` (a device int32 tensor; None = every record, in id order) ->
+    (len, 256) float32 on the device, asynchronous.  Row i equals ``engine.forward`` on the cloud that was added as record ids[i]."""
+    if ids is None:
+        ids = torch.arange(len(bank), dtype=torch.int32, device=bank.device)
+    n = int(ids.numel())
+    out = torch.empty((n, 256), dtype=torch.float32, device=bank.device)
+    for i in range(0, n, batch_size):
+        engine.forward_bank(bank, ids[i:i + batch_size], out=out[i:i + batch_size])
+    return out
+
+
+def mine_topk(table: torch.Tensor, queries: torch.Tensor, cand: torch.Tensor, cand_count: torch.Tensor, k: int,
+              workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Hard-negative search (train.py:857-869) on the device: query q against the rows ``table[cand[q, :cand_count[q]]]``.
+    ``table`` (T, D) and ``queries`` (Q, D) float32, ``cand`` (Q, C) and ``cand_count`` (Q,) int32, all on the device.  Returns
+    (dist (Q, k), pos (Q, k), ids (Q, k)): distance, position inside the candidate list and table row, nearest first; equal to
+    ``knn_search(table[cand[q, :count]], queries[q])`` bit for bit (ties -> lower position; (-1, +inf) where fewer than k
+    candidates lie at a finite distance).  Two launches (epc_mine_topk), no synchronisation."""
+    L.require_gpu()
+    for name, t, dt in (("table", table, torch.float32), ("queries", queries, torch.float32), ("cand", cand, torch.int32),
+                        ("cand_count", cand_count, torch.int32)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise L.EpcNetError(-1, "mine_topk: %s must be a contiguous %s tensor on the ROCm device" % (name, dt))
+    if table.dim() != 2 or queries.dim() != 2 or cand.dim() != 2 or queries.shape[1] != table.shape[1] \
+            or cand.shape[0] != queries.shape[0] or cand_count.numel() != queries.shape[0]:
+        raise L.EpcNetError(-1, "mine_topk: expected table (T, D), queries (Q, D), cand (Q, C), cand_count (Q,)")
+    q, c, k = int(queries.shape[0]), int(cand.shape[1]), int(k)
+    pos = torch.empty((q, max(k, 0)), dtype=torch.int32, device=queries.device)
+    ids = torch.empty_like(pos)
+    dist = torch.empty((q, max(k, 0)), dtype=torch.float32, device=queries.device)
+    need = int(L.lib().epc_mine_topk_workspace_bytes(q, c))
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=queries.device)
+    L.check(L.lib().epc_mine_topk(table.data_ptr(), int(table.shape[0]), int(table.shape[1]), queries.data_ptr(), q, cand.data_ptr(),
+                                  cand_count.data_ptr(), c, k, pos.data_ptr(), ids.data_ptr(), dist.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), L.current_stream()))
+    if workspace is None:
+        ws.record_stream(torch.cuda.current_stream(queries.device))
+    return dist, pos, ids
 
 
 def knn_search(database: torch.Tensor, queries: torch.Tensor, k: int = NUM_NEIGHBORS) -> Tuple[torch.Tensor, torch.Tensor]:

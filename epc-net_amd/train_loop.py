@@ -7,6 +7,8 @@ and checkpointing -- the control flow and its constants restated, the compute on
   * cached descriptors          train.py:871-965   -> ``retrieval.get_latent_vectors`` (row i = training cloud i)
   * hard negatives              train.py:857-869   -> exact GPU k-NN over the 4000 sampled negatives' cached descriptors
                                                       (sklearn KDTree in the reference)
+  * the same three by record id train.py:820-965   -> ``Trainer(bank=True, device_mining=True)``: ``engine.forward_bank``,
+                                                      ``retrieval.latent_vectors_bank`` and ``retrieval.mine_topk`` on the cloud bank
   * checkpoints                 train.py:611-617   -> TensorFlow bundle files (``tf_bundle.write_checkpoint``), same
                                                       variable names, readable by ``tf.train.Saver`` and by this package
 
@@ -22,7 +24,8 @@ import numpy as np
 import torch
 
 from . import tf_bundle
-from .retrieval import get_latent_vectors
+from . import lib as L
+from .retrieval import get_latent_vectors, latent_vectors_bank
 from .utils.loading_pointclouds import NUM_POINTS, get_query_tuple, get_query_tuple_ids, get_random_hard_negatives
 from .variables import variable_scope
 
@@ -35,13 +38,19 @@ class Trainer:
     def __init__(self, step, train_queries: Dict[int, dict], train_data: np.ndarray,
                  test_queries: Optional[Dict[int, dict]] = None, test_data: Optional[np.ndarray] = None,
                  save_path: Optional[str] = None, logger: Optional[logging.Logger] = None, graph: bool = False,
-                 bank: bool = False):
+                 bank: bool = False, device_mining: bool = False):
         """``step``: a TrainStep / DistillStep; ``*_queries``: the pickles of generate_training_tuples (key -> {'query',
         'positives', 'negatives'}); ``*_data``: (T, 4096, INPUT_DIM) float32 arrays in key order (train.py:159-190).
         ``bank=True``: ``train_data`` is uploaded ONCE into an ``ops.CloudBank`` (sorted clouds + finished kNN graphs, ~0.65 MB per
         4096-point cloud of device memory) and the loop steps on cloud ids (``step.step_ids``): no per-step tuple assembly and
         upload on the host, no per-step sort / kNN / transposition on the device; same tuples, same losses, bit for bit.  It serves
-        the unaugmented protocol of train.py:388.  ``evaluate_loss``, the mining and the descriptor cache keep reading the arrays."""
+        the unaugmented protocol of train.py:388.  ``evaluate_loss``, the mining and the descriptor cache keep reading the arrays
+        unless ``device_mining=True`` (needs the bank): the query's descriptor and the refreshed descriptor cache then come from the
+        bank's records by id (``engine.forward_bank``) and stay on the device, and the hard negatives of a key are searched there
+        (``retrieval.mine_topk``) -- per key one upload of the sampled ids and one copy of the NUM_TO_TAKE mined ids back; the
+        shuffles and the tuple logic stay on the host, so a seeded run mines the same negatives and steps alike, bit for bit."""
+        if device_mining and not bank:
+            raise ValueError("device_mining=True needs bank=True: the mining reads the clouds by record id")
         self.step = step
         self.params = step.params
         self.TRAINING_QUERIES, self.train_data = train_queries, train_data
@@ -60,6 +69,9 @@ class Trainer:
         self.device = step.store.device
         self.history: List[dict] = []
         self.bank = self._build_bank(train_data) if bank else None
+        self.device_mining = bool(device_mining)
+        self._table_src, self._table_dev = None, None       # the caller's numpy descriptor cache and its device copy (by identity)
+        self._mine_host, self._mine_dev, self._mine_ws = None, None, None
 
     def _build_bank(self, data: np.ndarray):
         """Upload ``data`` (T, n, 3) into a CloudBank, in slices that bound the staging copy; logs the one-time cost."""
@@ -127,14 +139,50 @@ class Trainer:
         return (as_ids([[t[0]] for t in tuples]), as_ids([t[1] for t in tuples]), as_ids([t[2] for t in tuples]),
                 as_ids([t[3] for t in tuples])), ""
 
+    def _mining_table(self) -> torch.Tensor:
+        """The descriptor cache as a device tensor: what the refresh left, or the caller's numpy array uploaded once."""
+        t = self.TRAINING_LATENT_VECTORS
+        if torch.is_tensor(t) and t.is_cuda:
+            return t
+        if self._table_src is not t:
+            self._table_dev = torch.as_tensor(np.asarray(t), dtype=torch.float32).to(self.device).contiguous()
+            self._table_src = t
+        return self._table_dev
+
+    def _mine_on_device(self, key: int, negatives: List[int]) -> List[int]:
+        """train.py:820-855 + :857-869 on the bank: descriptor of record ``key`` -> its NUM_TO_TAKE nearest among the cached descriptors
+        of ``negatives``.  One int32 buffer {key, count, ids ...} goes up, the mined ids come back."""
+        from .retrieval import mine_topk
+        table = self._mining_table()
+        if self._mine_dev is None:
+            self._mine_host = torch.zeros(2 + SAMPLED_NEG, dtype=torch.int32).pin_memory()
+            self._mine_dev = torch.zeros(2 + SAMPLED_NEG, dtype=torch.int32, device=self.device)
+            self._mine_ws = torch.empty(int(L.lib().epc_mine_topk_workspace_bytes(1, SAMPLED_NEG)), dtype=torch.uint8,
+                                        device=self.device)
+        m = len(negatives)
+        host = self._mine_host.numpy()           # (the previous key's copy has completed: its result was read back)
+        host[0], host[1] = int(key), m
+        host[2:2 + m] = np.asarray(negatives, dtype=np.int32)
+        self._mine_dev[:2 + m].copy_(self._mine_host[:2 + m], non_blocking=True)
+        self.step._ensure_built(self.bank.n)
+        query = self._engine().forward_bank(self.bank, self._mine_dev[0:1])
+        k = min(NUM_TO_TAKE, m)                  # (retrieval.knn_search: k = min(k, rows))
+        _, _, ids = mine_topk(table, query, self._mine_dev[2:].view(1, SAMPLED_NEG), self._mine_dev[1:2], k, workspace=self._mine_ws)
+        # (a slot without a neighbour at a finite distance indexes the list with -1 on the host path: its last entry)
+        return [int(v) if v >= 0 else int(negatives[-1]) for v in ids[0].cpu().tolist()]
+
     def _hard_negatives(self, key: int) -> List[int]:
         """train.py:373-377 / :390-395 (the three cache states)."""
         if len(self.TRAINING_LATENT_VECTORS) == 0:
             return []
-        query = self.get_feature_representation(key)
-        np.random.shuffle(self.TRAINING_QUERIES[key]["negatives"])
-        negatives = self.TRAINING_QUERIES[key]["negatives"][0:SAMPLED_NEG]
-        hard = get_random_hard_negatives(query, negatives, NUM_TO_TAKE, self.TRAINING_LATENT_VECTORS)
+        if self.device_mining:
+            np.random.shuffle(self.TRAINING_QUERIES[key]["negatives"])
+            hard = self._mine_on_device(int(key), self.TRAINING_QUERIES[key]["negatives"][0:SAMPLED_NEG])
+        else:
+            query = self.get_feature_representation(key)
+            np.random.shuffle(self.TRAINING_QUERIES[key]["negatives"])
+            negatives = self.TRAINING_QUERIES[key]["negatives"][0:SAMPLED_NEG]
+            hard = get_random_hard_negatives(query, negatives, NUM_TO_TAKE, self.TRAINING_LATENT_VECTORS)
         if len(self.HARD_NEGATIVES.keys()) != 0:
             hard = list(set().union(self.HARD_NEGATIVES[key], hard))
         return hard
@@ -182,7 +230,11 @@ class Trainer:
             if i % 200 == 7 and self.TEST_QUERIES is not None:                                  # train.py:523-594
                 self.log.info("\t\t\teval_loss: %f", self.evaluate_loss(epoch))
             if epoch > 5 and i % (1400 // self.B) == 29:                                        # train.py:597-602
-                self.TRAINING_LATENT_VECTORS = self.get_latent_vectors()
+                if self.device_mining:
+                    self.step._ensure_built(self.bank.n)
+                    self.TRAINING_LATENT_VECTORS = latent_vectors_bank(self._engine(), self.bank)
+                else:
+                    self.TRAINING_LATENT_VECTORS = self.get_latent_vectors()
                 self.log.info("Updated cached feature vectors")
             if i % (6000 // self.B) == 101 and self.save_path and rank == 0:                    # train.py:605-617
                 self.log.info("Model saved in file: %s", self.save(epoch, i))     # (the ranks hold identical variables)

@@ -295,6 +295,24 @@ int epc_pairwise_topk(const float* database, int num_db, const float* queries, i
 size_t epc_pairwise_topk_workspace_bytes(int num_db, int num_q);
 int epc_pairwise_topk_ws(const float* database, int num_db, const float* queries, int num_q, int dim, int k, int32_t* idx,
                          float* dist, void* workspace, size_t workspace_bytes, void* stream);
+/* Hard-negative mining (train.py:857-869 get_random_hard_negatives: KDTree(latent_vecs[random_negs]).query(query_vec, k); the cached
+ * descriptors of train.py:871-965 are the table, the query's descriptor comes from train.py:820-855): query q is searched against the
+ * table rows cand[q][0 .. cand_count[q]) -- cand (num_q, max_cand) and cand_count (num_q) device int32, read when the kernels run
+ * (cand_count is clamped to [0, max_cand]).  pos, ids (int32) and dist (float32), each (num_q, k): the position inside the candidate
+ * list, the table row cand[q][pos], and the Euclidean distance, nearest first.
+ * The result EQUALS epc_pairwise_topk(table[cand[q][:count]], queries[q]) bit for bit: the same f32 sum_c (q_c - d_c)^2 in the same
+ * order (one device function), ties -> the lower POSITION (not the lower id), and (-1, -1, +Inf) slots when fewer than k candidates
+ * lie at a finite distance (NaN / Inf rows or queries, count < k).  A candidate id outside [0, num_rows) is never selected and
+ * nothing is loaded for it.
+ * Two launches, no host round trip, no atomics, capturable: the distances with grid (candidate slabs, queries), every candidate row
+ * gathered from the table by id, into the (num_q, max_cand) f32 workspace; then per query one workgroup's k rounds of arg-min over
+ * the LDS copy of its distances (the selection of epc_pairwise_topk).
+ * Preconditions: dim a multiple of 4, 0 < k <= 56, 0 < max_cand <= 16384, table and queries 16-byte aligned; a workspace of at
+ * least epc_mine_topk_workspace_bytes(num_q, max_cand) bytes; otherwise EPC_EINVAL, nothing launched. */
+size_t epc_mine_topk_workspace_bytes(int num_q, int max_cand);
+int epc_mine_topk(const float* table, int num_rows, int dim, const float* queries, int num_q, const int32_t* cand,
+                  const int32_t* cand_count, int max_cand, int k, int32_t* pos, int32_t* ids, float* dist, void* workspace,
+                  size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* Training-step operators (config c3; train.py:251-277).  Per-layer forward/backward pairs: training-mode    */
@@ -690,6 +708,35 @@ int epc_bank_store(void* bank, int num_records, int first_slot, int num_clouds, 
 int epc_bank_assemble(const void* bank, int num_records, const int32_t* ids, int num_ids, int n, int cap, float* xyz, float* kth,
                       int32_t* cnt, int32_t* idx, int32_t* rdeg, int32_t* roff, int32_t* rlist, int32_t* ovf_cnt, int32_t* ovf_list,
                       int32_t* status, float* poison, void* stream);
+/* The records ids[0 .. num_ids) (int32 in DEVICE memory, read when the kernel runs; repeats and any order allowed) as the INFERENCE
+ * pipeline holds a batch after its sort and kNN launches (epc_net_forward's workspace): xyz (num_ids, n, 3) the Hilbert-sorted
+ * coordinates, kth, cnt (num_ids, n), idx_u16 (num_ids, n, cap) the cloud-local lists as uint16 entries exactly as the record stores
+ * them (ascending j; the slots past min(cnt, cap) hold 0 -- a valid row; rows with cnt > cap take the exact scan from kth and the
+ * coordinates), and status (num_ids int32) OVERWRITTEN per slot with EPC_STATUS_NONFINITE_INPUT or 0 by the test the kNN kernel
+ * applies to the coordinates.  What train.py:820-855 (one cloud through sess.run) and train.py:871-965 (the whole training set) feed
+ * from host arrays, taken from the bank instead.  ONE launch, a byte mover like epc_bank_assemble with grid (slabs, num_ids) and
+ * 16-byte chunks, but fewer bytes: no rdeg / roff / rlist / ovf sections and nothing widened -- 344 KB read and written per 4096-point
+ * cloud at cap = 32.  No atomics: one thread writes a slot's status word.
+ * An id outside [0, num_records), or a record whose stored {n, cap} differ from the arguments, reads no record: that slot gets NaN
+ * coordinates, kth = 0, cnt = 0, list entries 0 and the status word EPC_STATUS_NONFINITE_INPUT, so the head returns a NaN descriptor
+ * for it.  Preconditions as epc_bank_assemble; every output 16-byte aligned.  A shape outside them: EPC_EINVAL, nothing launched. */
+int epc_bank_gather_infer(const void* bank, int num_records, const int32_t* ids, int num_ids, int n, int cap, float* xyz, float* kth,
+                          int32_t* cnt, void* idx_u16, int32_t* status, void* stream);
+/* epc_net_forward on the clouds of a bank, named by record id: out (num_ids, output_dim) = the descriptors of the records
+ * ids[0 .. num_ids) (device int32, read when the kernels run: capturable with a static id buffer).  Replaces the same sess.run as
+ * epc_net_forward where the caller is the training loop -- the descriptor of one training cloud (train.py:820-855) and the refresh of
+ * the cached descriptors of all of them (train.py:871-965) -- without the upload, the sort and the kNN, which the records already
+ * hold.  Per pass of micro_batch ids on `stream`: epc_bank_gather_infer, conv1 as its standalone launch (the same arithmetic and the
+ * same EPC_STATUS_FP16_RANGE test as the fused kNN + conv1 launch), then the launches of epc_net_forward from the first block on.
+ * BIT-IDENTICAL to epc_net_forward on the clouds that were stored, in any order of their points (descriptors do not depend on it
+ * and both paths work on the Hilbert-sorted cloud), status words included; both architectures, both precisions.  Workspace:
+ * epc_net_workspace_bytes(cfg, num_ids); epc_net_last_status(cfg, workspace, num_ids, ...) answers for this call too.
+ * bank_n, bank_cap: the shape the bank's records were stored with (epc_bank_store's n and cap).  The bank is raw device memory and the
+ * library keeps no state about it, so the host side of an asynchronous, capturable call learns the shape from the caller; the kernel
+ * checks every record's own header against it (a mismatch = an id outside the bank).  EPC_EINVAL, nothing launched: cfg->num_points
+ * != bank_n, bank_n > 8192 (the 2-byte lists of the pipeline), bank_cap != EPC_KNN_CAP. */
+int epc_net_forward_bank(const epc_cfg* cfg, const void* packed, const void* bank, int num_records, int bank_n, int bank_cap,
+                         const int32_t* ids, int num_ids, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Backward of loupe.py:255-291 with respect to the point features: df[b][n][f] = sum_k a[b][n][k] dvlad[b][f][k] + sum_k dz[b][n][k] Wc[f][k]
  * (a, dz: (num_clouds n_points, 64) -- the soft assignment and the gradient of its pre-BatchNorm logits; dvlad (num_clouds, F, 64);
