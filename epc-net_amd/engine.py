@@ -213,6 +213,19 @@ class InferenceEngine:
                                              ids.data_ptr(), nc, L.ptr(out), ws.data_ptr(), ws.numel(), L.current_stream()))
         return out
 
+    def forward_scans(self, points: torch.Tensor, offsets: torch.Tensor, num_points: int = 4096, normalize: bool = True,
+                      out: Optional[torch.Tensor] = None):
+        """Descriptors of RAW scans: ``points`` (total, 3) float32 and ``offsets`` (B + 1,) int32 on the device (``ops.pack_scans``), any
+        number of points per scan -> ``(descriptors (B, FEATURE_OUTPUT_DIM), status (B,) int32)``.  Runs ``ops.grid_downsample`` (to
+        ``num_points`` points per cloud; include/epcnet.h: epc_grid_downsample) and then ``forward`` on the same stream, no host round
+        trip in between -- bit-identical to ``forward(ops.grid_downsample(points, offsets, num_points, normalize)[0])``, and capturable
+        in a graph (the offsets are read when the kernel runs).  ``status`` holds the down-sampler's words: a scan flagged
+        EPC_STATUS_NO_GRID reaches the network as NaN rows, so its descriptor is NaN and ``last_status`` reports
+        EPC_STATUS_NONFINITE_INPUT for it."""
+        from . import ops
+        xyz, status, _ = ops.grid_downsample(points, offsets, num_points, normalize=normalize)
+        return self.forward(xyz, out=out), status
+
     def last_status(self, xyz_or_count) -> "list[int]":
         """Per-cloud EPC_STATUS_* words of the last pass of the most recent ``forward`` call on this engine's own
         workspace (include/epcnet.h: epc_net_last_status; synchronises the stream).  A non-zero word = that cloud's

@@ -1589,6 +1589,59 @@ def morton_sort(xyz):
     return out
 
 
+def pack_scans(scans, device=None):
+    """Host helper: a list of (M_i, 3) arrays (numpy or tensors; any M_i >= 0, a different one per scan) -> ``(points (total, 3)
+    float32, offsets (len + 1,) int32)`` as DEVICE tensors, the ragged form ``grid_downsample`` and ``InferenceEngine.forward_scans``
+    take."""
+    L.require_gpu()
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise EpcNetError(-1, "pack_scans: the scans go to a ROCm device (no CPU fallback)")
+    rows = [torch.as_tensor(s, dtype=torch.float32).reshape(-1, 3) for s in scans]
+    offsets = [0]
+    for r in rows:
+        offsets.append(offsets[-1] + int(r.shape[0]))
+    if offsets[-1] >= 2 ** 31:
+        raise EpcNetError(-1, "pack_scans: %d points do not fit int32 offsets" % offsets[-1])
+    points = torch.cat(rows, 0) if rows else torch.zeros((0, 3), dtype=torch.float32)
+    return points.to(device), torch.tensor(offsets, dtype=torch.int32).to(device)
+
+
+def grid_downsample(points, offsets, n, normalize=True, out=None):
+    """Ragged raw scans -> exactly ``n`` points per cloud by the grid average of include/epcnet.h (epc_grid_downsample; numpy
+    restatement: tests/downsample_ref.py): ``(xyz (B, n, 3) float32, status (B,) int32, info (B, 4) int32)``, all device tensors,
+    one launch on the current stream, no host read.  ``points`` (total, 3) float32 and ``offsets`` (B + 1,) int32 are device tensors
+    (``pack_scans``); the offsets are read when the kernel runs.  ``normalize``: zero mean inside [-1, 1] (the benchmark's
+    convention, what the networks were trained on) or, False, the sensor's units.  A scan without a grid of ``n`` cells gets NaN rows and
+    the status word EPC_STATUS_NO_GRID; ``info``: finite points, R*, D(R*), count of the last kept cell.  ``n``: a multiple of 32 in
+    [32, 4096]."""
+    for name, t, dt in (("points", points, torch.float32), ("offsets", offsets, torch.int32)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise EpcNetError(-1, "grid_downsample: %s must live on a ROCm device (no CPU fallback)" % name)
+        if t.dtype != dt or not t.is_contiguous():
+            raise EpcNetError(-1, "grid_downsample: %s must be a contiguous %s tensor, got %s" % (name, dt, t.dtype))
+    if points.dim() != 2 or int(points.shape[1]) != 3 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise EpcNetError(-1, "grid_downsample: expected points (total, 3) and offsets (B + 1,), got %s and %s"
+                          % (tuple(points.shape), tuple(offsets.shape)))
+    L.require_gpu()
+    B, n, dev = int(offsets.numel()) - 1, int(n), points.device
+    need = int(L.lib().epc_grid_downsample_workspace_bytes(B, n))
+    if need == 0:
+        raise EpcNetError(-1, "grid_downsample: n must be a multiple of 32 in [32, 4096], got %d" % n)
+    if out is None:
+        out = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (B, n, 3) or out.dtype != torch.float32:
+        raise EpcNetError(-1, "grid_downsample: `out` must be float32 (%d, %d, 3)" % (B, n))
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    if points.numel() == 0:
+        points = torch.zeros((1, 3), dtype=torch.float32, device=dev)        # (a pointer the library can check; no row of it is read)
+    L.check(L.lib().epc_grid_downsample(points.data_ptr(), offsets.data_ptr(), B, n, 1 if normalize else 0, L.ptr(out),
+                                        status.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(), _st()))
+    return out, status, info
+
+
 def adam_step(w, m, v, g, lr, t, beta1=0.9, beta2=0.999, eps=1e-8):
     """tf.train.AdamOptimizer update of one tensor, in place (train.py:273).  ``lr`` may be a one-element device tensor
     holding the bias-corrected rate lr_t (``t`` is then ignored): the form a captured HIP graph of the step uses."""

@@ -71,6 +71,7 @@ typedef enum epc_status {
  * coordinate as well (every a_ij of utils/tf_util.py:651-656 involving the point is NaN). */
 #define EPC_STATUS_NONFINITE_INPUT 1 /* a coordinate of the cloud is NaN or +-Inf                                 */
 #define EPC_STATUS_FP16_RANGE 2      /* EPC_PRECISION_FAST: an activation left fp16's range (|v| > 65504)         */
+#define EPC_STATUS_NO_GRID 4         /* epc_grid_downsample: the scan has no grid of N cells (its rows are NaN)    */
 
 #define EPC_KNN_SELECT 20 /* utils/tf_util.py:660: tf.nn.top_k(a, k=20), hard-coded */
 #define EPC_KNN_CAP 32    /* neighbour-list slots per point; rows with more ties take the exact scan path */
@@ -163,6 +164,42 @@ int epc_profile_elapsed_ms(epc_profile* prof, float* stage_ms /* host, EPC_NUM_S
  * with xyz_sorted[r] = xyz[perm[r]].  No reference counterpart: descriptors are permutation-invariant, the
  * pipeline sorts first so that kNN tiles are spatially tight and gathers are cache-local.  N <= 16384. */
 int epc_morton_sort(const float* xyz, int num_clouds, int n, float* xyz_sorted, int32_t* perm, void* stream);
+
+/* Raw scans in: grid-average down-sampling of ragged clouds to exactly n points each, the kind of cloud the benchmark's files hold
+ * (the reference leaves this step to an offline script outside its tree).  A stage IN FRONT of the pipeline: its output is what
+ * epc_net_forward, epc_morton_sort or a cloud bank take.  points (total, 3) float32; offsets (num_clouds + 1) int32 in DEVICE memory,
+ * read when the kernel runs (the call can be captured in a graph and replayed on other scans): cloud c is rows offsets[c] ..
+ * offsets[c + 1] - 1, rows need no alignment.  xyz_out (num_clouds, n, 3).  One workgroup per cloud, integer arithmetic behind the
+ * quantisation: the result is the same bits on every run and equal to the numpy restatement in tests/downsample_ref.py.
+ *
+ * Per cloud, target n:
+ *   1. Points with a NaN or +-Inf coordinate are dropped (LiDAR no-returns).  lo = per-axis minimum, e = the largest axis extent
+ *      (float32).
+ *   2. For a grid of R cells along the longest axis (1 <= R <= 1024):  s = (float)R / e;  t = (p - lo) * s;
+ *      u = min((int)(t * 4096.0f), R * 4096 - 1) per axis, every operation rounded once, the division correctly rounded.
+ *      Cell c = u >> 12, in-cell fraction u & 4095, key = (cz * 1024 + cy) * 1024 + cx.  D(R) = number of distinct keys.
+ *   3. The cloud fails if D(1024) < n.  Otherwise a = 1, b = 1024; while b - a > 1: m = (a + b) / 2; D(m) >= n ? b = m : a = m;
+ *      R* = b.  D is not monotone in R: this bisection IS the definition, not a search for the smallest R.  The cloud fails if
+ *      D(R*) > 2 n.
+ *   4. At R*, per occupied cell: the number of points and the three uint32 sums S of their fractions (<= 2^20 points per cloud keep the
+ *      sums inside 32 bits).
+ *   5. The n cells first in the order (count descending, key ascending) are kept -- the D - n least-supported cells are dropped -- and
+ *      emitted in ascending key order.  Per axis q = c * 4096 + S / count (integer division).
+ *   6. normalize != 0 (the benchmark's convention: zero mean, inside [-1, 1]):  qm = (sum of q) / n (64-bit integer division),
+ *      d = q - qm, out = (float)d * (1.0f / (float)max|d|), the maximum over all three axes.
+ *      normalize == 0 (the sensor's units):  out = lo + (float)q * (e / (float)(R* * 4096)).
+ * A cloud fails if it has fewer than n finite points, e == 0, D(1024) < n or D(R*) > 2 n, or if its offsets are decreasing, negative
+ * or describe more than 2^20 points (device data: checked on the device).  A failed cloud gets n rows of NaN and the status word
+ * EPC_STATUS_NO_GRID; the pipeline then flags it EPC_STATUS_NONFINITE_INPUT and returns a NaN descriptor, never a wrong finite one.
+ *
+ * status (num_clouds int32): OVERWRITTEN per cloud with 0 or EPC_STATUS_NO_GRID.  info (num_clouds, 4) int32, may be NULL: finite
+ * points, R*, D(R*), the count of the last kept cell (words the cloud did not reach are 0; a cloud that fails with D(R*) > 2 n reports
+ * 2 n + 1, where the pass stops counting).  workspace: epc_grid_downsample_workspace_bytes(num_clouds, n) bytes (0 = unsupported n),
+ * 4-byte aligned; the call leaves 8 words per cloud there: the four info words, then lo x, y, z and e as float32 -- the grid's frame.
+ * EPC_EINVAL, with nothing launched, unless n is a multiple of 32 in [32, 4096]; EPC_ENOMEM for a short workspace. */
+size_t epc_grid_downsample_workspace_bytes(int num_clouds, int n);
+int epc_grid_downsample(const float* points, const int32_t* offsets, int num_clouds, int n, int normalize, float* xyz_out,
+                        int32_t* status, int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
 
 /* utils/tf_util.py:647-666 pairwise_distance_mask, in index form.  For every point i of every cloud:
  *   kth[i]  = 20th largest a_ij (with multiplicity), a_ij = -((|p_i|^2 + -2 p_i.p_j) + |p_j|^2) in fp32,
