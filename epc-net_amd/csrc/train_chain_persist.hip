@@ -41,8 +41,15 @@
 // Safety.  The grid is at most the CU count and the host checks with the occupancy query that every workgroup is co-resident; every
 // spin is bounded by a wall-clock budget (s_memrealtime), a time-out sets the sticky error word and every workgroup leaves at its next
 // poll; a launch that finds the error word set leaves at once.  Either way every workgroup writes NaN into one row of the f32 concat
-// (the first row of its slice) and nothing into cat_bf16.  epc_chain_persist_status() is the signal: it reads the word, _reset()
-// clears it.
+// (the first row of its slice) and into the same row of cat_bf16 when that is given (pst_poison), and EVERY OTHER output of the launch
+// is undefined: d, za, zb, z0_next, the batch moments and the rest of the concat hold whatever they held before (an abandoned launch
+// has written some of them).  The poisoned rows are a mark for whoever looks at the concat, NOT a signal that travels: the ReLUs and
+// hinges behind them are fmaxf, which drops a NaN operand, so a training loss computed from them is finite.  The signal is the error
+// word: epc_chain_persist_status() reads it (it synchronises the stream), _reset() clears it; the training step adds a verdict formed
+// from it on the stream to the loss it returns (ops.chain_persist_verdict).  A caller who captures the launch in a graph of their own
+// asks epc_chain_persist_status() before using what a replay produced -- the word is sticky, so once per batch of replays is enough
+// -- and after an EPC_EHIP discards the results since the last good answer, calls _reset() and goes on replaying: the launch reads the
+// word and the sequence number when it runs, nothing of them is baked into the captured arguments but the spin budget.
 #include "train_chain_common.h"
 
 #define PST_WAVES 12                 // one 32-row tile per wave: at most 384 rows per workgroup (98 304 rows on 256 CUs)
@@ -296,6 +303,16 @@ struct PstFwdArgs {
     long long budget;
 };
 
+// What a workgroup of a launch that does not complete leaves: NaN in row `row` (the first of its slice; a workgroup has at least one
+// row) of the f32 concat and of its bf16 copy when there is one -- whichever of the two a head reads shows the mark.
+__device__ __forceinline__ void pst_poison(const epc_chain_fwd_args& a, size_t row, int width) {
+    unsigned short* cat16 = reinterpret_cast<unsigned short*>(a.cat_bf16);
+    for (int o = threadIdx.x; o < width; o += blockDim.x) {
+        a.cat[row * width + o] = __int_as_float(0x7fc00000);
+        if (cat16) cat16[row * width + o] = 0x7fc0;   // (bf16 quiet NaN: the upper half of the f32 one)
+    }
+}
+
 template <int PF>
 __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFwdArgs g) {
     extern __shared__ __attribute__((aligned(16))) float tiles_all[];   // one staging tile per wave
@@ -311,8 +328,7 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
     char* ws = reinterpret_cast<char*>(g.a.workspace);
     unsigned* sync = reinterpret_cast<unsigned*>(ws);
     if (ld_coh(sync + PST_W_ERR) != 0u) {         // an earlier launch was abandoned and not reset: NaN out (as an abandoned launch does)
-        const int lb_ = xcd_contiguous_block(blockIdx.x, gridDim.x);
-        for (int o = threadIdx.x; o < g.width; o += blockDim.x) g.a.cat[(size_t)lb_ * g.wg_rows * g.width + o] = __int_as_float(0x7fc00000);
+        pst_poison(g.a, (size_t)xcd_contiguous_block(blockIdx.x, gridDim.x) * g.wg_rows, g.width);
         return;
     }
     PstCtx cx = pst_init(sync, g.budget);
@@ -322,11 +338,8 @@ __global__ __launch_bounds__(64 * PST_WAVES) void chain_fwd_persist_kernel(PstFw
     const int base = wg0 + wave * 32;   // the wave's tile (wave < tiles)
     const bool have = wave < tiles;
     int phase = 0;
-    // an abandoned launch leaves NaN in the first row of the workgroup's slice of the f32 concat (cat_bf16 is not written);
-    // epc_chain_persist_status() is what reports it
-    auto poison = [&]() {
-        for (int o = threadIdx.x; o < g.width; o += blockDim.x) g.a.cat[(size_t)wg0 * g.width + o] = __int_as_float(0x7fc00000);
-    };
+    // an abandoned launch leaves NaN in the first row of the workgroup's slice of the concat; epc_chain_persist_status() is what reports it
+    auto poison = [&]() { pst_poison(g.a, (size_t)wg0, g.width); };
     // The wave's tile as it stands -> its rows of a dense (rows, 64) tensor, 16 lanes x float4 per row.  The tensors only LATER launches
     // read (za, zb for the backward; the concat) leave this way AFTER the phase's partial is posted: their stores drain under the
     // barrier's round trips instead of in front of the post (a wave's stores and the loads of its polls retire in order).

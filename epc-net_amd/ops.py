@@ -724,7 +724,9 @@ class ProxyConvTail(torch.autograd.Function):
 # collectives overlap the BACKWARD), so no kernel that waits for it shares the device with it.
 CHAIN_PERSIST_FWD = True
 CHAIN_SPIN_TICKS = 0          # spin budget of a grid barrier in 10-ns ticks; 0: the library's default (a quarter second)
+CHAIN_WS_ERR_WORD = 2112      # the workspace's sticky error word as an int32 index (PST_W_ERR of csrc/train_chain_persist.hip)
 _CHAIN_WS = {}
+_CHAIN_PERSIST_LAUNCHES = 0   # persistent launches issued so far (a step asks whether its forward took one: chain_persist_launches)
 
 
 def chain_workspace(device):
@@ -740,6 +742,20 @@ def chain_workspace(device):
         L.check(L.lib().epc_chain_persist_init(t.data_ptr(), _st()))
         _CHAIN_WS[key] = t
     return t
+
+
+def chain_persist_launches():
+    """How many persistent chain launches this process has issued (captured ones count when they are captured)."""
+    return _CHAIN_PERSIST_LAUNCHES
+
+
+def chain_persist_verdict(device):
+    """0-d float32 on `device`: 0.0, or NaN when the workspace's error word is non-zero -- a persistent launch was abandoned, or found
+    the word set and left at once, and has not been reset.  What a training step adds to the loss it returns: after such a launch every
+    output of the chain but one NaN row per workgroup is undefined, and those rows do not reach the loss (the ReLUs and hinges are
+    fmaxf, which drops a NaN operand).  One tiny launch on the current stream, no host synchronisation: it replays inside a captured
+    graph and reads the word as the launch before it left it.  (xlogy(w, -1) = w log(-1): 0 for w = 0, NaN otherwise.)"""
+    return torch.xlogy(chain_workspace(device).view(torch.int32)[CHAIN_WS_ERR_WORD], -1.0)
 
 
 def chain_persist_check(device=None):
@@ -872,6 +888,8 @@ class ProxyConvChain(torch.autograd.Function):
             B.mean0, B.var0, B.mean_a, B.var_a, B.mean_b, B.var_b = (t.data_ptr() for t in moms[b])
             B.d, B.za, B.zb = (t.data_ptr() for t in tens[b])
         L.check(lib.epc_chain_fwd_persist(ctypes.byref(a), int(pieces_fwd), _st()))
+        global _CHAIN_PERSIST_LAUNCHES
+        _CHAIN_PERSIST_LAUNCHES += 1
 
     @staticmethod
     def backward(ctx, dcat, *_unused):

@@ -222,7 +222,10 @@ class Trainer:
             if not np.isfinite(losses[-1]) and self.bank is not None:
                 self.bank.check()       # an id outside the bank (a query dict that does not match train_data) raises here, naming the slot
             if not np.isfinite(losses[-1]):
-                # a persistent chain launch that was abandoned (a grid barrier ran out of its spin budget) leaves NaN: say so, and reset
+                # A persistent chain launch that was abandoned (a grid barrier ran out of its spin budget) makes the step's returned loss
+                # NaN through the verdict the step adds to it (TrainStep._forward_backward; the NaN rows the launch leaves in the concat
+                # would not: the ReLUs and hinges drop them).  Say so and reset: this raises EpcNetError.  The step's update has been
+                # applied from undefined activations by then -- whoever catches the error goes back to the last checkpoint.
                 from . import ops
                 ops.chain_persist_check()
             self.history.append({"epoch": epoch, "iter": i, "loss": losses[-1], "lr": lr})

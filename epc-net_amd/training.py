@@ -72,6 +72,7 @@ class TrainStep:
         self.v: Dict[str, torch.Tensor] = {}
         self._graph = None                        # captured HIP graph(s) of one step (step(..., graph=True))
         self._replays_since_sync = 0              # replayed steps since the last stream synchronisation (REPLAYS_PER_SYNC)
+        self._verdict = None                      # ops.chain_persist_verdict of the last forward, or None: it took no persistent launch
         self._exchange = None                     # flat gradient / statistics buffer of data-parallel steps
         # GEMM arithmetic of the step (ops.set_gemm_precision): "bf16x6" = f32-accurate like the reference's fp32 graph
         # (default); "bf16" = one bf16 value per operand, the arithmetic BASELINE.json configs[2] names
@@ -148,7 +149,10 @@ class TrainStep:
         (SURVEY.md 8e): THREE graphs around two all-reduces -- [forward, head backward, pack the head's gradients] -> RCCL all-reduce
         of those (asynchronous) || [backbone backward, moving averages, pack the rest] -> RCCL all-reduce of the rest -> [mean, unpack
         the statistics, Adam].  The schedule values (learning rate with Adam's bias correction, BN decay) live in device memory
-        and are refreshed before every replay, so replays follow train.py:138-157 exactly like eager steps."""
+        and are refreshed before every replay, so replays follow train.py:138-157 exactly like eager steps.
+        When the backbone's forward ran as the persistent launch and that launch was abandoned (``ops.chain_persist_check()`` says so
+        and resets), the returned loss is NaN and the step's update HAS been applied, from undefined activations: go back to the state
+        before it.  The error word is sticky: every later step does the same until the check."""
         p = self.params
         B = int(query.shape[0])
         self._ensure_built(int(query.shape[2]))
@@ -161,7 +165,11 @@ class TrainStep:
             loss = self._eager_step(query, positives, negatives, other_neg, lr, bn_decay, t)
         self.store.bump(self.outer or None)
         self.global_step += 1
-        # (the graphed path returns the replayed graph's static output buffer: clone it, or the next replay overwrites it)
+        # (the graphed path returns the replayed graph's static output buffer: copy it, or the next replay overwrites it -- the sum with
+        # the persistent launch's verdict, see _forward_backward, is that copy)
+        verdict = self._graph["verdict"] if graph else self._verdict
+        if verdict is not None:
+            return loss.detach() + verdict, lr, bn_decay
         return (loss.detach().clone() if graph else loss.detach()), lr, bn_decay
 
     def step_ids(self, bank, query_ids, positive_ids, negative_ids, other_ids, epoch: int = 0, graph: bool = False):
@@ -172,7 +180,7 @@ class TrainStep:
         before every replay, like the schedule values, and the assemble launch is INSIDE the captured graph (the first of the three
         in the data-parallel form).  Unaugmented tuples only (the reference's protocol, train.py:388): a rotated or jittered cloud
         has another graph -- use ``step``.  An id outside the bank gives a NaN loss (and a step on an empty cloud in that slot: go back
-        to the state before it); ``bank.check()`` names the slot."""
+        to the state before it); ``bank.check()`` names the slot.  An abandoned persistent launch gives a NaN loss as in ``step``."""
         import numpy as np
         p = self.params
         parts = [np.asarray(x.detach().cpu() if torch.is_tensor(x) else x).astype(np.int64) for x in
@@ -198,6 +206,10 @@ class TrainStep:
         # The returned loss = the step's loss + the assemble launch's verdict (0, or NaN when an id was outside the bank): the NaN
         # coordinates of such a slot alone do not reach the loss (the ReLUs and hinges are fmaxf).  One launch, where ``step`` clones
         # the replayed graph's static loss buffer; the step's own arithmetic is untouched.
+        # The persistent launch's verdict (see _forward_backward) is added the same way.
+        verdict = self._graph["verdict"] if graph else self._verdict
+        if verdict is not None:
+            return loss.detach() + src["out"]["poison"] + verdict, lr, bn_decay
         return loss.detach() + src["out"]["poison"], lr, bn_decay
 
     @staticmethod
@@ -227,6 +239,8 @@ class TrainStep:
         tf_util.defer_ema_updates()                 # the 34 moving-average updates are applied in one launch below
         tf_util.BACKBONE_TAP = None
         prev = ops.set_gemm_precision(self.precision)
+        self._verdict = None
+        launches = ops.chain_persist_launches()
         try:
             if source is not None:
                 with torch.no_grad():
@@ -234,6 +248,15 @@ class TrainStep:
                 loss = self.compute_loss(query, positives, negatives, other_neg, True, bn_decay, graph=assembled)
             else:
                 loss = self.compute_loss(query, positives, negatives, other_neg, True, bn_decay)
+            if ops.chain_persist_launches() != launches:
+                # The forward took the persistent launch.  If that launch was abandoned (a grid barrier ran out of its spin budget, or
+                # the error word of an earlier abandonment is still set), every tensor it should have written is undefined and the loss
+                # above is nevertheless FINITE: the NaN rows it leaves in the concat do not pass the fmaxf of the ReLUs and hinges.
+                # So the verdict -- 0, or NaN while the workspace's error word is set -- is formed here: on the stream, behind the
+                # chain's forward, inside whatever capture is open, without a host synchronisation.  ``step`` / ``step_ids`` add it to
+                # the loss they RETURN, as the assemble launch's verdict; the step's own arithmetic is untouched.
+                with torch.no_grad():
+                    self._verdict = ops.chain_persist_verdict(loss.device)
             tap = tf_util.BACKBONE_TAP
             if between is not None and tap is not None and tap.requires_grad:
                 # Which variables lie below the cut is a property of the GRAPH: those the backbone's output depends on
@@ -513,6 +536,7 @@ class TrainStep:
             with torch.cuda.graph(g["graph"]):
                 g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"], source=source)
                 self._apply(grads, g["lr_t"], t)
+            g["verdict"] = self._verdict              # (a static buffer of the graph like the loss, or None: no persistent launch)
         else:
             # Data-parallel: [forward, head backward, pack head] | RCCL (head, asynchronous) | [backbone backward, moving averages,
             # pack rest] | RCCL (rest) | [mean, unpack, Adam] -- the captures end and begin INSIDE the step, at the cut of its
@@ -547,6 +571,7 @@ class TrainStep:
                     begin(g["graph"])
                     g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"],
                                                               between=between if self.overlap_exchange else None, source=source)
+                    g["verdict"] = self._verdict
                     self._pack_rest(ex, grads, g["cut"])
                     end()
                     begin(g["graph2"], pool=g["graph"].pool())

@@ -657,9 +657,13 @@ int epc_chain_dw_sum(int layers, const float* const* partials, float* const* dW,
  * differs: group partials by row range).  Usable when epc_chain_persist_ok(rows) != 0: at most 12 tiles per workgroup (rows <=
  * 384 x CUs) and every workgroup co-resident by the occupancy query.  Nothing else may need the CUs these workgroups wait on: do not
  * run it beside a kernel that waits for IT.  Every spin is bounded (spin_ticks of the 100-MHz s_memrealtime, 0 = a quarter second): on
- * a time-out the sticky error word of the workspace is set, every workgroup leaves after writing NaN into one row of the f32 concat
- * (nothing into cat_bf16), and every later launch on the same workspace does the same at once.  epc_chain_persist_status()
- * (synchronises the stream) is the signal: it returns EPC_EHIP until epc_chain_persist_reset().  workspace:
+ * a time-out the sticky error word of the workspace is set, every workgroup leaves after writing NaN into one row of cat (and of
+ * cat_bf16 when given), and every later launch on the same workspace does the same at once.  After such a launch EVERY output but
+ * those rows is undefined (d, za, zb, z0_next, the moments, the rest of cat), and the NaN rows are no signal: behind fmaxf ReLUs a
+ * loss computed from them is finite.  epc_chain_persist_status() (synchronises the stream) is the signal: it returns EPC_EHIP
+ * until epc_chain_persist_reset().  A caller who captures the launch in a graph of their own calls it before using a replay's
+ * results (the word is sticky: once per batch of replays), discards them on EPC_EHIP, resets and goes on replaying -- the launch
+ * reads the word and the sequence number when it runs; only spin_ticks is baked into the captured arguments.  workspace:
  * epc_chain_persist_workspace_bytes() bytes, zeroed ONCE with epc_chain_persist_init() and then left to the library (launch sequence
  * number, the barriers' tagged partials); one launch at a time per workspace. */
 #define EPC_CHAIN_MAX_BLOCKS 4
