@@ -114,9 +114,8 @@ class InferenceEngine:
         c_names = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
         c_ptrs = (ctypes.c_void_p * len(names))(*[t.data_ptr() for t in tensors])
         buf = torch.empty(nbytes, dtype=torch.uint8, device=tensors[0].device)
-        rc = L.lib().epc_net_pack_weights(ctypes.byref(cfg), c_names, c_ptrs, len(names), buf.data_ptr(), nbytes,
-                                          L.current_stream())
-        L.check(rc)     # (fast precision: EPC_ERANGE when a folded weight does not fit fp16 -- never a packed Inf)
+        # (fast precision: EPC_ERANGE when a folded weight does not fit fp16 -- never a packed Inf)
+        L.run.epc_net_pack_weights(ctypes.byref(cfg), c_names, c_ptrs, len(names), buf, nbytes)
         if self._packed is not None:
             # batches submitted on the engine's lanes may still be reading the previous buffer: keep it alive until their
             # streams have passed this point (the caching allocator would otherwise hand it out again)
@@ -209,8 +208,8 @@ class InferenceEngine:
         ws = self.workspace(cfg, max(nc, 1), ids.device)
         self._last_cfg = cfg
         self._last_overlap = None
-        L.check(L.lib().epc_net_forward_bank(ctypes.byref(cfg), packed.data_ptr(), bank.records.data_ptr(), len(bank), bank.n, bank.cap,
-                                             ids.data_ptr(), nc, L.ptr(out), ws.data_ptr(), ws.numel(), L.current_stream()))
+        L.run.epc_net_forward_bank(ctypes.byref(cfg), packed, bank.records, len(bank), bank.n, bank.cap, ids, nc, L.ptr(out), ws,
+                                   ws.numel())
         return out
 
     def forward_scans(self, points: torch.Tensor, offsets: torch.Tensor, num_points: int = 4096, normalize: bool = True,
@@ -243,8 +242,7 @@ class InferenceEngine:
             for p in range((nc + mb - 1) // mb):
                 n_p = min(mb, nc - p * mb)
                 arr = (ctypes.c_int32 * n_p)()
-                L.check(L.lib().epc_net_last_status(ctypes.byref(cfg), self._ws.data_ptr() + (p % lanes) * slice_bytes, n_p, arr,
-                                                    L.current_stream()))
+                L.run.epc_net_last_status(ctypes.byref(cfg), self._ws.data_ptr() + (p % lanes) * slice_bytes, n_p, arr)
                 words += [int(v) for v in arr]
             return words
         if self._ws is None or self._last_cfg is None:
@@ -257,7 +255,7 @@ class InferenceEngine:
         mb = L.micro_batch_of(self._last_cfg, nc)
         last = nc % mb or mb
         arr = (ctypes.c_int32 * last)()
-        L.check(L.lib().epc_net_last_status(ctypes.byref(self._last_cfg), self._ws.data_ptr(), nc, arr, L.current_stream()))
+        L.run.epc_net_last_status(ctypes.byref(self._last_cfg), self._ws, nc, arr)
         return [int(v) for v in arr]
 
     # ---- throughput mode: independent batches in flight on the engine's own streams ---------------------------

@@ -2,8 +2,8 @@
 
 The header is the one definition of the C boundary: ``parse_header`` reads every declaration, ``#define EPC_*`` and the
 ``epc_status`` enum out of it, and this module sets ``restype`` / ``argtypes`` of every entry point, the ``EPC_*`` module
-attributes, ``STATUS_NAMES`` and ``EXPORTS`` from the result.  Anything the reader does not understand is an exception at
-import, never a skipped line.  Only the three structures are mirrored by hand (tests/test_host_cpu.py checks their layout
+attributes, ``STATUS_NAMES``, ``EXPORTS`` and the checked call form ``run`` of every entry point that takes a stream from the
+result.  Anything the reader does not understand is an exception at import, never a skipped line.  Only the three structures are mirrored by hand (tests/test_host_cpu.py checks their layout
 against the compiler).
 
 There is NO fallback: if the shared library has not been built (``python -c "import __graft_entry__ as g;
@@ -28,13 +28,15 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "epcnet.h")
 
 _SCALARS = {"int": c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "float": c_float,
             "size_t": ctypes.c_size_t, "int32_t": c_int32, "uint32_t": ctypes.c_uint32}
+# the dtype a tensor must have where the header declares a typed pointee (``run``); any dtype goes at every other pointer
+_POINTEES = {"float*": torch.float32, "int32_t*": torch.int32, "int*": torch.int32, "long*": torch.int64}
 
 
 def parse_header(text: str):
     """``(functions, constants, status)`` of the text of include/epcnet.h: ``functions[name] = (return type, [parameter
-    types])`` in header order, as C type names without ``const`` and spaces around ``*`` -- a key of ``_SCALARS``, or any
-    type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME> <integer>``; ``status``:
-    the members of ``enum epc_status``.  Raises ValueError on whatever it does not understand."""
+    types], [parameter names])`` in header order, the types as C type names without ``const`` and spaces around ``*`` -- a key
+    of ``_SCALARS``, or any type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME>
+    <integer>``; ``status``: the members of ``enum epc_status``.  Raises ValueError on whatever it does not understand."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)         # extern "C" { and its }
     constants = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(EPC_\w+)[ \t]+(.*?)[ \t]*$", text, flags=re.M)}
@@ -55,15 +57,16 @@ def parse_header(text: str):
         m = re.fullmatch(r"\s*([\w\s*]+?)\b(epc_\w+)\s*\((.*)\)\s*", decl, flags=re.S)
         if not m or m.group(2) in functions:
             raise ValueError("epcnet.h: not a declaration, or a second one of its name: %r" % " ".join(decl.split()))
-        ret, name, params = ctype(m.group(1)), m.group(2), []
+        ret, name, params, names = ctype(m.group(1)), m.group(2), [], []
         if ret not in _SCALARS and ret != "char*":
             raise ValueError("epcnet.h: %s: unknown return type %r" % (name, ret))
         for p in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
-            pm = re.fullmatch(r"\s*(.*[\s*])\w+\s*", p, flags=re.S)                # the type, then the parameter's name
+            pm = re.fullmatch(r"\s*(.*[\s*])(\w+)\s*", p, flags=re.S)              # the type, then the parameter's name
             if not pm or (ctype(pm.group(1)) not in _SCALARS and "*" not in pm.group(1)):
                 raise ValueError("epcnet.h: %s: unknown parameter type in %r" % (name, " ".join(p.split())))
             params.append(ctype(pm.group(1)))
-        functions[name] = (ret, params)
+            names.append(pm.group(2))
+        functions[name] = (ret, params, names)
     return functions, constants, status
 
 
@@ -121,7 +124,7 @@ _lib = ctypes.CDLL(LIB_PATH)
 
 # a pointer to a structure mirrored above keeps its type check; every other pointer is a void*
 _POINTERS = {"epc_cfg*": POINTER(EpcCfg), "epc_chain_fwd_args*": POINTER(ChainFwdArgs)}
-for _name, (_ret, _params) in _functions.items():
+for _name, (_ret, _params, _) in _functions.items():
     _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
     _fn.restype = c_char_p if _ret == "char*" else _SCALARS[_ret]
     _fn.argtypes = [_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
@@ -155,6 +158,68 @@ def micro_batch_of(cfg: "EpcCfg", num_clouds: int) -> int:
 
 def current_stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _converter(where: str, ctype: str):
+    """What turns one Python argument of a launching entry point into what ctypes takes for a parameter of C type ``ctype``
+    (``where`` names the function, the position and the parameter in a refusal).  Contiguity is the call site's business: the
+    GEMMs take strided views with their strides, the chain writes column slices of the concat."""
+    if "*" in ctype:
+        dtype = _POINTEES.get(ctype)
+
+        def pointer(a):
+            if a is None:                   # a null pointer
+                return None
+            try:
+                on_device = a.is_cuda
+            except AttributeError:          # an int (a raw address) or a ctypes object (byref, a pointer array): ctypes' business
+                return a
+            if not on_device:
+                raise EpcNetError(-1, "%s: tensor must live on a ROCm device: the HIP path has no CPU fallback" % where)
+            if dtype is not None and a.dtype is not dtype:
+                raise EpcNetError(-1, "%s: the header declares %s there, the tensor is %s" % (where, dtype, a.dtype))
+            return a.data_ptr()
+        return pointer
+    cast = float if ctype == "float" else int
+
+    def scalar(a):
+        if type(a) is cast:
+            return a
+        if isinstance(a, torch.Tensor):
+            raise TypeError("%s: a tensor where the header declares a scalar" % where)
+        return cast(a)
+    return scalar
+
+
+def _launcher(name: str, fn, types, names):
+    signature = "%s(%s)" % (name, ", ".join("%s %s" % tn for tn in zip(types, names)))
+    converters = [_converter("%s: argument %d (%s %s)" % (name, i + 1, t, n), t) for i, (t, n) in enumerate(zip(types[:-1], names))]
+    ok = _status["EPC_OK"]
+
+    def launch(*args, stream=None):
+        if len(args) != len(converters):
+            raise TypeError("%s takes %d arguments and the stream, got %d" % (signature, len(converters), len(args)))
+        status = fn(*[c(a) for c, a in zip(converters, args)], current_stream() if stream is None else stream)
+        if status != ok:
+            check(status)
+    launch.__name__ = launch.__qualname__ = name
+    launch.__doc__ = signature
+    return launch
+
+
+class run:
+    """The checked call form of every LAUNCHING entry point -- one whose last parameter is ``void* stream`` -- by name:
+    ``run.epc_col_sum(dy, rows, cout, db, ws, n)`` takes the header's arguments without the stream.  A tensor is legal at a pointer
+    parameter only, must live on the device and have the dtype of a typed pointee (``_POINTEES``; anything goes at ``void*``); its
+    address is passed, strides are the caller's.  None, an int address and ctypes objects pass unchanged, scalars through int() /
+    float().  The stream is the current one (or ``stream=``), the returned status goes through ``check``.  Everything else --
+    size queries, ``*_ok``, the forwards whose stream is not last -- is called on the raw handle ``lib()``."""
+
+
+LAUNCHING = [_n for _n, (_, _t, _pn) in _functions.items() if _t and (_t[-1], _pn[-1]) == ("void*", "stream")]
+for _name in LAUNCHING:
+    assert _functions[_name][0] == "int", "%s takes a stream and does not return a status" % _name
+    setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), *_functions[_name][1:])))
 
 
 def require_gpu() -> None:

@@ -1,6 +1,7 @@
 """Differentiable operators of the training step: ``torch.autograd.Function`` wrappers whose forward AND backward are
 calls into libepcnet_hip.so (``csrc/train_ops.hip``).  autograd is used as the tape only; there is no torch arithmetic
-in these functions and no CPU fallback.  Reference semantics are cited per operator."""
+in these functions and no CPU fallback.  Every launch goes through ``L.run`` (lib.py): tensors and views in, device and dtype
+checked against include/epcnet.h, the current stream appended, the status raised.  Reference semantics are cited per operator."""
 from __future__ import annotations
 
 import ctypes
@@ -13,10 +14,6 @@ from .lib import EpcNetError
 BN_EPS = 1e-3
 
 
-def _st():
-    return L.current_stream()
-
-
 _WORKSPACES = {}
 
 
@@ -24,7 +21,7 @@ def _ws(rows, C, device):
     """The column-reduction workspace of (device, current stream), reused by every reduction of that stream
     (include/epcnet.h, workspace contract)."""
     n = L.lib().epc_colreduce_workspace_bytes(int(rows), int(C))
-    key = (device.index, int(_st() or 0))
+    key = (device.index, int(L.current_stream() or 0))
     buf = _WORKSPACES.get(key)
     if buf is None or buf.numel() < n:
         buf = torch.zeros(max(n, 1 << 20), dtype=torch.uint8, device=device)
@@ -53,7 +50,7 @@ _SPLITK_WS = {}
 
 def _splitk_ws(floats, device):
     """The split-K partial-product workspace of (device, current stream) for the deterministic forward GEMMs."""
-    key = (device.index, int(_st() or 0))
+    key = (device.index, int(L.current_stream() or 0))
     buf = _SPLITK_WS.get(key)
     if buf is None or buf.numel() < floats:
         buf = _SPLITK_WS[key] = torch.empty(max(int(floats), 1 << 18), dtype=torch.float32, device=device)
@@ -84,19 +81,16 @@ def gemm(A, B, out=None, bias=None, trans_a=False, trans_b=False, splitk=1, accu
     if deterministic and splitk > 1:
         pieces = 1 if _GEMM_PRECISION == "bf16" else (2 if fast else 3)
         ws = _splitk_ws(nb * int(splitk) * M * N, A.device)
-        L.check(L.lib().epc_gemm_splitk_det(
-            A.data_ptr(), B.data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else None,
-            M, N, K, sAm, sAk, sBk, sBn, out.stride(-2), nb, A.stride(0) if batched else 0,
-            B.stride(0) if batched else 0, out.stride(0) if batched else 0, int(splitk), 1 if accumulate else 0, pieces,
-            ws.data_ptr(), ws.numel(), _st()))
+        L.run.epc_gemm_splitk_det(A, B, out, bias, M, N, K, sAm, sAk, sBk, sBn, out.stride(-2), nb, A.stride(0) if batched else 0,
+                                  B.stride(0) if batched else 0, out.stride(0) if batched else 0, splitk, 1 if accumulate else 0,
+                                  pieces, ws, ws.numel())
         return out
     if _GEMM_PRECISION == "bf16":
-        fn = L.lib().epc_gemm_bf16
+        fn = L.run.epc_gemm_bf16
     else:
-        fn = L.lib().epc_gemm_f32_fast if fast else L.lib().epc_gemm_f32
-    L.check(fn(A.data_ptr(), B.data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else None,
-             M, N, K, sAm, sAk, sBk, sBn, out.stride(-2), nb, A.stride(0) if batched else 0,
-             B.stride(0) if batched else 0, out.stride(0) if batched else 0, int(splitk), 1 if accumulate else 0, _st()))
+        fn = L.run.epc_gemm_f32_fast if fast else L.run.epc_gemm_f32
+    fn(A, B, out, bias, M, N, K, sAm, sAk, sBk, sBn, out.stride(-2), nb, A.stride(0) if batched else 0,
+       B.stride(0) if batched else 0, out.stride(0) if batched else 0, splitk, 1 if accumulate else 0)
     return out
 
 
@@ -138,8 +132,7 @@ class Linear(torch.autograd.Function):
         rows, cin = x.shape
         if cin <= 4 and W.shape[1] % 4 == 0 and W.is_contiguous():     # conv1 on the coordinates: three FMAs per output
             z = torch.empty((rows, W.shape[1]), dtype=torch.float32, device=x.device)
-            L.check(L.lib().epc_linear_smallk_fwd(x.data_ptr(), W.data_ptr(), b.data_ptr() if b is not None else None, rows, cin,
-                                                  W.shape[1], z.data_ptr(), _st()))
+            L.run.epc_linear_smallk_fwd(x, W, b, rows, cin, W.shape[1], z)
             return z
         # few output tiles but a deep K (the 16384-wide hidden projection on a handful of rows): split K over workgroups
         tiles = ((rows + 63) // 64) * ((W.shape[1] + 63) // 64)
@@ -157,15 +150,14 @@ class Linear(torch.autograd.Function):
             dW = torch.empty(W.shape, dtype=torch.float32, device=W.device)   # dense [cin][64] (the kernel's layout), whatever W's strides
             pf = L.lib().epc_linear_smallk_dw_partial_floats(rows, cin)
             part = _splitk_ws(pf, x.device)
-            L.check(L.lib().epc_linear_smallk_dw(x.data_ptr(), dy.data_ptr(), rows, cin, cout, dW.data_ptr(), part.data_ptr(),
-                                                 part.numel(), _st()))
+            L.run.epc_linear_smallk_dw(x, dy, rows, cin, cout, dW, part, part.numel())
         else:
             dW = gemm(x, dy, trans_a=True, splitk=_splitk_for(cin, cout, rows), fast=True, deterministic=True)
         db = None      # exactly zero in front of a training-mode BatchNorm: left undefined (TrainStep reads it as zeros)
         if ctx.has_bias and not ctx.zero_bias_grad:
             db = torch.empty(cout, dtype=torch.float32, device=x.device)
             ws, n = _ws(rows, cout, x.device)
-            L.check(L.lib().epc_col_sum(dy.data_ptr(), rows, cout, db.data_ptr(), ws.data_ptr(), n, _st()))
+            L.run.epc_col_sum(dy, rows, cout, db, ws, n)
         return dx, dW, db, None
 
 
@@ -181,10 +173,9 @@ class BatchNormTrain(torch.autograd.Function):
         mean = torch.empty(C, dtype=torch.float32, device=z.device)
         var = torch.empty(C, dtype=torch.float32, device=z.device)
         ws, n = _ws(rows, C, z.device)
-        L.check(L.lib().epc_col_moments(z.data_ptr(), rows, C, mean.data_ptr(), var.data_ptr(), ws.data_ptr(), n, _st()))
+        L.run.epc_col_moments(z, rows, C, mean, var, ws, n)
         y = torch.empty_like(z)
-        L.check(L.lib().epc_bn_apply_fwd(z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                         float(eps), int(relu), rows, C, y.data_ptr(), _st()))
+        L.run.epc_bn_apply_fwd(z, mean, var, gamma, beta, eps, relu, rows, C, y)
         ctx.save_for_backward(z, mean, var, gamma, beta)       # the ReLU mask is recomputed from z: y is not kept
         ctx.eps, ctx.relu = float(eps), int(relu)
         ctx.mark_non_differentiable(mean, var)
@@ -202,9 +193,7 @@ class BatchNormTrain(torch.autograd.Function):
         dgamma = torch.empty(C, dtype=torch.float32, device=z.device)
         dbeta = torch.empty(C, dtype=torch.float32, device=z.device)
         ws, n = _ws(rows, C, z.device)
-        L.check(L.lib().epc_bn_apply_bwd(dy.data_ptr(), z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(),
-                                         beta.data_ptr(), ctx.eps, ctx.relu, rows, C, dz.data_ptr(), dgamma.data_ptr(),
-                                         dbeta.data_ptr(), ws.data_ptr(), n, _st()))
+        L.run.epc_bn_apply_bwd(dy, z, mean, var, gamma, beta, ctx.eps, ctx.relu, rows, C, dz, dgamma, dbeta, ws, n)
         return dz, dgamma, dbeta, None, None
 
 
@@ -236,21 +225,16 @@ def _gemm_with_stats(x, W, b, f16x3=None):
     var = torch.empty(cout, dtype=torch.float32, device=x.device)
     if cin == 64 and cout == 64 and x.is_contiguous() and W.is_contiguous() and _GEMM_PRECISION == "bf16x6":
         ws, n = _ws(rows, 64, x.device)      # the thin layers: one launch, moments finished by the last workgroup
-        L.check(L.lib().epc_linear_stats64(x.data_ptr(), W.data_ptr(), b.data_ptr() if b is not None else None, rows,
-                                           z.data_ptr(), mean.data_ptr(), var.data_ptr(), ws.data_ptr(), n, _st()))
+        L.run.epc_linear_stats64(x, W, b, rows, z, mean, var, ws, n)
         return z, mean, var
     tiles = L.lib().epc_gemm_stats_tiles(rows)
     stats = torch.empty(tiles * 3 * cout + 1, dtype=torch.float32, device=x.device)   # per row tile: sum, sum of squares, pivot (+ the f16x3 range word)
     if f16x3 is not None and _FWD_F16X3 and _GEMM_PRECISION == "bf16x6":
-        L.check(L.lib().epc_gemm_f16x3_stats(x.data_ptr(), W.data_ptr(), z.data_ptr(), b.data_ptr() if b is not None else None,
-                                             rows, cout, cin, x.stride(0), x.stride(1), W.stride(0), W.stride(1), cout,
-                                             int(f16x3[0]), int(f16x3[1]), stats.data_ptr(), stats.numel(), mean.data_ptr(),
-                                             var.data_ptr(), _st()))
+        L.run.epc_gemm_f16x3_stats(x, W, z, b, rows, cout, cin, x.stride(0), x.stride(1), W.stride(0), W.stride(1), cout, f16x3[0],
+                                   f16x3[1], stats, stats.numel(), mean, var)
         return z, mean, var
-    fn = L.lib().epc_gemm_bf16_stats if _GEMM_PRECISION == "bf16" else L.lib().epc_gemm_f32_stats
-    L.check(fn(x.data_ptr(), W.data_ptr(), z.data_ptr(), b.data_ptr() if b is not None else None,
-               rows, cout, cin, x.stride(0), x.stride(1), W.stride(0), W.stride(1), cout,
-               stats.data_ptr(), stats.numel(), mean.data_ptr(), var.data_ptr(), _st()))
+    fn = L.run.epc_gemm_bf16_stats if _GEMM_PRECISION == "bf16" else L.run.epc_gemm_f32_stats
+    fn(x, W, z, b, rows, cout, cin, x.stride(0), x.stride(1), W.stride(0), W.stride(1), cout, stats, stats.numel(), mean, var)
     return z, mean, var
 
 
@@ -300,16 +284,14 @@ class LinearBatchNormTrain(torch.autograd.Function):
         if rownorm:
             y = torch.empty_like(z)
             rn = torch.empty(rows, dtype=torch.float32, device=z.device)
-            L.check(L.lib().epc_bn_relu_rownorm_fwd(z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(),
-                                                    beta.data_ptr(), float(eps), rows, C, y.data_ptr(), rn.data_ptr(), _st()))
+            L.run.epc_bn_relu_rownorm_fwd(z, mean, var, gamma, beta, eps, rows, C, y, rn)
             ctx.save_for_backward(x, W, z, mean, var, gamma, beta, rn)
             if ctx.link is not None:
                 lk = ctx.link
                 lk.z, lk.rn, lk.mean, lk.var, lk.gamma, lk.beta, lk.eps = z, rn, mean, var, gamma, beta, float(eps)
         else:
             y = torch.empty_like(z)
-            L.check(L.lib().epc_bn_apply_fwd(z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                             float(eps), int(relu), rows, C, y.data_ptr(), _st()))
+            L.run.epc_bn_apply_fwd(z, mean, var, gamma, beta, eps, relu, rows, C, y)
             ctx.save_for_backward(x, W, z, mean, var, gamma, beta)
         ctx.eps, ctx.relu, ctx.rownorm = float(eps), int(relu), bool(rownorm)
         ctx.mark_non_differentiable(mean, var)
@@ -337,9 +319,7 @@ class LinearBatchNormTrain(torch.autograd.Function):
                     raise EpcNetError(-1, "conv5's features have a second consumer with a gradient: set ops.FUSE_TAIL_BACKWARD = False")
                 dbeta, dgamma = sums[0], sums[1]
                 dz = du          # in place (out of place measured the same: 2.92 ms)
-                L.check(L.lib().epc_bn_apply_bwd_given(du.data_ptr(), z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(),
-                                                       beta.data_ptr(), dbeta.data_ptr(), dgamma.data_ptr(), ctx.eps, rows, C,
-                                                       dz.data_ptr(), _st()))
+                L.run.epc_bn_apply_bwd_given(du, z, mean, var, gamma, beta, dbeta, dgamma, ctx.eps, rows, C, dz)
             else:
                 dz, dgamma, dbeta = _bn_relu_rownorm_bwd(dy, z, rn, mean, var, gamma, beta, ctx.eps)
             dx = gemm(dz, W, trans_b=True, fast=True) if ctx.needs_input_grad[0] else None
@@ -354,15 +334,11 @@ class LinearBatchNormTrain(torch.autograd.Function):
             dW = torch.empty_like(W)
             pf = L.lib().epc_linear_bn_bwd64_partial_floats(rows)
             part = _splitk_ws(pf, z.device)
-            L.check(L.lib().epc_linear_bn_bwd64(dy.data_ptr(), z.data_ptr(), x.data_ptr(), W.data_ptr(), mean.data_ptr(),
-                                                var.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ctx.eps, ctx.relu, rows,
-                                                dx.data_ptr() if dx is not None else None, dW.data_ptr(), dgamma.data_ptr(),
-                                                dbeta.data_ptr(), ws.data_ptr(), n, part.data_ptr(), part.numel(), _st()))
+            L.run.epc_linear_bn_bwd64(dy, z, x, W, mean, var, gamma, beta, ctx.eps, ctx.relu, rows, dx, dW, dgamma, dbeta, ws, n,
+                                      part, part.numel())
             return dx, dW, None, dgamma, dbeta, None, None, None, None, None
         dz = torch.empty_like(z)
-        L.check(L.lib().epc_bn_apply_bwd(dy.data_ptr(), z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(),
-                                         beta.data_ptr(), ctx.eps, ctx.relu, rows, C, dz.data_ptr(),
-                                         dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), n, _st()))
+        L.run.epc_bn_apply_bwd(dy, z, mean, var, gamma, beta, ctx.eps, ctx.relu, rows, C, dz, dgamma, dbeta, ws, n)
         dx = gemm(dz, W, trans_b=True, fast=True) if ctx.needs_input_grad[0] else None
         dW = gemm(x, dz, trans_a=True, splitk=_splitk_for(cin, C, rows), fast=True, deterministic=True)
         return dx, dW, None, dgamma, dbeta, None, None, None, None, None
@@ -379,11 +355,10 @@ class BatchNormReluRowNorm(torch.autograd.Function):
         mean = torch.empty(C, dtype=torch.float32, device=z.device)
         var = torch.empty(C, dtype=torch.float32, device=z.device)
         ws, n = _ws(rows, C, z.device)
-        L.check(L.lib().epc_col_moments(z.data_ptr(), rows, C, mean.data_ptr(), var.data_ptr(), ws.data_ptr(), n, _st()))
+        L.run.epc_col_moments(z, rows, C, mean, var, ws, n)
         f = torch.empty_like(z)
         rn = torch.empty(rows, dtype=torch.float32, device=z.device)
-        L.check(L.lib().epc_bn_relu_rownorm_fwd(z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(),
-                                                beta.data_ptr(), float(eps), rows, C, f.data_ptr(), rn.data_ptr(), _st()))
+        L.run.epc_bn_relu_rownorm_fwd(z, mean, var, gamma, beta, eps, rows, C, f, rn)
         ctx.save_for_backward(z, mean, var, gamma, beta, rn)
         ctx.eps = float(eps)
         ctx.mark_non_differentiable(mean, var)
@@ -407,9 +382,7 @@ def _bn_relu_rownorm_bwd(df, z, rn, mean, var, gamma, beta, eps):
     rowdot = torch.empty(rows, dtype=torch.float32, device=z.device)
     pf = L.lib().epc_bn_relu_rownorm_bwd_partial_floats(rows)
     part = _splitk_ws(pf, z.device)
-    L.check(L.lib().epc_bn_relu_rownorm_bwd(df.data_ptr(), z.data_ptr(), rn.data_ptr(), mean.data_ptr(), var.data_ptr(),
-                                            gamma.data_ptr(), beta.data_ptr(), float(eps), rows, C, dz.data_ptr(),
-                                            sums.data_ptr(), rowdot.data_ptr(), part.data_ptr(), part.numel(), _st()))
+    L.run.epc_bn_relu_rownorm_bwd(df, z, rn, mean, var, gamma, beta, eps, rows, C, dz, sums, rowdot, part, part.numel())
     return dz, sums[1], sums[0]
 
 
@@ -417,8 +390,7 @@ def bn_apply_train(z, mean, var, gamma, beta, eps, relu):
     """act(batch_norm(z)) with GIVEN batch moments (epc_bn_apply_fwd), no autograd: what a fused node leaves unmaterialised."""
     z = z.detach().contiguous()
     y = torch.empty_like(z)
-    L.check(L.lib().epc_bn_apply_fwd(z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                     float(eps), int(bool(relu)), z.shape[0], z.shape[1], y.data_ptr(), _st()))
+    L.run.epc_bn_apply_fwd(z, mean, var, gamma, beta, eps, bool(relu), z.shape[0], z.shape[1], y)
     return y
 
 
@@ -427,8 +399,7 @@ def bn_inference(z, mean, var, gamma, beta, eps=BN_EPS, relu=False):
     z = z.contiguous()
     rows, C = z.shape
     y = torch.empty_like(z)
-    L.check(L.lib().epc_bn_apply_fwd(z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                     float(eps), int(relu), rows, C, y.data_ptr(), _st()))
+    L.run.epc_bn_apply_fwd(z, mean, var, gamma, beta, eps, relu, rows, C, y)
     return y
 
 
@@ -451,8 +422,7 @@ class KnnGraph:
             dev = self.xyz.device
             oc = torch.empty(self.num_clouds, dtype=torch.int32, device=dev)
             ol = torch.empty((self.num_clouds, self.n), dtype=torch.int32, device=dev)
-            L.check(L.lib().epc_knn_overflow_lists(self.cnt.data_ptr(), L.EPC_KNN_CAP, self.num_clouds, self.n, oc.data_ptr(),
-                                                   ol.data_ptr(), _st()))
+            L.run.epc_knn_overflow_lists(self.cnt, L.EPC_KNN_CAP, self.num_clouds, self.n, oc, ol)
             self._overflow = (oc, ol)
         return self._overflow
 
@@ -461,10 +431,8 @@ class KnnGraph:
         backward of every block of a step gathers over it."""
         if self._transposed is None:
             rdeg, roff, cursor, rlist, oc, ol = self._build_transposed()
-            L.check(L.lib().epc_knn_transpose(self.idx.data_ptr(), self.cnt.data_ptr(), L.EPC_KNN_CAP, self.num_clouds, self.n,
-                                              rdeg.data_ptr(), roff.data_ptr(), cursor.data_ptr(), rlist.data_ptr(), _st()))
-            L.check(L.lib().epc_knn_overflow_lists(self.cnt.data_ptr(), L.EPC_KNN_CAP, self.num_clouds, self.n, oc.data_ptr(),
-                                                   ol.data_ptr(), _st()))
+            L.run.epc_knn_transpose(self.idx, self.cnt, L.EPC_KNN_CAP, self.num_clouds, self.n, rdeg, roff, cursor, rlist)
+            L.run.epc_knn_overflow_lists(self.cnt, L.EPC_KNN_CAP, self.num_clouds, self.n, oc, ol)
             self._transposed, self._overflow = (rdeg, roff, rlist), (oc, ol)
         return self._transposed
 
@@ -539,10 +507,8 @@ class CloudBank:
             rdeg, roff, rlist = g.transposed()
             oc, ol = g.overflow()
             self._store_status.zero_()
-            L.check(L.lib().epc_bank_store(self.records.data_ptr(), self.capacity, self._size, g.num_clouds, self.n, self.cap,
-                                           part.data_ptr(), g.kth.data_ptr(), g.cnt.data_ptr(), g.idx.data_ptr(), rdeg.data_ptr(),
-                                           roff.data_ptr(), rlist.data_ptr(), oc.data_ptr(), ol.data_ptr(),
-                                           self._store_status.data_ptr(), _st()))
+            L.run.epc_bank_store(self.records, self.capacity, self._size, g.num_clouds, self.n, self.cap, part, g.kth, g.cnt,
+                                 g.idx, rdeg, roff, rlist, oc, ol, self._store_status)
             if int(self._store_status.item()) != 0:
                 raise EpcNetError(-1, "CloudBank.add: a graph of clouds %d..%d does not fit the 16-bit record format; nothing "
                                       "of that chunk was stored" % (a, a + g.num_clouds - 1))
@@ -573,10 +539,8 @@ class CloudBank:
             raise EpcNetError(-1, "CloudBank.assemble: `out` was made for %d ids, got %d" % (int(o["xyz"].shape[0]), T))
         if self._size == 0:
             raise EpcNetError(-1, "CloudBank.assemble: the bank is empty")
-        L.check(L.lib().epc_bank_assemble(self.records.data_ptr(), self._size, ids.data_ptr(), T, self.n, self.cap,
-                                          o["xyz"].data_ptr(), o["kth"].data_ptr(), o["cnt"].data_ptr(), o["idx"].data_ptr(),
-                                          o["rdeg"].data_ptr(), o["roff"].data_ptr(), o["rlist"].data_ptr(), o["ovf_cnt"].data_ptr(),
-                                          o["ovf_list"].data_ptr(), self.status.data_ptr(), o["poison"].data_ptr(), _st()))
+        L.run.epc_bank_assemble(self.records, self._size, ids, T, self.n, self.cap, o["xyz"], o["kth"], o["cnt"], o["idx"],
+                                o["rdeg"], o["roff"], o["rlist"], o["ovf_cnt"], o["ovf_list"], self.status, o["poison"])
         graph = KnnGraph.from_parts(o["xyz"], o["kth"], o["idx"], o["cnt"], (o["rdeg"], o["roff"], o["rlist"]),
                                     (o["ovf_cnt"], o["ovf_list"]))
         return o["xyz"], graph
@@ -600,9 +564,7 @@ class NeighbourMean(torch.autograd.Function):
         ctx.graph, ctx.k = graph, int(k)
         xm = torch.empty_like(x)
         g = graph
-        L.check(L.lib().epc_neighbour_mean_fwd(x.data_ptr(), g.xyz.data_ptr(), g.idx.data_ptr(), g.cnt.data_ptr(),
-                                               g.kth.data_ptr(), L.EPC_KNN_CAP, g.num_clouds, g.n, int(k), xm.data_ptr(),
-                                               _st()))
+        L.run.epc_neighbour_mean_fwd(x, g.xyz, g.idx, g.cnt, g.kth, L.EPC_KNN_CAP, g.num_clouds, g.n, k, xm)
         return xm
 
     @staticmethod
@@ -611,9 +573,8 @@ class NeighbourMean(torch.autograd.Function):
         dxm = dxm.contiguous()
         dx = torch.empty_like(dxm)
         rdeg, roff, rlist = g.transposed()
-        L.check(L.lib().epc_neighbour_mean_bwd_gather(dxm.data_ptr(), g.xyz.data_ptr(), g.cnt.data_ptr(), g.kth.data_ptr(),
-                                                      L.EPC_KNN_CAP, rdeg.data_ptr(), roff.data_ptr(), rlist.data_ptr(),
-                                                      g.num_clouds, g.n, ctx.k, dx.data_ptr(), _st()))
+        L.run.epc_neighbour_mean_bwd_gather(dxm, g.xyz, g.cnt, g.kth, L.EPC_KNN_CAP, rdeg, roff, rlist, g.num_clouds, g.n, ctx.k,
+                                            dx)
         return dx, None, None
 
 
@@ -627,9 +588,7 @@ class NeighbourMeanDiff(torch.autograd.Function):
         ctx.graph, ctx.k = graph, int(k)
         xm, diff = torch.empty_like(x), torch.empty_like(x)
         g = graph
-        L.check(L.lib().epc_neighbour_mean_diff_fwd(x.data_ptr(), g.xyz.data_ptr(), g.idx.data_ptr(), g.cnt.data_ptr(),
-                                                    g.kth.data_ptr(), L.EPC_KNN_CAP, g.num_clouds, g.n, int(k),
-                                                    xm.data_ptr(), diff.data_ptr(), _st()))
+        L.run.epc_neighbour_mean_diff_fwd(x, g.xyz, g.idx, g.cnt, g.kth, L.EPC_KNN_CAP, g.num_clouds, g.n, k, xm, diff)
         return xm, diff
 
     @staticmethod
@@ -638,10 +597,8 @@ class NeighbourMeanDiff(torch.autograd.Function):
         dxm, ddiff = dxm.contiguous(), ddiff.contiguous()
         dx = torch.empty_like(dxm)
         rdeg, roff, rlist = g.transposed()
-        L.check(L.lib().epc_neighbour_mean_diff_bwd_gather(dxm.data_ptr(), ddiff.data_ptr(), g.xyz.data_ptr(),
-                                                           g.cnt.data_ptr(), g.kth.data_ptr(), L.EPC_KNN_CAP, rdeg.data_ptr(),
-                                                           roff.data_ptr(), rlist.data_ptr(), g.num_clouds, g.n, ctx.k,
-                                                           dx.data_ptr(), _st()))
+        L.run.epc_neighbour_mean_diff_bwd_gather(dxm, ddiff, g.xyz, g.cnt, g.kth, L.EPC_KNN_CAP, rdeg, roff, rlist, g.num_clouds,
+                                                 g.n, ctx.k, dx)
         return dx, None, None
 
 
@@ -660,22 +617,16 @@ class ProxyConvTail(torch.autograd.Function):
         assert x.shape[1] == 64 and Wa.shape == (64, 64) and Wb.shape == (64, 64) and _GEMM_PRECISION == "bf16x6"
         Wa, Wb = Wa.contiguous(), Wb.contiguous()
         g = graph
-        lib = L.lib()
         xm, diff = torch.empty_like(x), torch.empty_like(x)
-        L.check(lib.epc_neighbour_mean_diff_fwd(x.data_ptr(), g.xyz.data_ptr(), g.idx.data_ptr(), g.cnt.data_ptr(),
-                                                g.kth.data_ptr(), L.EPC_KNN_CAP, g.num_clouds, g.n, int(k), xm.data_ptr(),
-                                                diff.data_ptr(), _st()))
+        L.run.epc_neighbour_mean_diff_fwd(x, g.xyz, g.idx, g.cnt, g.kth, L.EPC_KNN_CAP, g.num_clouds, g.n, k, xm, diff)
         za, ma, va = _gemm_with_stats(diff, Wa, ba)
         zb = torch.empty_like(za)
         mb = torch.empty(64, dtype=torch.float32, device=x.device)
         vb = torch.empty(64, dtype=torch.float32, device=x.device)
         ws, n = _ws(rows, 64, x.device)
-        L.check(lib.epc_linear_stats64_bn(za.data_ptr(), ma.data_ptr(), va.data_ptr(), ga.data_ptr(), bta.data_ptr(), float(eps),
-                                          Wb.data_ptr(), bb.data_ptr() if bb is not None else None, rows, zb.data_ptr(),
-                                          mb.data_ptr(), vb.data_ptr(), ws.data_ptr(), n, _st()))
+        L.run.epc_linear_stats64_bn(za, ma, va, ga, bta, eps, Wb, bb, rows, zb, mb, vb, ws, n)
         out = torch.empty_like(x)
-        L.check(lib.epc_bn_apply_add_fwd(zb.data_ptr(), mb.data_ptr(), vb.data_ptr(), gb.data_ptr(), btb.data_ptr(), float(eps), 1,
-                                         rows, 64, xm.data_ptr(), out.data_ptr(), _st()))
+        L.run.epc_bn_apply_add_fwd(zb, mb, vb, gb, btb, eps, 1, rows, 64, xm, out)
         ctx.save_for_backward(diff, Wa, za, ma, va, ga, bta, Wb, zb, mb, vb, gb, btb)
         ctx.graph, ctx.k, ctx.eps = graph, int(k), float(eps)
         ctx.mark_non_differentiable(za, ma, va, zb, mb, vb)
@@ -690,30 +641,25 @@ class ProxyConvTail(torch.autograd.Function):
         dout = dout.contiguous()
         rows = za.shape[0]
         dev = za.device
-        lib, g, eps = L.lib(), ctx.graph, ctx.eps
+        g, eps = ctx.graph, ctx.eps
         new = lambda: torch.empty(64, dtype=torch.float32, device=dev)
         ws, n = _ws(rows, 64, dev)
-        pf = lib.epc_linear_bn_bwd64_partial_floats(rows)
+        pf = L.lib().epc_linear_bn_bwd64_partial_floats(rows)
         part = _splitk_ws(pf, dev)
         # conv_b: its input is relu(bn(z_a)), re-formed from z_a
         dta, dWb, dgb, dbtb = torch.empty_like(za), torch.empty_like(Wb), new(), new()
-        L.check(lib.epc_linear_bn_bwd64_ex(dout.data_ptr(), zb.data_ptr(), za.data_ptr(), ma.data_ptr(), va.data_ptr(),
-                                           ga.data_ptr(), bta.data_ptr(), Wb.data_ptr(), mb.data_ptr(), vb.data_ptr(),
-                                           gb.data_ptr(), btb.data_ptr(), eps, 1, rows, dta.data_ptr(), None, dWb.data_ptr(),
-                                           dgb.data_ptr(), dbtb.data_ptr(), ws.data_ptr(), n, part.data_ptr(), part.numel(), _st()))
+        L.run.epc_linear_bn_bwd64_ex(dout, zb, za, ma, va, ga, bta, Wb, mb, vb, gb, btb, eps, 1, rows, dta, None, dWb, dgb, dbtb,
+                                     ws, n, part, part.numel())
         # conv_a: the gradient of its input (xm - x) leaves as s = ddiff + dout, dout being what reaches xm by the residual
         s, dWa, dga, dbta = torch.empty_like(za), torch.empty_like(Wa), new(), new()
-        L.check(lib.epc_linear_bn_bwd64_ex(dta.data_ptr(), za.data_ptr(), diff.data_ptr(), None, None, None, None, Wa.data_ptr(),
-                                           ma.data_ptr(), va.data_ptr(), ga.data_ptr(), bta.data_ptr(), eps, 1, rows, s.data_ptr(),
-                                           dout.data_ptr(), dWa.data_ptr(), dga.data_ptr(), dbta.data_ptr(), ws.data_ptr(), n,
-                                           part.data_ptr(), part.numel(), _st()))
+        L.run.epc_linear_bn_bwd64_ex(dta, za, diff, None, None, None, None, Wa, ma, va, ga, bta, eps, 1, rows, s, dout, dWa, dga,
+                                     dbta, ws, n, part, part.numel())
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(za)
             rdeg, roff, rlist = g.transposed()
-            L.check(lib.epc_neighbour_mean_diff_bwd_gather_sum(s.data_ptr(), dout.data_ptr(), g.xyz.data_ptr(), g.cnt.data_ptr(),
-                                                               g.kth.data_ptr(), L.EPC_KNN_CAP, rdeg.data_ptr(), roff.data_ptr(),
-                                                               rlist.data_ptr(), g.num_clouds, g.n, ctx.k, dx.data_ptr(), _st()))
+            L.run.epc_neighbour_mean_diff_bwd_gather_sum(s, dout, g.xyz, g.cnt, g.kth, L.EPC_KNN_CAP, rdeg, roff, rlist,
+                                                         g.num_clouds, g.n, ctx.k, dx)
         # (bias gradients in front of a training-mode BatchNorm are exactly zero: LinearBatchNormTrain)
         return dx, None, None, dWa, None, dga, dbta, dWb, None, dgb, dbtb, None
 
@@ -726,6 +672,11 @@ CHAIN_PERSIST_FWD = True
 CHAIN_SPIN_TICKS = 0          # spin budget of a grid barrier in 10-ns ticks; 0: the library's default (a quarter second)
 CHAIN_WS_ERR_WORD = 2112      # the workspace's sticky error word as an int32 index (PST_W_ERR of csrc/train_chain_persist.hip)
 _CHAIN_WS = {}
+
+
+def _ptr_or_null(t):
+    """A tensor's address for a structure field, None (a null pointer) for None."""
+    return t.data_ptr() if t is not None else None
 _CHAIN_PERSIST_LAUNCHES = 0   # persistent launches issued so far (a step asks whether its forward took one: chain_persist_launches)
 
 
@@ -739,7 +690,7 @@ def chain_workspace(device):
             raise RuntimeError("the persistent chain's workspace must exist before a graph capture (its one-time zeroing would be "
                                "replayed): run one eager step first, as TrainStep's warm-up does")
         t = torch.empty(L.lib().epc_chain_persist_workspace_bytes(), dtype=torch.uint8, device=device)
-        L.check(L.lib().epc_chain_persist_init(t.data_ptr(), _st()))
+        L.run.epc_chain_persist_init(t)
         _CHAIN_WS[key] = t
     return t
 
@@ -764,9 +715,9 @@ def chain_persist_check(device=None):
     for key, t in list(_CHAIN_WS.items()):
         if device is not None and key != (device.type, device.index):
             continue
-        rc = L.lib().epc_chain_persist_status(t.data_ptr(), _st())
+        rc = L.lib().epc_chain_persist_status(t.data_ptr(), L.current_stream())      # (raw: the status decides about the reset)
         if rc != L.EPC_OK:
-            L.lib().epc_chain_persist_reset(t.data_ptr(), _st())
+            L.lib().epc_chain_persist_reset(t.data_ptr(), L.current_stream())
             L.check(rc)
 
 
@@ -801,7 +752,6 @@ class ProxyConvChain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z01, graph, k, eps, nblocks, pieces_fwd, pieces_bwd, want_bf16, *params):
-        lib = L.lib()
         z01 = z01.contiguous()
         rows = int(z01.shape[0])
         assert z01.shape[1] == 64 and rows == graph.num_clouds * graph.n
@@ -819,10 +769,10 @@ class ProxyConvChain(torch.autograd.Function):
         z0s = [z01] + [new() for _ in range(nblocks - 1)] + [None]
         tens = [(new(), new(), new()) for _ in range(nblocks)]
         moms = [tuple(vec() for _ in range(6)) for _ in range(nblocks)]
-        if CHAIN_PERSIST_FWD and nblocks <= L.EPC_CHAIN_MAX_BLOCKS and lib.epc_chain_persist_ok(rows):
-            ProxyConvChain._launch_persistent(lib, graph, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16)
+        if CHAIN_PERSIST_FWD and nblocks <= L.EPC_CHAIN_MAX_BLOCKS and L.lib().epc_chain_persist_ok(rows):
+            ProxyConvChain._launch_persistent(graph, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16)
         else:
-            ProxyConvChain._launch_chain(lib, graph, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16)
+            ProxyConvChain._launch_chain(graph, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16)
         saved, outs = [], []
         for b in range(nblocks):
             (d, za, zb), (m0, v0, ma, va, mb, vb) = tens[b], moms[b]
@@ -836,40 +786,32 @@ class ProxyConvChain(torch.autograd.Function):
         return (cat,) + tuple(outs) + (cat16,)
 
     @staticmethod
-    def _launch_chain(lib, g, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16):
+    def _launch_chain(g, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16):
         """The forward as the launch chain: z01's moment partials, then gather, mid and head (or tail) per block."""
         rows, width, dev, nblocks = int(cat.shape[0]), int(cat.shape[1]), cat.device, len(blocks)
-        stats = lambda: torch.empty(lib.epc_chain_parts(rows) * 192, dtype=torch.float32, device=dev)
-        ptr = lambda t: t.data_ptr() if t is not None else None
+        stats = lambda: torch.empty(L.lib().epc_chain_parts(rows) * 192, dtype=torch.float32, device=dev)
         in_stats, in_bias = stats(), None
-        L.check(lib.epc_chain_stats(z0s[0].data_ptr(), rows, in_stats.data_ptr(), _st()))
+        L.run.epc_chain_stats(z0s[0], rows, in_stats)
         for b, (W0, b0, g0, bt0, Wa, ba, ga, bta, Wb, bb, gb, btb) in enumerate(blocks):
             z0, z0n, (d, za, zb), (m0, v0, ma, va, mb, vb) = z0s[b], z0s[b + 1], tens[b], moms[b]
             xm = torch.empty_like(d)      # (the persistent kernel keeps the neighbour means in registers)
             st_a, st_b = stats(), stats()
-            L.check(lib.epc_chain_fwd_gather(z0.data_ptr(), in_stats.data_ptr(), ptr(in_bias), m0.data_ptr(), v0.data_ptr(),
-                                             g0.data_ptr(), bt0.data_ptr(), float(eps), g.xyz.data_ptr(), g.idx.data_ptr(),
-                                             g.cnt.data_ptr(), g.kth.data_ptr(), L.EPC_KNN_CAP, g.num_clouds, g.n, int(k),
-                                             Wa.data_ptr(), ptr(ba), xm.data_ptr(), d.data_ptr(), za.data_ptr(), st_a.data_ptr(),
-                                             int(pieces_fwd), _st()))
-            L.check(lib.epc_chain_fwd_linear(za.data_ptr(), st_a.data_ptr(), ptr(ba), ma.data_ptr(), va.data_ptr(), ga.data_ptr(),
-                                             bta.data_ptr(), float(eps), None, None, 0, None, Wb.data_ptr(), ptr(bb), zb.data_ptr(),
-                                             st_b.data_ptr(), rows, int(pieces_fwd), _st()))
-            slice_ptr = cat.data_ptr() + 4 * 64 * b
-            slice16 = cat16.data_ptr() + 2 * 64 * b if cat16 is not None else None
+            L.run.epc_chain_fwd_gather(z0, in_stats, in_bias, m0, v0, g0, bt0, eps, g.xyz, g.idx, g.cnt, g.kth, L.EPC_KNN_CAP,
+                                       g.num_clouds, g.n, k, Wa, ba, xm, d, za, st_a, pieces_fwd)
+            L.run.epc_chain_fwd_linear(za, st_a, ba, ma, va, ga, bta, eps, None, None, 0, None, Wb, bb, zb, st_b, rows, pieces_fwd)
+            out, out16 = cat[:, 64 * b:], (cat16[:, 64 * b:] if cat16 is not None else None)      # row stride: width
             # head: the block's output into its slice of the concat and, before the last block's tail, the next block's leading conv
             W0n, b0n = (blocks[b + 1][0], blocks[b + 1][1]) if b + 1 < nblocks else (None, None)
             st0n = stats() if z0n is not None else None
-            L.check(lib.epc_chain_fwd_linear(zb.data_ptr(), st_b.data_ptr(), ptr(bb), mb.data_ptr(), vb.data_ptr(), gb.data_ptr(),
-                                             btb.data_ptr(), float(eps), xm.data_ptr(), slice_ptr, width, slice16, ptr(W0n),
-                                             ptr(b0n), ptr(z0n), ptr(st0n), rows, int(pieces_fwd), _st()))
+            L.run.epc_chain_fwd_linear(zb, st_b, bb, mb, vb, gb, btb, eps, xm, out, width, out16, W0n, b0n, z0n, st0n,
+                                       rows, pieces_fwd)
             in_stats, in_bias = st0n, b0n
 
     @staticmethod
-    def _launch_persistent(lib, g, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16):
+    def _launch_persistent(g, k, eps, pieces_fwd, blocks, z0s, tens, moms, cat, cat16):
         """The whole forward as one launch (epc_chain_fwd_persist)."""
         nblocks = len(blocks)
-        ptr = lambda t: t.data_ptr() if t is not None else None
+        ptr = _ptr_or_null
         a = L.ChainFwdArgs()
         a.nblocks = nblocks
         a.xyz, a.idx, a.cnt, a.kth = g.xyz.data_ptr(), g.idx.data_ptr(), g.cnt.data_ptr(), g.kth.data_ptr()
@@ -887,7 +829,7 @@ class ProxyConvChain(torch.autograd.Function):
             B.z0, B.z0_next = z0s[b].data_ptr(), ptr(z0s[b + 1])
             B.mean0, B.var0, B.mean_a, B.var_a, B.mean_b, B.var_b = (t.data_ptr() for t in moms[b])
             B.d, B.za, B.zb = (t.data_ptr() for t in tens[b])
-        L.check(lib.epc_chain_fwd_persist(ctypes.byref(a), int(pieces_fwd), _st()))
+        L.run.epc_chain_fwd_persist(ctypes.byref(a), pieces_fwd)
         global _CHAIN_PERSIST_LAUNCHES
         _CHAIN_PERSIST_LAUNCHES += 1
 
@@ -897,7 +839,6 @@ class ProxyConvChain(torch.autograd.Function):
         n_in = 8 + ctx.n_params
         if dcat is None:
             return (None,) * n_in
-        lib = L.lib()
         sv = ctx.saved_tensors
         cat = sv[0]
         per = [sv[1 + 10 * b: 11 + 10 * b] for b in range(nb)]          # z0, d, za, zb, m0, v0, ma, va, mb, vb
@@ -907,7 +848,7 @@ class ProxyConvChain(torch.autograd.Function):
         rows, width = int(cat.shape[0]), int(cat.shape[1])
         dev = cat.device
         g, eps, k, pc = ctx.graph, ctx.eps, ctx.k, ctx.pieces_bwd
-        P = lib.epc_chain_parts(rows)
+        P = L.lib().epc_chain_parts(rows)
         new = lambda: torch.empty((rows, 64), dtype=torch.float32, device=dev)
         vec = lambda: torch.empty(64, dtype=torch.float32, device=dev)
         sums = lambda: torch.empty(P * 128, dtype=torch.float32, device=dev)
@@ -920,43 +861,34 @@ class ProxyConvChain(torch.autograd.Function):
         at_of = lambda b: 0 if b == 0 else 10 + 12 * (b - 1)          # index of block b's first parameter in `params`
         z_b, m_b, v_b = per[nb - 1][3], per[nb - 1][8], per[nb - 1][9]
         sums_b = sums()
-        last = dcat.data_ptr() + 4 * 64 * (nb - 1)
-        L.check(lib.epc_chain_sums(last, width, z_b.data_ptr(), m_b.data_ptr(), v_b.data_ptr(), blocks[nb - 1][10].data_ptr(),
-                                   blocks[nb - 1][11].data_ptr(), eps, rows, sums_b.data_ptr(), _st()))
+        L.run.epc_chain_sums(dcat[:, 64 * (nb - 1):], width, z_b, m_b, v_b, blocks[nb - 1][10], blocks[nb - 1][11], eps, rows, sums_b)
         gout = None
         dz01 = None
         for b in range(nb - 1, -1, -1):
             z0, d, za, zb, m0, v0, ma, va, mb, vb = per[b]
             W0, b0, g0, bt0, Wa, ba, ga, bta, Wb, bb, gb, btb = blocks[b]
             base = at_of(b) + (2 if b == 0 else 4)                   # Wa's index
-            dy_ptr, dy_stride = (gout.data_ptr(), 64) if gout is not None else (dcat.data_ptr() + 4 * 64 * b, width)
+            dy, dy_stride = (gout, 64) if gout is not None else (dcat[:, 64 * b:], width)
             # conv_b: its input is relu(bn_a(za)), re-formed from za; leaves conv_a's BatchNorm sums
             dya, dgb, dbtb, sums_a = new(), vec(), vec(), sums()
-            L.check(lib.epc_chain_bwd_linear(dy_ptr, dy_stride, zb.data_ptr(), mb.data_ptr(), vb.data_ptr(), gb.data_ptr(),
-                                             btb.data_ptr(), eps, sums_b.data_ptr(), dgb.data_ptr(), dbtb.data_ptr(), Wb.data_ptr(),
-                                             za.data_ptr(), 64, ma.data_ptr(), va.data_ptr(), ga.data_ptr(), bta.data_ptr(),
-                                             dya.data_ptr(), None, 0, parts[layer_at].data_ptr(), za.data_ptr(), ma.data_ptr(),
-                                             va.data_ptr(), ga.data_ptr(), bta.data_ptr(), sums_a.data_ptr(), rows, pc, _st()))
+            L.run.epc_chain_bwd_linear(dy, dy_stride, zb, mb, vb, gb, btb, eps, sums_b, dgb, dbtb, Wb, za, 64, ma, va, ga, bta,
+                                       dya, None, 0, parts[layer_at], za, ma, va, ga, bta, sums_a, rows, pc)
             dWb = torch.empty_like(Wb)
             layer_dw.append(dWb)
             layer_at += 1
             grads[base + 4], grads[base + 6], grads[base + 7] = dWb, dgb, dbtb
             # conv_a: the gradient of its input d = xm - x leaves as s = dd + dout (dout reaches xm by the residual path)
             s_, dga, dbta = new(), vec(), vec()
-            L.check(lib.epc_chain_bwd_linear(dya.data_ptr(), 64, za.data_ptr(), ma.data_ptr(), va.data_ptr(), ga.data_ptr(),
-                                             bta.data_ptr(), eps, sums_a.data_ptr(), dga.data_ptr(), dbta.data_ptr(), Wa.data_ptr(),
-                                             d.data_ptr(), 64, None, None, None, None, s_.data_ptr(), dy_ptr, dy_stride,
-                                             parts[layer_at].data_ptr(), None, None, None, None, None, None, rows, pc, _st()))
+            L.run.epc_chain_bwd_linear(dya, 64, za, ma, va, ga, bta, eps, sums_a, dga, dbta, Wa, d, 64, None, None, None, None, s_,
+                                       dy, dy_stride, parts[layer_at], None, None, None, None, None, None, rows, pc)
             dWa = torch.empty_like(Wa)
             layer_dw.append(dWa)
             layer_at += 1
             grads[base + 0], grads[base + 2], grads[base + 3] = dWa, dga, dbta
             # the gather's transpose: dx = mask^T s / k - (s - dout); leaves the leading BatchNorm's sums
             dxx, sums_0 = new(), sums()
-            L.check(lib.epc_chain_bwd_gather(s_.data_ptr(), dy_ptr, dy_stride, rdeg.data_ptr(), roff.data_ptr(), rlist.data_ptr(),
-                                             ovc.data_ptr(), ovl.data_ptr(), g.xyz.data_ptr(), g.kth.data_ptr(), g.num_clouds, g.n,
-                                             k, z0.data_ptr(), m0.data_ptr(), v0.data_ptr(), g0.data_ptr(), bt0.data_ptr(), eps,
-                                             sums_0.data_ptr(), dxx.data_ptr(), _st()))
+            L.run.epc_chain_bwd_gather(s_, dy, dy_stride, rdeg, roff, rlist, ovc, ovl, g.xyz, g.kth, g.num_clouds, g.n, k, z0,
+                                       m0, v0, g0, bt0, eps, sums_0, dxx)
             dg0, dbt0 = vec(), vec()
             if b > 0:
                 # the leading conv: its input is the previous block's output (a slice of cat); its dx, plus the concat's gradient of
@@ -964,13 +896,10 @@ class ProxyConvChain(torch.autograd.Function):
                 pz = per[b - 1]
                 pgb, pbtb = blocks[b - 1][10], blocks[b - 1][11]
                 gnew, sums_prev = new(), sums()
-                prev_slice = 4 * 64 * (b - 1)
-                L.check(lib.epc_chain_bwd_linear(dxx.data_ptr(), 64, z0.data_ptr(), m0.data_ptr(), v0.data_ptr(), g0.data_ptr(),
-                                                 bt0.data_ptr(), eps, sums_0.data_ptr(), dg0.data_ptr(), dbt0.data_ptr(),
-                                                 W0.data_ptr(), cat.data_ptr() + prev_slice, width, None, None, None, None,
-                                                 gnew.data_ptr(), dcat.data_ptr() + prev_slice, width, parts[layer_at].data_ptr(),
-                                                 pz[3].data_ptr(), pz[8].data_ptr(), pz[9].data_ptr(), pgb.data_ptr(), pbtb.data_ptr(),
-                                                 sums_prev.data_ptr(), rows, pc, _st()))
+                prev = slice(64 * (b - 1), None)
+                L.run.epc_chain_bwd_linear(dxx, 64, z0, m0, v0, g0, bt0, eps, sums_0, dg0, dbt0, W0, cat[:, prev], width, None, None,
+                                           None, None, gnew, dcat[:, prev], width, parts[layer_at], pz[3], pz[8], pz[9], pgb, pbtb,
+                                           sums_prev, rows, pc)
                 dW0 = torch.empty_like(W0)
                 layer_dw.append(dW0)
                 layer_at += 1
@@ -979,12 +908,9 @@ class ProxyConvChain(torch.autograd.Function):
                 gout, sums_b = gnew, sums_prev
             else:
                 dz01 = new()
-                L.check(lib.epc_chain_bn_bwd(dxx.data_ptr(), z0.data_ptr(), m0.data_ptr(), v0.data_ptr(), g0.data_ptr(), bt0.data_ptr(),
-                                             eps, sums_0.data_ptr(), dg0.data_ptr(), dbt0.data_ptr(), rows, dz01.data_ptr(), _st()))
+                L.run.epc_chain_bn_bwd(dxx, z0, m0, v0, g0, bt0, eps, sums_0, dg0, dbt0, rows, dz01)
                 grads[0], grads[1] = dg0, dbt0
-        pa = (ctypes.c_void_p * n_layers)(*[parts[l].data_ptr() for l in range(n_layers)])
-        pw = (ctypes.c_void_p * n_layers)(*[w.data_ptr() for w in layer_dw])
-        L.check(lib.epc_chain_dw_sum(n_layers, pa, pw, rows, _st()))
+        L.run.epc_chain_dw_sum(n_layers, _ptr_array(list(parts)), _ptr_array(layer_dw), rows)
         return (dz01 if ctx.needs_input_grad[0] else None, None, None, None, None, None, None, None) + tuple(grads)
 
 
@@ -997,7 +923,7 @@ class RowL2Normalize(torch.autograd.Function):
         rows, C = x.shape
         y = torch.empty_like(x)
         rn = torch.empty(rows, dtype=torch.float32, device=x.device)
-        L.check(L.lib().epc_rownorm_fwd(x.data_ptr(), rows, C, y.data_ptr(), rn.data_ptr(), _st()))
+        L.run.epc_rownorm_fwd(x, rows, C, y, rn)
         ctx.save_for_backward(y, rn)
         return y
 
@@ -1006,7 +932,7 @@ class RowL2Normalize(torch.autograd.Function):
         y, rn = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(y)
-        L.check(L.lib().epc_rownorm_bwd(dy.data_ptr(), y.data_ptr(), rn.data_ptr(), y.shape[0], y.shape[1], dx.data_ptr(), _st()))
+        L.run.epc_rownorm_bwd(dy, y, rn, y.shape[0], y.shape[1], dx)
         return dx
 
 
@@ -1022,8 +948,7 @@ class VladNormalize(torch.autograd.Function):
         out = torch.empty_like(raw)
         r1 = torch.empty((B, C), dtype=torch.float32, device=raw.device)
         r2 = torch.empty((B,), dtype=torch.float32, device=raw.device)
-        L.check(L.lib().epc_vlad_normalize_fwd(raw.data_ptr(), a_sum.data_ptr(), w2.data_ptr(), B, F, C, out.data_ptr(),
-                                               r1.data_ptr(), r2.data_ptr(), _st()))
+        L.run.epc_vlad_normalize_fwd(raw, a_sum, w2, B, F, C, out, r1, r2)
         ctx.save_for_backward(out, r1, r2, w2, a_sum)
         return out
 
@@ -1034,12 +959,11 @@ class VladNormalize(torch.autograd.Function):
         B, F, C = out.shape
         draw = torch.empty_like(out)
         da = torch.empty_like(a_sum)
-        L.check(L.lib().epc_vlad_normalize_bwd(dout.data_ptr(), out.data_ptr(), r1.data_ptr(), r2.data_ptr(), w2.data_ptr(),
-                                               B, F, C, draw.data_ptr(), da.data_ptr(), _st()))
+        L.run.epc_vlad_normalize_bwd(dout, out, r1, r2, w2, B, F, C, draw, da)
         dw2 = None
         if ctx.needs_input_grad[2]:
             dw2 = torch.empty(w2.shape, dtype=torch.float32, device=out.device)
-            L.check(L.lib().epc_vlad_w2_grad(draw.data_ptr(), a_sum.data_ptr(), B, F, C, dw2.data_ptr(), _st()))
+            L.run.epc_vlad_w2_grad(draw, a_sum, B, F, C, dw2)
         return draw, da, dw2
 
 
@@ -1054,8 +978,7 @@ class LazyQuadrupletLoss(torch.autograd.Function):
         Nn = neg.shape[1]
         loss = torch.empty((), dtype=torch.float32, device=q.device)
         sel = torch.empty((B, 3), dtype=torch.int32, device=q.device)
-        L.check(L.lib().epc_lazy_quadruplet_loss_fwd(q.data_ptr(), pos.data_ptr(), neg.data_ptr(), other.data_ptr(), B, P, Nn,
-                                                     D, float(m1), float(m2), loss.data_ptr(), sel.data_ptr(), _st()))
+        L.run.epc_lazy_quadruplet_loss_fwd(q, pos, neg, other, B, P, Nn, D, m1, m2, loss, sel)
         ctx.save_for_backward(q, pos, neg, other, sel)
         return loss
 
@@ -1066,9 +989,7 @@ class LazyQuadrupletLoss(torch.autograd.Function):
         B, P, D = pos.shape
         Nn = neg.shape[1]
         dq, dpos, dneg, dother = (torch.empty_like(t) for t in (q, pos, neg, other))
-        L.check(L.lib().epc_lazy_quadruplet_loss_bwd(q.data_ptr(), pos.data_ptr(), neg.data_ptr(), other.data_ptr(),
-                                                     sel.data_ptr(), dloss.data_ptr(), B, P, Nn, D, dq.data_ptr(),
-                                                     dpos.data_ptr(), dneg.data_ptr(), dother.data_ptr(), _st()))
+        L.run.epc_lazy_quadruplet_loss_bwd(q, pos, neg, other, sel, dloss, B, P, Nn, D, dq, dpos, dneg, dother)
         return dq, dpos, dneg, dother, None, None
 
 
@@ -1080,7 +1001,7 @@ class Softmax64(torch.autograd.Function):
         x = x.contiguous()
         assert x.shape[1] == 64
         y = torch.empty_like(x)
-        L.check(L.lib().epc_softmax64_fwd(x.data_ptr(), x.shape[0], y.data_ptr(), _st()))
+        L.run.epc_softmax64_fwd(x, x.shape[0], y)
         ctx.save_for_backward(y)
         return y
 
@@ -1089,7 +1010,7 @@ class Softmax64(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(y)
-        L.check(L.lib().epc_softmax64_bwd(dy.data_ptr(), y.data_ptr(), y.shape[0], dx.data_ptr(), _st()))
+        L.run.epc_softmax64_bwd(dy, y, y.shape[0], dx)
         return dx
 
 
@@ -1135,16 +1056,14 @@ class VladAssignAggregate(torch.autograd.Function):
             mean = torch.empty(64, dtype=torch.float32, device=f.device)
             var = torch.empty(64, dtype=torch.float32, device=f.device)
             ws, n = _ws(rows, 64, f.device)
-            L.check(L.lib().epc_col_moments(z.data_ptr(), rows, 64, mean.data_ptr(), var.data_ptr(), ws.data_ptr(), n, _st()))
+            L.run.epc_col_moments(z, rows, 64, mean, var, ws, n)
         B = rows // n_points
         a = torch.empty_like(z)
         a_sum = torch.empty((B, 1, 64), dtype=torch.float32, device=f.device)
         nparts = L.lib().epc_cloud_colsum64_partial_floats(B)
         parts = _splitk_ws(nparts, f.device)
         # a = softmax(batch_norm(z)) and a_sum in one pass over z (epc_assign_softmax_fwd)
-        L.check(L.lib().epc_assign_softmax_fwd(z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                               float(eps), B, n_points, a.data_ptr(), a_sum.data_ptr(), parts.data_ptr(),
-                                               parts.numel(), _st()))
+        L.run.epc_assign_softmax_fwd(z, mean, var, gamma, beta, eps, B, n_points, a, a_sum, parts, parts.numel())
         f3, a3 = f.view(B, n_points, F), a.view(B, n_points, 64)
         vlad = gemm(f3, a3, trans_a=True, splitk=max(1, min(8, n_points // 256)), deterministic=True)
         ctx.save_for_backward(f, Wc, z, mean, var, gamma, beta, a)
@@ -1176,10 +1095,8 @@ class VladAssignAggregate(torch.autograd.Function):
                         and N % 32 == 0 and Wc.is_contiguous() and tuple(lk.z.shape) == (rows, F))
         trow = torch.empty(rows, dtype=torch.float32, device=z.device) if through_tail else None
         # softmax backward (+ the a_sum gradient of every point's cloud) with BatchNorm's sums, then dz in place
-        L.check(L.lib().epc_assign_softmax_bwd(da.data_ptr(), dasum.data_ptr() if dasum is not None else None, a.data_ptr(),
-                                               z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                               ctx.eps, B, N, dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                               trow.data_ptr() if through_tail else None, ws.data_ptr(), n, _st()))
+        L.run.epc_assign_softmax_bwd(da, dasum, a, z, mean, var, gamma, beta, ctx.eps, B, N, dz, dgamma, dbeta,
+                                     trow, ws, n)
         dWc = gemm(f, dz, trans_a=True, splitk=_splitk_for(F, 64, rows), fast=True, deterministic=True)
         df = None
         if through_tail:
@@ -1189,12 +1106,8 @@ class VladAssignAggregate(torch.autograd.Function):
             nbytes = L.lib().epc_vlad_df_packed_bytes(B, F)
             pfl = L.lib().epc_vlad_df_tail_partial_floats(B, N)
             scratch = _splitk_ws((nbytes + 3) // 4 + pfl, f.device)
-            part_ptr = scratch.data_ptr() + 4 * ((nbytes + 3) // 4)
-            L.check(L.lib().epc_vlad_df_tail(a.data_ptr(), dz.data_ptr(), dvlad.data_ptr(), Wc.data_ptr(), B, N,
-                                             1 if _GEMM_PRECISION == "bf16" else 2, scratch.data_ptr(), nbytes, lk.z.data_ptr(),
-                                             lk.rn.data_ptr(), trow.data_ptr(), lk.mean.data_ptr(), lk.var.data_ptr(),
-                                             lk.gamma.data_ptr(), lk.beta.data_ptr(), lk.eps, du.data_ptr(), sums.data_ptr(),
-                                             part_ptr, pfl, _st()))
+            L.run.epc_vlad_df_tail(a, dz, dvlad, Wc, B, N, 1 if _GEMM_PRECISION == "bf16" else 2, scratch, nbytes, lk.z, lk.rn,
+                                   trow, lk.mean, lk.var, lk.gamma, lk.beta, lk.eps, du, sums, scratch[(nbytes + 3) // 4:], pfl)
             lk.du, lk.sums = du, sums
             df = du
         elif ctx.needs_input_grad[0]:
@@ -1203,9 +1116,7 @@ class VladAssignAggregate(torch.autograd.Function):
                 df = torch.empty((rows, F), dtype=torch.float32, device=f.device)
                 nbytes = L.lib().epc_vlad_df_packed_bytes(B, F)
                 packed = _splitk_ws((nbytes + 3) // 4, f.device)
-                L.check(L.lib().epc_vlad_df(a.data_ptr(), dz.data_ptr(), dvlad.data_ptr(), Wc.data_ptr(), B, N, F,
-                                            1 if _GEMM_PRECISION == "bf16" else 2, packed.data_ptr(), packed.numel() * 4,
-                                            df.data_ptr(), _st()))
+                L.run.epc_vlad_df(a, dz, dvlad, Wc, B, N, F, 1 if _GEMM_PRECISION == "bf16" else 2, packed, packed.numel() * 4, df)
             else:
                 lhs = torch.cat((a, dz), dim=1).view(B, N, 128)                                    # [a | dz]
                 rhs = torch.cat((dvlad.transpose(1, 2), Wc.t().unsqueeze(0).expand(B, 64, F)), dim=1)   # [dvlad^T ; Wc^T]  (B, 128, F)
@@ -1260,10 +1171,11 @@ def _scratch_bytes(nbytes, device):
     return buf, buf.numel() * 4
 
 
-def _head_entry(lib, h16):
-    """name -> the streamed head's entry point of that name in the mode's arithmetic (epc_h16_* on bf16 tensors, epc_h32_* on f32)."""
+def _head_entry(h16):
+    """name -> the streamed head's entry point of that name in the mode's arithmetic (epc_h16_* on bf16 tensors, epc_h32_* on f32):
+    the checked call form of a launch, the raw function of a size query."""
     prefix = "epc_h16_" if h16 else "epc_h32_"
-    return lambda name: getattr(lib, prefix + name)
+    return lambda name: getattr(L.lib() if name.endswith("_bytes") else L.run, prefix + name)
 
 
 class Conv5VladHead(torch.autograd.Function):
@@ -1285,33 +1197,29 @@ class Conv5VladHead(torch.autograd.Function):
         B = rows // N
         dev = cat.device
         h16 = mode == "bf16"
-        hx = _head_entry(lib, h16)
+        hx = _head_entry(h16)
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         z5 = torch.empty((rows, 1024), dtype=torch.bfloat16 if h16 else torch.float32, device=dev)
         mean5, var5 = f32(1024), f32(1024)
-        bn5 = lambda: (mean5.data_ptr(), var5.data_ptr(), g5.data_ptr(), bt5.data_ptr(), float(eps5))
+        bn5 = (mean5, var5, g5, bt5, eps5)
         lhs = cat
         if h16:
             if cat16 is not None and tuple(cat16.shape) == (rows, 256) and cat16.dtype == torch.bfloat16:
                 lhs = cat16                                    # the chain's bf16 copy of this very tensor
             sc, n = _scratch_bytes(lib.epc_h16_conv5_fwd_scratch_bytes(rows), dev)
-            L.check(lib.epc_h16_conv5_fwd(lhs.data_ptr(), int(lhs is not cat), W5.data_ptr(), b5.data_ptr(), rows, z5.data_ptr(),
-                                          mean5.data_ptr(), var5.data_ptr(), sc.data_ptr(), n, _st()))
+            L.run.epc_h16_conv5_fwd(lhs, lhs is not cat, W5, b5, rows, z5, mean5, var5, sc, n)
         else:
             sc, n = _scratch_bytes(lib.epc_h32_conv5_fwd_scratch_bytes(rows), dev)
-            L.check(lib.epc_h32_conv5_fwd(cat.data_ptr(), W5.data_ptr(), b5.data_ptr(), rows, z5.data_ptr(), mean5.data_ptr(),
-                                          var5.data_ptr(), sc.data_ptr(), n, _st()))
+            L.run.epc_h32_conv5_fwd(cat, W5, b5, rows, z5, mean5, var5, sc, n)
         za, rn, mean_c, var_c = f32(rows, 64), f32(rows), f32(64), f32(64)
         sc, n = _scratch_bytes(hx("assign_scratch_bytes")(B, N, 0), dev)
-        L.check(hx("assign")(z5.data_ptr(), *bn5(), Wc.data_ptr(), 0, B, N, za.data_ptr(), rn.data_ptr(), mean_c.data_ptr(), var_c.data_ptr(),
-                             sc.data_ptr(), n, _st()))
+        hx("assign")(z5, *bn5, Wc, 0, B, N, za, rn, mean_c, var_c, sc, n)
         a, a_sum = f32(rows, 64), f32(B, 1, 64)
         parts = _splitk_ws(lib.epc_cloud_colsum64_partial_floats(B), dev)
-        L.check(lib.epc_assign_softmax_fwd(za.data_ptr(), mean_c.data_ptr(), var_c.data_ptr(), gc.data_ptr(), btc.data_ptr(),
-                                           float(epsc), B, N, a.data_ptr(), a_sum.data_ptr(), parts.data_ptr(), parts.numel(), _st()))
+        L.run.epc_assign_softmax_fwd(za, mean_c, var_c, gc, btc, epsc, B, N, a, a_sum, parts, parts.numel())
         vlad = f32(B, 1024, 64)
         sc, n = _scratch_bytes(hx("colgemm_scratch_bytes")(B, N), dev)
-        L.check(hx("colgemm")(z5.data_ptr(), *bn5(), a.data_ptr(), rn.data_ptr(), B, N, 1, vlad.data_ptr(), sc.data_ptr(), n, _st()))
+        hx("colgemm")(z5, *bn5, a, rn, B, N, 1, vlad, sc, n)
         ctx.save_for_backward(lhs, W5, z5, mean5, var5, g5, bt5, rn, Wc, za, mean_c, var_c, gc, btc, a)
         ctx.eps5, ctx.epsc, ctx.n_points, ctx.h16 = float(eps5), float(epsc), N, h16
         ctx.mark_non_differentiable(mean5, var5, mean_c, var_c, z5, rn)
@@ -1324,67 +1232,58 @@ class Conv5VladHead(torch.autograd.Function):
         cat, W5, z5, mean5, var5, g5, bt5, rn, Wc, za, mean_c, var_c, gc, btc, a = ctx.saved_tensors
         rows = int(cat.shape[0])
         N, h16 = ctx.n_points, ctx.h16
-        hx = _head_entry(lib, h16)
+        hx = _head_entry(h16)
         B = rows // N
         dev = cat.device
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         if dvlad is None:
             dvlad = torch.zeros((B, 1024, 64), dtype=torch.float32, device=dev)
         dvlad = dvlad.contiguous()
-        bn5 = (mean5.data_ptr(), var5.data_ptr(), g5.data_ptr(), bt5.data_ptr(), ctx.eps5)
+        bn5 = (mean5, var5, g5, bt5, ctx.eps5)
         # da = f dvlad[cloud] (the a_sum gradient of every point's cloud is added inside the softmax backward)
         da = f32(rows, 64)
         sc, n = _scratch_bytes(hx("assign_scratch_bytes")(B, N, 1), dev)
-        L.check(hx("assign")(z5.data_ptr(), *bn5, dvlad.data_ptr(), 1, B, N, da.data_ptr(), None, None, None, sc.data_ptr(), n, _st()))
+        hx("assign")(z5, *bn5, dvlad, 1, B, N, da, None, None, None, sc, n)
         dz, dgc, dbtc, trow = f32(rows, 64), f32(64), f32(64), f32(rows)
         ws, wn = _ws(rows, 64, dev)
-        L.check(lib.epc_assign_softmax_bwd(da.data_ptr(), dasum.contiguous().data_ptr() if dasum is not None else None, a.data_ptr(),
-                                           za.data_ptr(), mean_c.data_ptr(), var_c.data_ptr(), gc.data_ptr(), btc.data_ptr(), ctx.epsc,
-                                           B, N, dz.data_ptr(), dgc.data_ptr(), dbtc.data_ptr(), trow.data_ptr(), ws.data_ptr(), wn, _st()))
+        L.run.epc_assign_softmax_bwd(da, dasum.contiguous() if dasum is not None else None, a, za, mean_c, var_c, gc, btc,
+                                     ctx.epsc, B, N, dz, dgc, dbtc, trow, ws, wn)
         dWc = f32(1024, 64)
         sc, n = _scratch_bytes(hx("colgemm_scratch_bytes")(B, N), dev)
-        L.check(hx("colgemm")(z5.data_ptr(), *bn5, dz.data_ptr(), rn.data_ptr(), B, N, 0, dWc.data_ptr(), sc.data_ptr(), n, _st()))
+        hx("colgemm")(z5, *bn5, dz, rn, B, N, 0, dWc, sc, n)
         # du = [f > 0] rn ([a | dz] [dvlad^T ; Wc^T] - f trow), the BatchNorm's column sums, then dz5 in place
         need_dx = bool(ctx.needs_input_grad[0])
         du = torch.empty_like(z5)
         sums = f32(2, 1024)
         if h16:
             sc, n = _scratch_bytes(lib.epc_h16_df_tail_scratch_bytes(B, N), dev)
-            L.check(lib.epc_h16_df_tail(a.data_ptr(), dz.data_ptr(), dvlad.data_ptr(), Wc.data_ptr(), B, N, z5.data_ptr(), rn.data_ptr(),
-                                        trow.data_ptr(), *bn5, du.data_ptr(), sums.data_ptr(), sc.data_ptr(), n, _st()))
+            L.run.epc_h16_df_tail(a, dz, dvlad, Wc, B, N, z5, rn, trow, *bn5, du, sums, sc, n)
             if not need_dx:
-                L.check(lib.epc_h16_bn_bwd_apply(du.data_ptr(), z5.data_ptr(), *bn5, sums[0].data_ptr(), sums[1].data_ptr(), rows,
-                                                 du.data_ptr(), _st()))
+                L.run.epc_h16_bn_bwd_apply(du, z5, *bn5, sums[0], sums[1], rows, du)
         else:
             nbytes = lib.epc_vlad_df_packed_bytes(B, 1024)
             pfl = lib.epc_vlad_df_tail_partial_floats(B, N)
             scratch = _splitk_ws((nbytes + 3) // 4 + pfl, dev)
-            L.check(lib.epc_vlad_df_tail(a.data_ptr(), dz.data_ptr(), dvlad.data_ptr(), Wc.data_ptr(), B, N, 2, scratch.data_ptr(), nbytes,
-                                         z5.data_ptr(), rn.data_ptr(), trow.data_ptr(), *bn5, du.data_ptr(), sums.data_ptr(),
-                                         scratch.data_ptr() + 4 * ((nbytes + 3) // 4), pfl, _st()))
+            L.run.epc_vlad_df_tail(a, dz, dvlad, Wc, B, N, 2, scratch, nbytes, z5, rn, trow, *bn5, du, sums,
+                                   scratch[(nbytes + 3) // 4:], pfl)
             if not need_dx:
-                L.check(lib.epc_bn_apply_bwd_given(du.data_ptr(), z5.data_ptr(), mean5.data_ptr(), var5.data_ptr(), g5.data_ptr(),
-                                                   bt5.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(), ctx.eps5, rows, 1024, du.data_ptr(),
-                                                   _st()))
+                L.run.epc_bn_apply_bwd_given(du, z5, mean5, var5, g5, bt5, sums[0], sums[1], ctx.eps5, rows, 1024, du)
         dcat = None
         if need_dx:
             # dz5 = gamma rstd (du - dbeta / R - zhat dgamma / R) is formed INSIDE dcat's product as du and z5 stream, and written over du for
             # dW5's: one pass over the (rows, 1024) tensors instead of the apply pass + the product's own read
             dcat = f32(rows, 256)
             sc, n = _scratch_bytes(hx("dx_scratch_bytes")(), dev)
-            L.check(hx("conv5_dx_bn")(
-                du.data_ptr(), z5.data_ptr(), mean5.data_ptr(), var5.data_ptr(), g5.data_ptr(), ctx.eps5, sums[0].data_ptr(), sums[1].data_ptr(),
-                W5.data_ptr(), rows, du.data_ptr(), dcat.data_ptr(), sc.data_ptr(), n, _st()))
+            hx("conv5_dx_bn")(du, z5, mean5, var5, g5, ctx.eps5, sums[0], sums[1], W5, rows, du, dcat, sc, n)
         # dW5 = cat^T dz5, row slices added in a fixed order
         if h16:
             dW5 = f32(256, 1024)
             sc, n = _scratch_bytes(lib.epc_h16_conv5_dw_scratch_bytes(rows), dev)
-            L.check(lib.epc_h16_conv5_dw(cat.data_ptr(), int(cat.dtype == torch.bfloat16), du.data_ptr(), rows, dW5.data_ptr(),
-                                         sc.data_ptr(), n, _st()))
+            L.run.epc_h16_conv5_dw(cat, cat.dtype == torch.bfloat16, du, rows, dW5, sc, n)
         else:
             dW5 = f32(256, 1024)
             sc, n = _scratch_bytes(lib.epc_h32_conv5_dw_scratch_bytes(rows), dev)
-            L.check(lib.epc_h32_conv5_dw(cat.data_ptr(), du.data_ptr(), rows, dW5.data_ptr(), sc.data_ptr(), n, _st()))
+            L.run.epc_h32_conv5_dw(cat, du, rows, dW5, sc, n)
         return dcat, dW5, None, sums[1], sums[0], None, dWc, dgc, dbtc, None, None, None, None
 
 
@@ -1394,11 +1293,10 @@ def expand16(z16, bn=None, rn=None):
     rows = int(z16.shape[0])
     y = torch.empty((rows, 1024), dtype=torch.float32, device=z16.device)
     if bn is None:
-        L.check(L.lib().epc_h16_expand(z16.data_ptr(), None, None, None, None, 0.0, None, rows, y.data_ptr(), _st()))
+        L.run.epc_h16_expand(z16, None, None, None, None, 0.0, None, rows, y)
     else:
         mean, var, gamma, beta, eps = bn
-        L.check(L.lib().epc_h16_expand(z16.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps),
-                                       rn.data_ptr() if rn is not None else None, rows, y.data_ptr(), _st()))
+        L.run.epc_h16_expand(z16, mean, var, gamma, beta, eps, rn, rows, y)
     return y
 
 
@@ -1411,14 +1309,14 @@ class GroupSum(torch.autograd.Function):
         rows, O = (int(v) for v in x.shape)
         ctx.G, ctx.shape = int(G), (rows, O)
         y = torch.empty((rows // int(G), O), dtype=torch.float32, device=x.device)
-        L.check(L.lib().epc_group_sum_fwd(x.data_ptr(), rows // int(G), int(G), O, y.data_ptr(), _st()))
+        L.run.epc_group_sum_fwd(x, rows // int(G), G, O, y)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         rows, O = ctx.shape
         dx = torch.empty((rows, O), dtype=torch.float32, device=dy.device)
-        L.check(L.lib().epc_group_sum_bwd(dy.contiguous().data_ptr(), rows // ctx.G, ctx.G, O, dx.data_ptr(), _st()))
+        L.run.epc_group_sum_bwd(dy.contiguous(), rows // ctx.G, ctx.G, O, dx)
         return dx, None
 
 
@@ -1445,7 +1343,7 @@ class HiddenProjection(torch.autograd.Function):
         bf16 = _GEMM_PRECISION == "bf16"
         y = torch.empty((M, int(W.shape[1])), dtype=torch.float32, device=x.device)
         sc, n = _scratch_bytes(lib.epc_hidden_proj_scratch_bytes(M, K), x.device)
-        L.check(lib.epc_hidden_proj_fwd(x.data_ptr(), W.data_ptr(), M, K, 1 if bf16 else 3, y.data_ptr(), sc.data_ptr(), n, _st()))
+        L.run.epc_hidden_proj_fwd(x, W, M, K, 1 if bf16 else 3, y, sc, n)
         ctx.save_for_backward(x, W)
         ctx.pieces = 1 if bf16 else 2
         return y
@@ -1457,8 +1355,7 @@ class HiddenProjection(torch.autograd.Function):
         M, K = int(x.shape[0]), int(x.shape[1])
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dW = torch.empty_like(W) if ctx.needs_input_grad[1] else None
-        L.check(L.lib().epc_hidden_proj_bwd(x.data_ptr(), W.data_ptr(), dy.data_ptr(), M, K, ctx.pieces,
-                                            dx.data_ptr() if dx is not None else None, dW.data_ptr() if dW is not None else None, _st()))
+        L.run.epc_hidden_proj_bwd(x, W, dy, M, K, ctx.pieces, dx, dW)
         return dx, dW
 
 
@@ -1482,7 +1379,6 @@ class HiddenTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, gamma1, beta1, G, Wg, gamma2, beta2, eps):
-        lib = L.lib()
         h, Wg = h.contiguous(), Wg.contiguous()
         R, O = (int(v) for v in h.shape)
         G = int(G)
@@ -1491,10 +1387,8 @@ class HiddenTail(torch.autograd.Function):
         vec = lambda: torch.empty(O, dtype=torch.float32, device=dev)
         mat = lambda: torch.empty((B, O), dtype=torch.float32, device=dev)
         mean1, var1, var1u, mean2, var2, var2u, v, gl, out = vec(), vec(), vec(), vec(), vec(), vec(), mat(), mat(), mat()
-        L.check(lib.epc_hidden_tail_fwd(h.data_ptr(), B, G, O, gamma1.data_ptr(), beta1.data_ptr(), Wg.data_ptr(), gamma2.data_ptr(),
-                                        beta2.data_ptr(), float(eps), R / max(R - 1, 1), B / max(B - 1, 1), mean1.data_ptr(), var1.data_ptr(),
-                                        var1u.data_ptr(), v.data_ptr(), gl.data_ptr(), mean2.data_ptr(), var2.data_ptr(), var2u.data_ptr(),
-                                        out.data_ptr(), _st()))
+        L.run.epc_hidden_tail_fwd(h, B, G, O, gamma1, beta1, Wg, gamma2, beta2, eps, R / max(R - 1, 1), B / max(B - 1, 1), mean1,
+                                  var1, var1u, v, gl, mean2, var2, var2u, out)
         ctx.save_for_backward(h, gamma1, mean1, var1, v, gl, Wg, gamma2, beta2, mean2, var2)
         ctx.G, ctx.eps, ctx.pieces = G, float(eps), 1 if _GEMM_PRECISION == "bf16" else 2
         ctx.mark_non_differentiable(mean1, var1u, mean2, var2u)
@@ -1505,7 +1399,6 @@ class HiddenTail(torch.autograd.Function):
     def backward(ctx, dout, *_unused):
         if dout is None:
             return (None,) * 8
-        lib = L.lib()
         h, gamma1, mean1, var1, v, gl, Wg, gamma2, beta2, mean2, var2 = ctx.saved_tensors
         R, O = (int(x) for x in h.shape)
         B = R // ctx.G
@@ -1514,10 +1407,8 @@ class HiddenTail(torch.autograd.Function):
         vec = lambda: torch.empty(O, dtype=torch.float32, device=dev)
         dh, dWg = torch.empty_like(h), torch.empty_like(Wg)
         dg1, db1, dg2, db2 = vec(), vec(), vec(), vec()
-        L.check(lib.epc_hidden_tail_bwd(dout.data_ptr(), h.data_ptr(), B, ctx.G, O, gamma1.data_ptr(), mean1.data_ptr(), var1.data_ptr(),
-                                        v.data_ptr(), gl.data_ptr(), Wg.data_ptr(), gamma2.data_ptr(), beta2.data_ptr(), mean2.data_ptr(),
-                                        var2.data_ptr(), ctx.eps, ctx.pieces, dh.data_ptr(), dg1.data_ptr(), db1.data_ptr(), dWg.data_ptr(),
-                                        dg2.data_ptr(), db2.data_ptr(), _st()))
+        L.run.epc_hidden_tail_bwd(dout, h, B, ctx.G, O, gamma1, mean1, var1, v, gl, Wg, gamma2, beta2, mean2, var2, ctx.eps,
+                                  ctx.pieces, dh, dg1, db1, dWg, dg2, db2)
         return dh, dg1, db1, None, dWg, dg2, db2, None
 
 
@@ -1531,7 +1422,7 @@ class MaxPoolPoints(torch.autograd.Function):
         B, N, C = (int(v) for v in x.shape)
         out = torch.empty((B, C), dtype=torch.float32, device=x.device)
         arg = torch.empty((B, C), dtype=torch.int32, device=x.device)
-        L.check(L.lib().epc_maxpool_points_fwd(x.data_ptr(), B, N, C, out.data_ptr(), arg.data_ptr(), _st()))
+        L.run.epc_maxpool_points_fwd(x, B, N, C, out, arg)
         ctx.save_for_backward(arg)
         ctx.shape = (B, N, C)
         return out
@@ -1541,7 +1432,7 @@ class MaxPoolPoints(torch.autograd.Function):
         (arg,) = ctx.saved_tensors
         B, N, C = ctx.shape
         dx = torch.empty((B, N, C), dtype=torch.float32, device=dy.device)
-        L.check(L.lib().epc_maxpool_points_bwd(dy.contiguous().data_ptr(), arg.data_ptr(), B, N, C, dx.data_ptr(), _st()))
+        L.run.epc_maxpool_points_bwd(dy.contiguous(), arg, B, N, C, dx)
         return dx
 
 
@@ -1553,7 +1444,7 @@ class GateMul(torch.autograd.Function):
         y, g = y.contiguous(), g.contiguous()
         assert y.shape == g.shape
         out = torch.empty_like(y)
-        L.check(L.lib().epc_gate_fwd(y.data_ptr(), g.data_ptr(), y.numel(), out.data_ptr(), _st()))
+        L.run.epc_gate_fwd(y, g, y.numel(), out)
         ctx.save_for_backward(y, g)
         return out
 
@@ -1562,8 +1453,7 @@ class GateMul(torch.autograd.Function):
         y, g = ctx.saved_tensors
         dout = dout.contiguous()
         dy, dg = torch.empty_like(y), torch.empty_like(g)
-        L.check(L.lib().epc_gate_bwd(dout.data_ptr(), y.data_ptr(), g.data_ptr(), y.numel(), dy.data_ptr(), dg.data_ptr(),
-                                     _st()))
+        L.run.epc_gate_bwd(dout, y, g, y.numel(), dy, dg)
         return dy, dg
 
 
@@ -1580,8 +1470,7 @@ class SquaredError(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=a.device)
         pf = L.lib().epc_sq_err_partial_floats(n)
         part = _splitk_ws(pf, a.device)
-        L.check(L.lib().epc_sq_err_fwd(a.data_ptr(), b.data_ptr(), n, int(bool(mean)), loss.data_ptr(), part.data_ptr(),
-                                       part.numel(), _st()))
+        L.run.epc_sq_err_fwd(a, b, n, bool(mean), loss, part, part.numel())
         ctx.save_for_backward(a, b)
         ctx.mean = int(bool(mean))
         return loss
@@ -1591,7 +1480,7 @@ class SquaredError(torch.autograd.Function):
         a, b = ctx.saved_tensors
         da = torch.empty_like(a)
         dloss = dloss.contiguous().float()
-        L.check(L.lib().epc_sq_err_bwd(a.data_ptr(), b.data_ptr(), a.numel(), ctx.mean, dloss.data_ptr(), da.data_ptr(), _st()))
+        L.run.epc_sq_err_bwd(a, b, a.numel(), ctx.mean, dloss, da)
         return da, None, None
 
 
@@ -1603,7 +1492,7 @@ def morton_sort(xyz):
     if xyz.shape[1] > 16384:
         return xyz
     out = torch.empty_like(xyz)
-    L.check(L.lib().epc_morton_sort(xyz.data_ptr(), int(xyz.shape[0]), int(xyz.shape[1]), out.data_ptr(), None, _st()))
+    L.run.epc_morton_sort(xyz, xyz.shape[0], xyz.shape[1], out, None)
     return out
 
 
@@ -1655,8 +1544,7 @@ def grid_downsample(points, offsets, n, normalize=True, out=None):
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     if points.numel() == 0:
         points = torch.zeros((1, 3), dtype=torch.float32, device=dev)        # (a pointer the library can check; no row of it is read)
-    L.check(L.lib().epc_grid_downsample(points.data_ptr(), offsets.data_ptr(), B, n, 1 if normalize else 0, L.ptr(out),
-                                        status.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(), _st()))
+    L.run.epc_grid_downsample(points, offsets, B, n, 1 if normalize else 0, L.ptr(out), status, info, ws, ws.numel())
     return out, status, info
 
 
@@ -1664,35 +1552,28 @@ def adam_step(w, m, v, g, lr, t, beta1=0.9, beta2=0.999, eps=1e-8):
     """tf.train.AdamOptimizer update of one tensor, in place (train.py:273).  ``lr`` may be a one-element device tensor
     holding the bias-corrected rate lr_t (``t`` is then ignored): the form a captured HIP graph of the step uses."""
     if torch.is_tensor(lr):
-        L.check(L.lib().epc_adam_step_dev(w.data_ptr(), m.data_ptr(), v.data_ptr(), g.contiguous().data_ptr(), w.numel(),
-                                          lr.data_ptr(), float(beta1), float(beta2), float(eps), _st()))
+        L.run.epc_adam_step_dev(w, m, v, g.contiguous(), w.numel(), lr, beta1, beta2, eps)
         return
-    L.check(L.lib().epc_adam_step(w.data_ptr(), m.data_ptr(), v.data_ptr(), g.contiguous().data_ptr(), w.numel(), float(lr),
-                                  float(beta1), float(beta2), float(eps), int(t), _st()))
+    L.run.epc_adam_step(w, m, v, g.contiguous(), w.numel(), lr, beta1, beta2, eps, t)
 
 
 def _ptr_array(tensors):
-    import ctypes
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 def adam_multi(ws, ms, vs, gs, lr, t, beta1=0.9, beta2=0.999, eps=1e-8):
     """adam_step over lists of tensors in one launch per 64 tensors (epc_adam_multi)."""
-    import ctypes
     gs = [g.contiguous() for g in gs]
     n = (ctypes.c_long * len(ws))(*[w.numel() for w in ws])
-    dev_lr = lr.data_ptr() if torch.is_tensor(lr) else None
-    L.check(L.lib().epc_adam_multi(len(ws), _ptr_array(ws), _ptr_array(ms), _ptr_array(vs), _ptr_array(gs), n,
-                                   0.0 if torch.is_tensor(lr) else float(lr), float(beta1), float(beta2), float(eps),
-                                   int(t), dev_lr, _st()))
+    L.run.epc_adam_multi(len(ws), _ptr_array(ws), _ptr_array(ms), _ptr_array(vs), _ptr_array(gs), n,
+                         0.0 if torch.is_tensor(lr) else lr, beta1, beta2, eps, t, lr if torch.is_tensor(lr) else None)
 
 
 def ema_multi(shadows, values, scheduled, fixed_decay, sched_decay):
     """All moving-average updates of a step in one launch (epc_ema_multi).  ``sched_decay``: float or 0-d device tensor."""
-    import ctypes
     values = [v.detach().contiguous() for v in values]
     n = (ctypes.c_long * len(shadows))(*[s_.numel() for s_ in shadows])
     flags = (ctypes.c_int * len(shadows))(*[1 if f else 0 for f in scheduled])
-    dev = sched_decay.data_ptr() if torch.is_tensor(sched_decay) else None
-    L.check(L.lib().epc_ema_multi(len(shadows), _ptr_array(shadows), _ptr_array(values), n, flags, float(fixed_decay),
-                                  0.0 if torch.is_tensor(sched_decay) else float(sched_decay), dev, _st()))
+    dev = torch.is_tensor(sched_decay)
+    L.run.epc_ema_multi(len(shadows), _ptr_array(shadows), _ptr_array(values), n, flags, fixed_decay, 0.0 if dev else sched_decay,
+                        sched_decay if dev else None)

@@ -84,9 +84,7 @@ def mine_topk(table: torch.Tensor, queries: torch.Tensor, cand: torch.Tensor, ca
     ws = workspace
     if ws is None:
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=queries.device)
-    L.check(L.lib().epc_mine_topk(table.data_ptr(), int(table.shape[0]), int(table.shape[1]), queries.data_ptr(), q, cand.data_ptr(),
-                                  cand_count.data_ptr(), c, k, pos.data_ptr(), ids.data_ptr(), dist.data_ptr(), ws.data_ptr(),
-                                  ws.numel(), L.current_stream()))
+    L.run.epc_mine_topk(table, table.shape[0], table.shape[1], queries, q, cand, cand_count, c, k, pos, ids, dist, ws, ws.numel())
     if workspace is None:
         ws.record_stream(torch.cuda.current_stream(queries.device))
     return dist, pos, ids
@@ -108,12 +106,10 @@ def knn_search(database: torch.Tensor, queries: torch.Tensor, k: int = NUM_NEIGH
         # pairwise matrix on the matrix pipe + exact re-rank of the candidates (epc_pairwise_topk_ws): any database size
         need = L.lib().epc_pairwise_topk_workspace_bytes(d, q)
         ws = torch.empty(need, dtype=torch.uint8, device=queries.device)
-        L.check(L.lib().epc_pairwise_topk_ws(L.ptr(database), d, L.ptr(queries), q, dim, k, L.ptr(idx), L.ptr(dist),
-                                             ws.data_ptr(), need, L.current_stream()))
+        L.run.epc_pairwise_topk_ws(L.ptr(database), d, L.ptr(queries), q, dim, k, L.ptr(idx), L.ptr(dist), ws, need)
         ws.record_stream(torch.cuda.current_stream(queries.device))
     else:
-        L.check(L.lib().epc_pairwise_topk(L.ptr(database), d, L.ptr(queries), q, dim, k, L.ptr(idx), L.ptr(dist),
-                                          L.current_stream()))
+        L.run.epc_pairwise_topk(L.ptr(database), d, L.ptr(queries), q, dim, k, L.ptr(idx), L.ptr(dist))
     return dist, idx
 
 

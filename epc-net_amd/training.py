@@ -9,6 +9,8 @@ One ``TrainStep.step(query, positives, negatives, other_neg, epoch)`` = one ``se
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import importlib
 import math
 from typing import Dict, Optional
@@ -55,6 +57,22 @@ def _joined_along_dim1(parts):
     if p0.shape[0] > 1 and total * int(p0.stride(1)) > int(p0.stride(0)):
         return None            # (rows of the leading dim would overlap: not slices of one (B, total, ...) tensor)
     return joined
+
+
+@contextlib.contextmanager
+def _no_finalisers_inside_a_capture():
+    """Nothing may be finalised while a stream captures: this runtime's CUDAGraph destructor synchronises the device, a capturing
+    stream refuses that, and a refusal inside a destructor ends the process.  torch.cuda.graph no longer collects on entry, and when
+    the cyclic collector runs is an accident of allocation counts.  So dead cycles (an earlier TrainStep's graphs) are collected
+    now, and the collector stays off until the captures have ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class TrainStep:
@@ -531,55 +549,56 @@ class TrainStep:
                 x.copy_(s0)
         for name in self.trainable_names():
             self.store.vars[name].grad = None
-        g["graph"] = torch.cuda.CUDAGraph()
-        if not dp:
-            with torch.cuda.graph(g["graph"]):
-                g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"], source=source)
-                self._apply(grads, g["lr_t"], t)
-            g["verdict"] = self._verdict              # (a static buffer of the graph like the loss, or None: no persistent launch)
-        else:
-            # Data-parallel: [forward, head backward, pack head] | RCCL (head, asynchronous) | [backbone backward, moving averages,
-            # pack rest] | RCCL (rest) | [mean, unpack, Adam] -- the captures end and begin INSIDE the step, at the cut of its
-            # backward (the `between` callback runs on this thread, between two autograd calls).
-            ws = D.world()[1]
-            g["graph_mid"] = torch.cuda.CUDAGraph() if self.overlap_exchange else None
-            g["graph2"] = torch.cuda.CUDAGraph()
-            g["cut"] = False
-            torch.cuda.synchronize(dev)
-            cap = torch.cuda.Stream(device=dev)
-            cap.wait_stream(torch.cuda.current_stream(dev))
+        with _no_finalisers_inside_a_capture():
+            g["graph"] = torch.cuda.CUDAGraph()
+            if not dp:
+                with torch.cuda.graph(g["graph"]):
+                    g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"], source=source)
+                    self._apply(grads, g["lr_t"], t)
+                g["verdict"] = self._verdict              # (a static buffer of the graph like the loss, or None: no persistent launch)
+            else:
+                # Data-parallel: [forward, head backward, pack head] | RCCL (head, asynchronous) | [backbone backward, moving averages,
+                # pack rest] | RCCL (rest) | [mean, unpack, Adam] -- the captures end and begin INSIDE the step, at the cut of its
+                # backward (the `between` callback runs on this thread, between two autograd calls).
+                ws = D.world()[1]
+                g["graph_mid"] = torch.cuda.CUDAGraph() if self.overlap_exchange else None
+                g["graph2"] = torch.cuda.CUDAGraph()
+                g["cut"] = False
+                torch.cuda.synchronize(dev)
+                cap = torch.cuda.Stream(device=dev)
+                cap.wait_stream(torch.cuda.current_stream(dev))
 
-            open_graph = [None]        # the graph whose capture is open RIGHT NOW: the only one a failure may end
+                open_graph = [None]        # the graph whose capture is open RIGHT NOW: the only one a failure may end
 
-            def begin(graph, **kw):
-                graph.capture_begin(**kw)
-                open_graph[0] = graph
+                def begin(graph, **kw):
+                    graph.capture_begin(**kw)
+                    open_graph[0] = graph
 
-            def end():
-                graph, open_graph[0] = open_graph[0], None
-                if graph is not None:
-                    graph.capture_end()
+                def end():
+                    graph, open_graph[0] = open_graph[0], None
+                    if graph is not None:
+                        graph.capture_end()
 
-            def between(hn, hg):
-                self._pack_head(ex, hn, hg)
-                end()
-                begin(g["graph_mid"], pool=g["graph"].pool())
-                g["cut"] = True
-
-            with torch.cuda.stream(cap):
-                try:
-                    begin(g["graph"])
-                    g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"],
-                                                              between=between if self.overlap_exchange else None, source=source)
-                    g["verdict"] = self._verdict
-                    self._pack_rest(ex, grads, g["cut"])
+                def between(hn, hg):
+                    self._pack_head(ex, hn, hg)
                     end()
-                    begin(g["graph2"], pool=g["graph"].pool())
-                    self._apply(self._unpack_mean(ex, ws), g["lr_t"], t)
-                finally:
-                    end()
-            torch.cuda.current_stream(dev).wait_stream(cap)
-            g["ex"] = ex
+                    begin(g["graph_mid"], pool=g["graph"].pool())
+                    g["cut"] = True
+
+                with torch.cuda.stream(cap):
+                    try:
+                        begin(g["graph"])
+                        g["loss"], grads = self._forward_backward(*g["in"], g["bn_decay"],
+                                                                  between=between if self.overlap_exchange else None, source=source)
+                        g["verdict"] = self._verdict
+                        self._pack_rest(ex, grads, g["cut"])
+                        end()
+                        begin(g["graph2"], pool=g["graph"].pool())
+                        self._apply(self._unpack_mean(ex, ws), g["lr_t"], t)
+                    finally:
+                        end()
+                torch.cuda.current_stream(dev).wait_stream(cap)
+                g["ex"] = ex
         self._graph = g
 
     def _replay_step(self, g, dp, lr, bn_decay, t):

@@ -95,7 +95,7 @@ def pairwise_distance_mask(pc: torch.Tensor, k: int = 20) -> torch.Tensor:
     B, N, _ = pc.shape
     kth, _, _ = knn_index(pc)
     mask = torch.empty((B, N, N), dtype=torch.float32, device=pc.device)
-    L.check(L.lib().epc_knn_mask(L.ptr(pc), L.ptr(kth), B, N, L.ptr(mask), L.current_stream()))
+    L.run.epc_knn_mask(L.ptr(pc), L.ptr(kth), B, N, L.ptr(mask))
     return mask
 
 
@@ -109,10 +109,9 @@ def knn_index(pc: torch.Tensor, form: Optional[int] = None):
     cnt = torch.empty((B, N), dtype=torch.int32, device=pc.device)
     kth = torch.empty((B, N), dtype=torch.float32, device=pc.device)
     if form is None:
-        L.check(L.lib().epc_knn_topk(L.ptr(pc), B, N, L.EPC_KNN_CAP, L.ptr(idx), L.ptr(cnt), L.ptr(kth), L.current_stream()))
+        L.run.epc_knn_topk(L.ptr(pc), B, N, L.EPC_KNN_CAP, L.ptr(idx), L.ptr(cnt), L.ptr(kth))
     else:
-        L.check(L.lib().epc_knn_topk_form(L.ptr(pc), B, N, L.EPC_KNN_CAP, L.ptr(idx), L.ptr(cnt), L.ptr(kth), int(form),
-                                          L.current_stream()))
+        L.run.epc_knn_topk_form(L.ptr(pc), B, N, L.EPC_KNN_CAP, L.ptr(idx), L.ptr(cnt), L.ptr(kth), form)
     return kth, idx, cnt
 
 
@@ -145,11 +144,9 @@ def _ema_update(shadow: torch.Tensor, value: torch.Tensor, decay, scheduled: boo
         return
     value = value.detach().contiguous()
     if torch.is_tensor(decay):
-        L.check(L.lib().epc_ema_update(shadow.data_ptr(), value.data_ptr(), shadow.numel(), 0.0, decay.data_ptr(),
-                                       L.current_stream()))
+        L.run.epc_ema_update(shadow, value, shadow.numel(), 0.0, decay)
     else:
-        L.check(L.lib().epc_ema_update(shadow.data_ptr(), value.data_ptr(), shadow.numel(), float(decay), None,
-                                       L.current_stream()))
+        L.run.epc_ema_update(shadow, value, shadow.numel(), decay, None)
     from ..variables import current_scope
     default_store().bump(current_scope() or None)
 

@@ -749,3 +749,55 @@ def test_transposed_graph_with_a_hub_longer_than_a_wave(dev):
     for j in range(M):
         assert rdeg[j] == len(want[j]) and list(rlist[roff[j]:roff[j] + rdeg[j]]) == want[j], j
     assert rdeg[5] > 600
+
+
+@pytest.mark.parametrize("rows", [64, 65])          # 65: the partial last row tile
+def test_checked_call_form_equals_the_raw_call(dev, rows):
+    """epc_col_sum and epc_col_moments through lib.run (tensors in, the stream and the status handled) and through the raw handle with
+    hand-written pointers, on the same zero-filled workspace: the same bits."""
+    L, ops = H.pkg("lib"), H.pkg("ops")
+    C = 64
+    x = torch.randn(rows, C, generator=torch.Generator().manual_seed(rows)).to(dev)
+    ws, n = ops._ws(rows, C, dev)
+    new = lambda: torch.full((C,), float("nan"), dtype=torch.float32, device=dev)
+    s_run, s_raw, m_run, v_run, m_raw, v_raw = (new() for _ in range(6))
+    ws.zero_()
+    L.run.epc_col_sum(x, rows, C, s_run, ws, n)
+    ws.zero_()
+    L.check(L.lib().epc_col_sum(x.data_ptr(), rows, C, s_raw.data_ptr(), ws.data_ptr(), n, L.current_stream()))
+    ws.zero_()
+    L.run.epc_col_moments(x, rows, C, m_run, v_run, ws, n)
+    ws.zero_()
+    L.check(L.lib().epc_col_moments(x.data_ptr(), rows, C, m_raw.data_ptr(), v_raw.data_ptr(), ws.data_ptr(), n, L.current_stream()))
+    torch.cuda.synchronize()
+    for a, b in ((s_run, s_raw), (m_run, m_raw), (v_run, v_raw)):
+        assert torch.isfinite(b).all() and torch.equal(a, b)
+    assert rel(s_raw, x.double().sum(0)) <= 2e-5 and rel(m_raw, x.double().mean(0)) <= 2e-5      # (and they are the column sums)
+
+
+def test_strided_views_pass_by_address_and_stride(dev):
+    """ops.gemm with trans_a on a (2, 64, 32) batched operand that is a VIEW -- a column range of a wider tensor, and a transposed
+    tensor -- against its .contiguous() copy: the same bits (nothing was compacted on the way, nothing read from the wrong place)."""
+    ops = H.pkg("ops")
+    g = torch.Generator().manual_seed(5)
+    wide = torch.randn(2, 64, 48, generator=g).to(dev)
+    tall = torch.randn(2, 32, 64, generator=g).to(dev)
+    B = torch.randn(2, 64, 64, generator=g).to(dev)
+    for A in (wide[:, :, 8:40], tall.transpose(1, 2)):
+        assert tuple(A.shape) == (2, 64, 32) and not A.is_contiguous()
+        got, want = ops.gemm(A, B, trans_a=True), ops.gemm(A.contiguous(), B, trans_a=True)
+        assert torch.equal(got, want)
+        assert rel(want, A.double().transpose(1, 2) @ B.double()) <= 2e-5
+
+
+def test_checked_call_form_refuses_a_bf16_tensor_at_a_float_pointer(dev):
+    """A bfloat16 device tensor where the header declares `const float*` raises, and nothing was launched: the output keeps its fill."""
+    L, ops = H.pkg("lib"), H.pkg("ops")
+    x = torch.ones(64, 64, dtype=torch.bfloat16, device=dev)
+    out = torch.full((64,), 7.0, dtype=torch.float32, device=dev)
+    ws, n = ops._ws(64, 64, dev)
+    with pytest.raises(L.EpcNetError) as e:
+        L.run.epc_col_sum(x, 64, 64, out, ws, n)
+    assert "epc_col_sum" in str(e.value) and "argument 1" in str(e.value) and "torch.bfloat16" in str(e.value)
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())

@@ -80,7 +80,9 @@ def test_header_reader_refuses_what_it_does_not_understand():
     enum = "typedef enum epc_status { EPC_OK = 0, EPC_EINVAL = -1 } epc_status;\n#define EPC_KNN_CAP 32 /* slots */\n"
     good = enum + "int epc_a(const float* x, long n, void* stream);\nsize_t epc_b(void); /* bytes */\n"
     functions, constants, status = L.parse_header(good)
-    assert functions == {"epc_a": ("int", ["float*", "long", "void*"]), "epc_b": ("size_t", [])}
+    assert functions == {"epc_a": ("int", ["float*", "long", "void*"], ["x", "n", "stream"]), "epc_b": ("size_t", [], [])}
+    names = L.parse_header(enum + "int epc_c(const epc_cfg *cfg, float* const* w, const int32_t*idx, void* stream, int lanes);\n")[0]
+    assert names == {"epc_c": ("int", ["epc_cfg*", "float**", "int32_t*", "void*", "int"], ["cfg", "w", "idx", "stream", "lanes"])}
     assert list(functions) == ["epc_a", "epc_b"] and constants == {"EPC_KNN_CAP": 32} and status == {"EPC_OK": 0, "EPC_EINVAL": -1}
     for bad in (good.replace("long n", "double n"),                  # an unknown parameter type
                 good.replace("long n", "long"),                      # a parameter without a name
@@ -92,6 +94,87 @@ def test_header_reader_refuses_what_it_does_not_understand():
                 good + "}\n"):                                       # text after the last declaration
         with pytest.raises(ValueError):
             L.parse_header(bad)
+
+
+def test_launching_set_is_the_headers_stream_last_functions():
+    """lib.LAUNCHING / lib.run: exactly the declarations whose last parameter is `void* stream`, read here from the header's text with a
+    pattern of the test's own."""
+    L = H.pkg("lib")
+    header = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "epcnet.h")).read(), flags=re.S)
+    want = re.findall(r"\b(epc_\w+)\s*\([^()]*\bvoid\s*\*\s*stream\s*\)\s*;", header)
+    assert len(want) == 114 and set(want) == set(L.LAUNCHING) and len(L.LAUNCHING) == 114
+    assert [n for n in L.EXPORTS if hasattr(L.run, n)] == L.LAUNCHING
+    for name in ("epc_net_forward_overlapped", "epc_net_forward_profiled"):      # their stream is not the last parameter
+        assert name in L.EXPORTS and name not in L.LAUNCHING
+    functions = L.parse_header(open(os.path.join(ROOT, "include", "epcnet.h")).read())[0]
+    assert len(functions) == 156
+    assert all(functions[name][0] == "int" for name in L.LAUNCHING)              # a status; no size_t query is among them
+    assert not [name for name, (ret, _, _) in functions.items() if ret == "size_t" and name in L.LAUNCHING]
+
+
+class _FakeDeviceTensor:
+    """What lib.run asks of a tensor argument, without a device."""
+
+    def __init__(self, dtype, is_cuda=True):
+        self.dtype, self.is_cuda, self.asked = dtype, is_cuda, 0
+
+    def data_ptr(self):
+        self.asked += 1
+        return 0x1000
+
+
+def test_checked_call_form_refuses_before_the_library_is_reached():
+    """Every refusal names the function, the parameter's position and its header name, and happens before the C function runs: the
+    library's last-error text stays what the call before left."""
+    L = H.pkg("lib")
+    functions = L.parse_header(open(os.path.join(ROOT, "include", "epcnet.h")).read())[0]
+    _, types, names = functions["epc_col_moments"]
+    assert types == ["float*", "int", "int", "float*", "float*", "void*", "size_t", "void*"] and names[-1] == "stream"
+    # a status reaches the caller: epc_col_sum checks its pointers (EPC_CHECK_ARG, then colreduce_check) before its first HIP call
+    with pytest.raises(L.EpcNetError) as e:
+        L.run.epc_col_sum(None, 0, 0, None, None, 0, stream=0)
+    assert e.value.status == L.EPC_EINVAL and "EPC_EINVAL" in str(e.value) and "epc_col_sum: null pointer" in str(e.value)
+    mark = L.lib().epc_last_error()
+    assert mark == b"epc_col_sum: null pointer"
+
+    def refused(exc, position, *args):
+        with pytest.raises(exc) as e:
+            L.run.epc_col_moments(*args, stream=0)
+        text = str(e.value)
+        assert "epc_col_moments" in text and ("argument %d" % position) in text and names[position - 1] in text, text
+        assert L.lib().epc_last_error() == mark                      # (reached, it would read "epc_col_moments: null pointer")
+        return e.value
+
+    err = refused(L.EpcNetError, 1, torch.zeros(4, 4), 4, 4, None, None, None, 0)         # a CPU tensor at `const float* x`
+    assert err.status == -1 and "tensor must live on a ROCm device: the HIP path has no CPU fallback" in str(err)
+    refused(TypeError, 2, None, torch.zeros(1), 4, None, None, None, 0)                   # a tensor at `int rows`
+    for args in ((None, 4, 4, None, None, None), (None, 4, 4, None, None, None, 0, 0)):   # one short, one over (the stream is a keyword)
+        with pytest.raises(TypeError) as e:
+            L.run.epc_col_moments(*args, stream=0)
+        assert "epc_col_moments" in str(e.value) and all(n in str(e.value) for n in names), str(e.value)
+        assert L.lib().epc_last_error() == mark
+    # dtypes, on a stand-in that answers is_cuda / dtype / data_ptr() (the conversion is the one the callable runs)
+    f32, i32, bf16 = (_FakeDeviceTensor(d) for d in (torch.float32, torch.int32, torch.bfloat16))
+    for bad in (i32, bf16):
+        err = refused(L.EpcNetError, 1, bad, 4, 4, None, None, None, 0)                   # at `const float* x`
+        assert str(bad.dtype) in str(err) and "torch.float32" in str(err) and bad.asked == 0
+    assert functions["epc_neighbour_mean_fwd"][1][2] == "int32_t*" and functions["epc_neighbour_mean_fwd"][2][2] == "idx"
+    with pytest.raises(L.EpcNetError) as e:                                               # float32 at `const int32_t* idx`
+        L.run.epc_neighbour_mean_fwd(None, None, f32, None, None, 32, 1, 8, 4, None, stream=0)
+    assert "epc_neighbour_mean_fwd" in str(e.value) and "argument 3" in str(e.value) and "idx" in str(e.value) and f32.asked == 0
+    assert L.lib().epc_last_error() == mark
+    # the same tensors pass at `void* workspace`: the call reaches the library, which refuses the null `x`
+    for ok in (f32, i32, bf16):
+        with pytest.raises(L.EpcNetError) as e:
+            L.run.epc_col_moments(None, 4, 4, None, None, ok, 0, stream=0)
+        assert e.value.status == L.EPC_EINVAL and "epc_col_moments: null pointer" in str(e.value) and ok.asked == 1
+    with pytest.raises(L.EpcNetError) as e:                                               # float32 passes at `const float* x`
+        L.run.epc_col_moments(f32, 4, 4, None, None, None, 0, stream=0)
+    assert e.value.status == L.EPC_EINVAL and f32.asked == 2
+    assert functions["epc_adam_multi"][1][5] == "long*"                                   # `const long* n` wants int64
+    with pytest.raises(L.EpcNetError) as e:
+        L.run.epc_adam_multi(0, None, None, None, None, i32, 0.0, 0.9, 0.999, 1e-8, 1, None, stream=0)
+    assert "argument 6" in str(e.value) and "torch.int64" in str(e.value) and i32.asked == 1
 
 
 def test_mirrored_struct_layouts_match_the_compiler(tmp_path):
