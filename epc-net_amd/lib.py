@@ -29,11 +29,12 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "epcnet.h")
 _SCALARS = {"int": c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "float": c_float,
             "size_t": ctypes.c_size_t, "int32_t": c_int32, "uint32_t": ctypes.c_uint32}
 # the dtype a tensor must have where the header declares a typed pointee (``run``); any dtype goes at every other pointer
-_POINTEES = {"float*": torch.float32, "int32_t*": torch.int32, "int*": torch.int32, "long*": torch.int64}
+_POINTEES = {"float*": torch.float32, "double*": torch.float64, "int32_t*": torch.int32, "int*": torch.int32, "long*": torch.int64}
 
 
-def parse_header(text: str):
-    """``(functions, constants, status)`` of the text of include/epcnet.h: ``functions[name] = (return type, [parameter
+def parse_header(text: str, need_status: bool = True):
+    """``(functions, constants, status)`` of the text of include/epcnet.h (or, with ``need_status=False``, of a further header in the
+    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h): ``functions[name] = (return type, [parameter
     types], [parameter names])`` in header order, the types as C type names without ``const`` and spaces around ``*`` -- a key
     of ``_SCALARS``, or any type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME>
     <integer>``; ``status``: the members of ``enum epc_status``.  Raises ValueError on whatever it does not understand."""
@@ -41,9 +42,9 @@ def parse_header(text: str):
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)         # extern "C" { and its }
     constants = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(EPC_\w+)[ \t]+(.*?)[ \t]*$", text, flags=re.M)}
     enum = re.search(r"typedef\s+enum\s+epc_status\s*\{(.*?)\}", text, flags=re.S)
-    if not enum:
+    if not enum and need_status:
         raise ValueError("epcnet.h: no enum epc_status")
-    status = {n.strip(): int(v, 0) for n, v in (m.split("=") for m in enum.group(1).split(","))}
+    status = {n.strip(): int(v, 0) for n, v in (m.split("=") for m in enum.group(1).split(","))} if enum else {}
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
     text = re.sub(r"typedef\s+(struct|enum)\s+\w+\s*(\{[^{}]*\})?\s*\w+\s*;", " ", text)
 
@@ -54,7 +55,7 @@ def parse_header(text: str):
     for decl in text.split(";"):
         if not decl.strip():
             continue
-        m = re.fullmatch(r"\s*([\w\s*]+?)\b(epc_\w+)\s*\((.*)\)\s*", decl, flags=re.S)
+        m = re.fullmatch(r"\s*([\w\s*]+?)\b(epc(?:net)?_\w+)\s*\((.*)\)\s*", decl, flags=re.S)
         if not m or m.group(2) in functions:
             raise ValueError("epcnet.h: not a declaration, or a second one of its name: %r" % " ".join(decl.split()))
         ret, name, params, names = ctype(m.group(1)), m.group(2), [], []
@@ -76,6 +77,17 @@ if not os.path.exists(HEADER_PATH):
         "There is no second copy of the declarations." % HEADER_PATH)
 with open(HEADER_PATH) as _f:
     _functions, _constants, _status = parse_header(_f.read())
+# the second header (relations and tuples from poses): the same grammar, its entries bound and callable like the others but listed on
+# their own -- EXPORTS stays what include/epcnet.h declares
+POSES_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_poses.h")
+if not os.path.exists(POSES_HEADER_PATH):
+    raise ImportError("%s is missing: the binding of the pose entries is derived from it" % POSES_HEADER_PATH)
+with open(POSES_HEADER_PATH) as _f:
+    _pose_functions, _pose_constants, _ = parse_header(_f.read(), need_status=False)
+if set(_pose_functions) & set(_functions) or set(_pose_constants) & set(_constants):
+    raise ImportError("epcnet_poses.h declares a name epcnet.h declares")
+_constants.update(_pose_constants)
+POSE_EXPORTS = list(_pose_functions)
 globals().update(_constants, **_status)     # EPC_OK, EPC_EINVAL, EPC_KNN_CAP, EPC_PRECISION_FAST, EPC_NUM_STAGES ... as module attributes
 # every symbol include/epcnet.h declares, in its order (tests check the library exports exactly these)
 EXPORTS = list(_functions)
@@ -124,7 +136,7 @@ _lib = ctypes.CDLL(LIB_PATH)
 
 # a pointer to a structure mirrored above keeps its type check; every other pointer is a void*
 _POINTERS = {"epc_cfg*": POINTER(EpcCfg), "epc_chain_fwd_args*": POINTER(ChainFwdArgs)}
-for _name, (_ret, _params, _) in _functions.items():
+for _name, (_ret, _params, _) in list(_functions.items()) + list(_pose_functions.items()):
     _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
     _fn.restype = c_char_p if _ret == "char*" else _SCALARS[_ret]
     _fn.argtypes = [_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
@@ -220,6 +232,9 @@ LAUNCHING = [_n for _n, (_, _t, _pn) in _functions.items() if _t and (_t[-1], _p
 for _name in LAUNCHING:
     assert _functions[_name][0] == "int", "%s takes a stream and does not return a status" % _name
     setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), *_functions[_name][1:])))
+for _name, (_ret, _t, _pn) in _pose_functions.items():          # every entry of include/epcnet_poses.h launches
+    assert _ret == "int" and (_t[-1], _pn[-1]) == ("void*", "stream"), "%s does not take a stream last and return a status" % _name
+    setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))
 
 
 def require_gpu() -> None:

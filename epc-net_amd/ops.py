@@ -1548,6 +1548,157 @@ def grid_downsample(points, offsets, n, normalize=True, out=None):
     return out, status, info
 
 
+def _device_poses(name, poses, device=None):
+    """(rows, 2) float64 poses (numpy or torch, host or device) -> a contiguous device tensor.  Any other dtype is refused, not
+    converted: float32 has a 0.5 m spacing at UTM northings, and a silent round trip through it would move the relations."""
+    import numpy as np
+    if isinstance(poses, np.ndarray):
+        if poses.dtype != np.float64:
+            raise EpcNetError(-1, "%s: poses must be float64, got %s (float32 UTM coordinates are 0.5 m apart)" % (name, poses.dtype))
+        poses = torch.from_numpy(np.ascontiguousarray(poses))
+    if not torch.is_tensor(poses) or poses.dtype != torch.float64:
+        raise EpcNetError(-1, "%s: poses must be a float64 numpy array or tensor, got %s"
+                          % (name, poses.dtype if torch.is_tensor(poses) else type(poses).__name__))
+    if poses.dim() != 2 or int(poses.shape[1]) != 2:
+        raise EpcNetError(-1, "%s: poses must be (rows, 2) = (northing, easting), got %s" % (name, tuple(poses.shape)))
+    L.require_gpu()
+    if device is None:
+        device = poses.device if poses.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise EpcNetError(-1, "%s: the poses go to a ROCm device (no CPU fallback)" % name)
+    return poses.to(device).contiguous()
+
+
+def _radius(r):
+    import ctypes
+    return ctypes.c_double(float(r))       # (lib.run passes ctypes objects on: the header's `const double* radius` in host memory)
+
+
+def pose_radius_lists(query_poses, db_poses, r, width=None, device=None):
+    """For each of the Q query poses the indices of the D database poses within ``r`` (inclusive, as sklearn's
+    ``KDTree.query_radius``; generate_test_sets.py:95-104), ascending: ``(padded (Q, width) int32, lens (Q,) int32)`` on the device,
+    rows padded with -2 -- the tables of ``retrieval.PackedTruth``.  Poses: (rows, 2) float64, numpy or torch.  ``width=None``: the
+    longest row's length (at least 1), from a count pass and ONE read of its maximum; a given ``width`` costs no host read, and a row
+    that does not fit raises ``EpcNetError`` (after a read of the status word) -- ``lens`` always holds the full lengths."""
+    import ctypes
+    q = _device_poses("pose_radius_lists", query_poses, device)
+    d = _device_poses("pose_radius_lists", db_poses, q.device)
+    Q, D, rad = int(q.shape[0]), int(d.shape[0]), _radius(r)
+    lens = torch.zeros(Q, dtype=torch.int32, device=q.device)
+    if Q == 0 or D == 0:
+        return torch.full((Q, max(int(width or 1), 1)), -2, dtype=torch.int32, device=q.device), lens
+    with torch.cuda.device(q.device):
+        given = width is not None
+        if not given:
+            L.run.epcnet_pose_radius_count(q, Q, d, D, ctypes.byref(rad), lens)
+            width = max(int(lens.max().item()), 1)
+        width = int(width)
+        if width <= 0:
+            raise EpcNetError(-1, "pose_radius_lists: width must be positive")
+        padded = torch.empty((Q, width), dtype=torch.int32, device=q.device)
+        status = torch.zeros(1, dtype=torch.int32, device=q.device)
+        L.run.epcnet_pose_radius_fill(q, Q, d, D, ctypes.byref(rad), width, lens, padded, status)
+        if given and int(status.item()) != 0:
+            raise EpcNetError(-1, "pose_radius_lists: a row holds %d entries, width is %d (the lists were truncated)"
+                              % (int(lens.max().item()), width))
+    return padded, lens
+
+
+class PoseTuples:
+    """Training tuples drawn on the device from the records' poses (include/epcnet_poses.h;
+    numpy restatement: tests/tuples_ref.py) -- what generate_training_tuples_baseline.py's pickles and
+    ``loading_pointclouds.get_query_tuple_ids`` do with Python lists, without any list: the (T, 2) float64 poses stay on the device and
+    every relation is decided from them when it is needed.  Record i's positives are the other records within ``r_pos`` (inclusive),
+    its negatives those strictly beyond ``r_neg``.  ``counts`` (T,) int32: the number of positives per record, computed once.
+    The draw is a fixed hash of (seed, step, key, stream, id), so it does not depend on thread order and ``tuples_ref`` draws the same
+    tuples; it is NOT Python's ``random`` stream."""
+
+    def __init__(self, poses, r_pos: float = 10.0, r_neg: float = 50.0, seed: int = 0, device=None):
+        import ctypes
+        self.poses = _device_poses("PoseTuples", poses, device)
+        self.device = self.poses.device
+        self.T = int(self.poses.shape[0])
+        if not 0 < self.T <= 1 << 24:
+            raise EpcNetError(-1, "PoseTuples: between 1 and 2^24 records, got %d" % self.T)
+        self.r_pos, self.r_neg, self.seed = float(r_pos), float(r_neg), int(seed)
+        self._rp, self._rn = _radius(self.r_pos), _radius(self.r_neg)
+        self.counts = torch.empty(self.T, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            L.run.epcnet_pose_pos_count(self.poses, self.T, ctypes.byref(self._rp), self.counts)
+        self._slots = {}             # per batch size: the sticky status words and the key that set them
+
+    def __len__(self) -> int:
+        return self.T
+
+    @staticmethod
+    def _i64(v: int) -> int:
+        v &= (1 << 64) - 1
+        return v - (1 << 64) if v >> 63 else v
+
+    def _keys(self, name, keys):
+        if not torch.is_tensor(keys) or not keys.is_cuda or keys.dtype != torch.int32 or not keys.is_contiguous() or keys.dim() != 1:
+            raise EpcNetError(-1, "PoseTuples.%s: keys must be a contiguous 1-d int32 tensor on the ROCm device" % name)
+        B = int(keys.numel())
+        if B not in self._slots:
+            self._slots[B] = (torch.zeros(B, dtype=torch.int32, device=self.device),
+                              torch.full((B,), -1, dtype=torch.int32, device=self.device))
+        return B, self._slots[B]
+
+    def candidates(self, keys, step: int, C: int = 4000, out=None):
+        """Phase A (epcnet_tuple_candidates): per key the min(C, #negatives) negatives with the smallest (hash, id) of stream 1, ascending by
+        id -> ``(cand (B, C) int32, cand_count (B,) int32)``, the buffers ``retrieval.mine_topk`` takes.  ``keys``: (B,) int32 on the
+        device, read when the kernel runs.  ``out``: a (cand, cand_count) pair to write into.  One launch, no host read."""
+        import ctypes
+        B, (status, flagged) = self._keys("candidates", keys)
+        C = int(C)
+        cand, count = out if out is not None else (torch.empty((B, C), dtype=torch.int32, device=self.device),
+                                                   torch.empty(B, dtype=torch.int32, device=self.device))
+        if tuple(cand.shape) != (B, C) or int(count.numel()) != B or not cand.is_contiguous():
+            raise EpcNetError(-1, "PoseTuples.candidates: `out` must be contiguous (B, C) and (B,) int32 tensors")
+        with torch.cuda.device(self.device):
+            L.run.epcnet_tuple_candidates(self.poses, self.T, keys, B, ctypes.byref(self._rn), self._i64(self.seed), self._i64(int(step)), C,
+                                       cand, count, status, flagged)
+        return cand, count
+
+    def sample(self, keys, step: int, P: int, Nn: int, hard=None):
+        """Phase B (epcnet_tuple_sample): ``(ids (B, 1 + P + Nn + 1) int32, status (B,) int32)`` on the device -- per key {key, P positives,
+        Nn negatives, other negative} in ``TrainStep.step_ids``' order.  ``hard`` (B, H <= 32) int32 on the device or None: taken first
+        (entries < 0 or >= T and repeats dropped, e.g. ``mine_topk``'s ids as they are), the rest filled from the negatives.  A slot
+        that cannot be filled is -1; ``status`` is the sticky word ``check`` reads.  One launch, no host read."""
+        import ctypes
+        B, (status, flagged) = self._keys("sample", keys)
+        H = 0
+        if hard is not None:
+            if not torch.is_tensor(hard) or not hard.is_cuda or hard.dtype != torch.int32 or not hard.is_contiguous() \
+                    or hard.dim() != 2 or int(hard.shape[0]) != B:
+                raise EpcNetError(-1, "PoseTuples.sample: hard must be a contiguous (B, H) int32 tensor on the ROCm device")
+            H = int(hard.shape[1])
+        ids = torch.empty((B, 1 + int(P) + int(Nn) + 1), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            L.run.epcnet_tuple_sample(self.poses, self.T, keys, B, ctypes.byref(self._rp), ctypes.byref(self._rn), self._i64(self.seed),
+                                   self._i64(int(step)), int(P), int(Nn), hard if H else None, H, ids, status, flagged)
+        return ids, status
+
+    KINDS = ((L.EPC_TUPLE_FEW_POSITIVES, "fewer positives than asked for"), (L.EPC_TUPLE_FEW_NEGATIVES, "fewer negatives than asked for"),
+             (L.EPC_TUPLE_NO_OTHER, "no eligible other negative"), (L.EPC_TUPLE_BAD_KEY, "key outside the records"))
+
+    def check(self) -> None:
+        """Read the status words of every ``candidates`` / ``sample`` since the last check (a device synchronisation) and clear them;
+        raises EpcNetError naming, per batch slot, the last key that set a bit and the kinds seen in that slot."""
+        bad = []
+        for B, (status, flagged) in sorted(self._slots.items()):
+            words, keys = status.cpu().tolist(), flagged.cpu().tolist()
+            if any(words):
+                status.zero_()
+                flagged.fill_(-1)
+            for b, (w, k) in enumerate(zip(words, keys)):
+                if w:
+                    bad.append("key %d (slot %d of %d): %s" % (k, b, B, ", ".join(t for bit, t in self.KINDS if w & bit)))
+        if bad:
+            raise EpcNetError(-1, "PoseTuples: " + "; ".join(bad))
+
+
 def adam_step(w, m, v, g, lr, t, beta1=0.9, beta2=0.999, eps=1e-8):
     """tf.train.AdamOptimizer update of one tensor, in place (train.py:273).  ``lr`` may be a one-element device tensor
     holding the bias-corrected rate lr_t (``t`` is then ignored): the form a captured HIP graph of the step uses."""

@@ -7,6 +7,7 @@
   mine_topk            train.py:857-869     the hard-negative KDTree query over rows named by id (epc_mine_topk)
   get_recall           evaluate.py:455-537  recall@1..25, top-1 % recall, top-1 similarity for one (m, n) run pair
   evaluate_runs        evaluate.py:293-332  average over all ordered pairs m != n
+  truth_from_poses     generate_test_sets.py:95-104  the truth sets from the runs' poses, on the device (epcnet_pose_radius_fill)
   evaluate_sharded     evaluate.py:293-332 end to end over the ranks of a process group (BASELINE.json configs[4]):
                        extraction of every run sharded over the ranks -> ONE all-gather of the descriptors -> every rank
                        ranks AND books its share of the queries on its device -> ONE all-reduce of integer counters
@@ -246,6 +247,29 @@ def pack_truth(truth, n_dbs: Sequence[int], n_qs: Sequence[int]) -> PackedTruth:
             raise ValueError("packed truth was built for other run sizes")
         return truth
     return PackedTruth(truth, n_dbs, n_qs)
+
+
+def truth_from_poses(db_poses_per_run, query_poses_per_run, r: float = 25.0, device=None) -> PackedTruth:
+    """The evaluation truth of generate_test_sets.py:95-104 from the runs' poses, built on the device: query i of run n has as true
+    neighbours in database run m the poses of m within ``r`` metres (inclusive, ``KDTree.query_radius``).  ``*_poses_per_run``: one
+    (rows, 2) float64 (northing, easting) array per run, numpy or torch.  Returns a ``PackedTruth`` already on the device whose tables
+    equal ``pack_truth`` over the brute-force lists (``ops.pose_radius_lists``: one count and one fill launch per database run);
+    ``evaluate_runs`` / ``evaluate_sharded`` take it as it is."""
+    from . import ops
+    dbs = [ops._device_poses("truth_from_poses", p, device) for p in db_poses_per_run]
+    dev = dbs[0].device if dbs else torch.device("cuda", torch.cuda.current_device())
+    qs = [ops._device_poses("truth_from_poses", p, dev) for p in query_poses_per_run]
+    packed = PackedTruth.__new__(PackedTruth)
+    packed.n_dbs, packed.n_qs = [int(p.shape[0]) for p in dbs], [int(p.shape[0]) for p in qs]
+    packed.padded, packed.lens = [], []
+    for m in range(len(dbs)):
+        others = [qs[n] for n in range(len(qs)) if n != m]
+        rows = torch.cat(others, 0) if others else torch.empty((0, 2), dtype=torch.float64, device=dev)
+        pad, lens = ops.pose_radius_lists(rows, dbs[m], r, device=dev)
+        packed.padded.append(pad)
+        packed.lens.append(lens)
+    packed.device = dev
+    return packed
 
 
 SIM_FIXED_BITS = 40      # top-1 similarities are summed as round(score * 2^40) in int64: exact, order- and shard-independent

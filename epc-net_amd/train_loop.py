@@ -35,10 +35,11 @@ EVAL_BATCHES = 5       # train.py:527
 
 
 class Trainer:
-    def __init__(self, step, train_queries: Dict[int, dict], train_data: np.ndarray,
+    def __init__(self, step, train_queries: Optional[Dict[int, dict]], train_data: np.ndarray,
                  test_queries: Optional[Dict[int, dict]] = None, test_data: Optional[np.ndarray] = None,
                  save_path: Optional[str] = None, logger: Optional[logging.Logger] = None, graph: bool = False,
-                 bank: bool = False, device_mining: bool = False):
+                 bank: bool = False, device_mining: bool = False, poses=None, tuple_seed: int = 0, r_pos: float = 10.0,
+                 r_neg: float = 50.0):
         """``step``: a TrainStep / DistillStep; ``*_queries``: the pickles of generate_training_tuples (key -> {'query',
         'positives', 'negatives'}); ``*_data``: (T, 4096, INPUT_DIM) float32 arrays in key order (train.py:159-190).
         ``bank=True``: ``train_data`` is uploaded ONCE into an ``ops.CloudBank`` (sorted clouds + finished kNN graphs, ~0.65 MB per
@@ -48,9 +49,20 @@ class Trainer:
         unless ``device_mining=True`` (needs the bank): the query's descriptor and the refreshed descriptor cache then come from the
         bank's records by id (``engine.forward_bank``) and stay on the device, and the hard negatives of a key are searched there
         (``retrieval.mine_topk``) -- per key one upload of the sampled ids and one copy of the NUM_TO_TAKE mined ids back; the
-        shuffles and the tuple logic stay on the host, so a seeded run mines the same negatives and steps alike, bit for bit."""
+        shuffles and the tuple logic stay on the host, so a seeded run mines the same negatives and steps alike, bit for bit.
+        ``poses`` ((T, 2) float64 northing / easting of the records, numpy or torch; needs ``bank=True, device_mining=True``): the
+        tuples are drawn on the device from the poses (``ops.PoseTuples``: positives within ``r_pos``, negatives beyond ``r_neg``, the
+        reference's other-negative rule) and ``train_queries`` may be None -- no pickle, no Python lists.  Per iteration: candidates ->
+        ``forward_bank`` -> ``mine_topk`` (both only once a descriptor cache exists) -> sample -> ``step_ids``, all on the device; the
+        only host read is the loss.  Keys with fewer than P positives leave the epoch's permutation up front.  The draw is a fixed hash of
+        (``tuple_seed``, global step, key): a NEW sampling stream -- deterministic, but it does not reproduce a seeded run of the host
+        path.  ``HARD_NEGATIVES`` is not consulted on this path; ``evaluate_loss`` keeps reading ``test_queries``."""
         if device_mining and not bank:
             raise ValueError("device_mining=True needs bank=True: the mining reads the clouds by record id")
+        if poses is not None and not (bank and device_mining):
+            raise ValueError("poses= needs bank=True and device_mining=True: the tuples are drawn and mined on the device by record id")
+        if poses is None and train_queries is None:
+            raise ValueError("train_queries may be None only with poses=")
         self.step = step
         self.params = step.params
         self.TRAINING_QUERIES, self.train_data = train_queries, train_data
@@ -72,6 +84,12 @@ class Trainer:
         self.device_mining = bool(device_mining)
         self._table_src, self._table_dev = None, None       # the caller's numpy descriptor cache and its device copy (by identity)
         self._mine_host, self._mine_dev, self._mine_ws = None, None, None
+        self.tuples, self._enough, self._cand = None, None, None
+        if poses is not None:
+            from . import ops
+            self.tuples = ops.PoseTuples(poses, r_pos=r_pos, r_neg=r_neg, seed=tuple_seed, device=self.device)
+            if len(self.tuples) != int(train_data.shape[0]):
+                raise ValueError("poses has %d rows for %d training clouds" % (len(self.tuples), int(train_data.shape[0])))
 
     def _build_bank(self, data: np.ndarray):
         """Upload ``data`` (T, n, 3) into a CloudBank, in slices that bound the staging copy; logs the one-time cost."""
@@ -171,6 +189,25 @@ class Trainer:
         # (a slot without a neighbour at a finite distance indexes the list with -1 on the host path: its last entry)
         return [int(v) if v >= 0 else int(negatives[-1]) for v in ids[0].cpu().tolist()]
 
+    def _tuple_ids_from_poses(self, keys: torch.Tensor):
+        """The id tensors of ``step.step_ids`` for ``keys`` ((B,) int32 on the device), drawn there: candidates -> descriptor of the key
+        -> mined hard negatives (once a descriptor cache exists: train.py:373-377 / :390-395) -> sample.  Four launches plus the
+        inference pass; nothing is read back."""
+        from .retrieval import mine_topk
+        step, hard = int(self.step.global_step), None
+        if len(self.TRAINING_LATENT_VECTORS) != 0:
+            B = int(keys.numel())
+            if self._cand is None or int(self._cand[0].shape[0]) != B:
+                self._cand = (torch.empty((B, SAMPLED_NEG), dtype=torch.int32, device=self.device),
+                              torch.empty(B, dtype=torch.int32, device=self.device),
+                              torch.empty(int(L.lib().epc_mine_topk_workspace_bytes(B, SAMPLED_NEG)), dtype=torch.uint8, device=self.device))
+            cand, count = self.tuples.candidates(keys, step, SAMPLED_NEG, out=self._cand[:2])
+            self.step._ensure_built(self.bank.n)
+            query = self._engine().forward_bank(self.bank, keys)
+            _, _, hard = mine_topk(self._mining_table(), query, cand, count, NUM_TO_TAKE, workspace=self._cand[2])
+        ids, _ = self.tuples.sample(keys, step, self.P, self.N, hard=hard)
+        return ids[:, :1], ids[:, 1:1 + self.P], ids[:, 1 + self.P:1 + self.P + self.N], ids[:, 1 + self.P + self.N:]
+
     def _hard_negatives(self, key: int) -> List[int]:
         """train.py:373-377 / :390-395 (the three cache states)."""
         if len(self.TRAINING_LATENT_VECTORS) == 0:
@@ -192,7 +229,7 @@ class Trainer:
         """train.py:330-617.  ``max_iters`` truncates the epoch (tests / smoke runs); None = the whole epoch."""
         from . import distributed as D
         rank, world = D.world()
-        idxs = np.arange(0, len(self.TRAINING_QUERIES.keys()))
+        idxs = np.arange(0, len(self.tuples) if self.tuples is not None else len(self.TRAINING_QUERIES.keys()))
         np.random.shuffle(idxs)
         if world > 1:
             # data-parallel over tuples (SURVEY.md 8e): every rank must walk the SAME permutation (rank 0's) and take its own
@@ -200,16 +237,28 @@ class Trainer:
             perm = torch.as_tensor(idxs, dtype=torch.int64, device=self.device)
             D.broadcast_tensors([perm], src=0)
             idxs = perm.cpu().numpy()
+        perm_dev = None
+        if self.tuples is not None:
+            # the reference's "FAULTY TUPLE" (fewer than P positives), decided once from the device-side counts instead of per step
+            if self._enough is None:
+                self._enough = (self.tuples.counts >= self.P).cpu().numpy()
+            kept = idxs[self._enough[idxs]]
+            self.log.info("Epoch %d: %d of %d keys have fewer than %d positives and are left out", epoch, len(idxs) - len(kept),
+                          len(idxs), self.P)
+            idxs = kept
+            perm_dev = torch.from_numpy(idxs.astype(np.int32)).to(self.device)     # the epoch's keys, uploaded once
         iter_num = len(idxs) // (self.B * world)
         losses = []
         for i in range(iter_num if max_iters is None else min(iter_num, max_iters)):
             base = (i * world + rank) * self.B
             keys = idxs[base:base + self.B]
-            if self.bank is not None:
+            if perm_dev is not None:
+                batch, why = self._tuple_ids_from_poses(perm_dev[base:base + self.B]), ""
+            elif self.bank is not None:
                 batch, why = self._tuple_ids(keys, self.TRAINING_QUERIES, self._hard_negatives)
             else:
                 batch, why = self._tuples(keys, self.TRAINING_QUERIES, self.train_data, self._hard_negatives)
-            if not D.all_true(batch is not None, self.device):
+            if perm_dev is None and not D.all_true(batch is not None, self.device):
                 # a rank that skipped alone would leave the others waiting in the gradient all-reduce
                 self.log.info("Epoch: [%d/%d][%d/%d] %s!!!", epoch, self.max_epoch, i + 1, iter_num,
                               why or "another rank drew a faulty tuple")
@@ -219,6 +268,8 @@ class Trainer:
             else:
                 loss, lr, _ = self.step.step(*batch, epoch=epoch, graph=self.graph) if self.graph else self.step.step(*batch, epoch=epoch)
             losses.append(float(loss))
+            if not np.isfinite(losses[-1]) and self.tuples is not None:
+                self.tuples.check()     # a slot the draw could not fill (-1: too few negatives, no other negative) raises here, naming the key
             if not np.isfinite(losses[-1]) and self.bank is not None:
                 self.bank.check()       # an id outside the bank (a query dict that does not match train_data) raises here, naming the slot
             if not np.isfinite(losses[-1]):

@@ -192,7 +192,8 @@ class TrainStep:
 
     def step_ids(self, bank, query_ids, positive_ids, negative_ids, other_ids, epoch: int = 0, graph: bool = False):
         """``step`` on clouds of a device-resident ``ops.CloudBank``, named by their record ids: (B,1), (B,P), (B,Nn), (B,1) integer
-        tensors or arrays.  The batch -- sorted clouds and their finished kNN graph -- is assembled from the bank in one launch
+        tensors or arrays; four int32 tensors on the bank's device (``ops.PoseTuples.sample``) are copied device to device, without a read
+        or a synchronisation.  The batch -- sorted clouds and their finished kNN graph -- is assembled from the bank in one launch
         (epc_bank_assemble) instead of being sorted, searched and transposed again; every later kernel reads the same bits, so the
         step is the one ``step`` runs on the same clouds.  ``graph=True``: the ids live in a static device buffer that is refreshed
         before every replay, like the schedule values, and the assemble launch is INSIDE the captured graph (the first of the three
@@ -201,23 +202,33 @@ class TrainStep:
         to the state before it); ``bank.check()`` names the slot.  An abandoned persistent launch gives a NaN loss as in ``step``."""
         import numpy as np
         p = self.params
-        parts = [np.asarray(x.detach().cpu() if torch.is_tensor(x) else x).astype(np.int64) for x in
-                 (query_ids, positive_ids, negative_ids, other_ids)]
+        given = (query_ids, positive_ids, negative_ids, other_ids)
+        on_device = all(torch.is_tensor(x) and x.is_cuda and x.device == bank.device and x.dtype == torch.int32 for x in given)
+        if on_device:
+            # ids drawn on the device (ops.PoseTuples.sample): device to device into the static id buffer, nothing read back and no
+            # synchronisation -- the four slices of one (B, 1 + P + Nn + 1) tensor are that tensor, anything else is joined there
+            parts = given
+        else:
+            parts = [np.asarray(x.detach().cpu() if torch.is_tensor(x) else x).astype(np.int64) for x in given]
         B = int(parts[0].shape[0])
         if any(x.ndim != 2 or x.shape[0] != B for x in parts) or parts[0].shape[1] != 1 or parts[3].shape[1] != 1:
-            raise ValueError("step_ids: ids must be (B,1), (B,P), (B,Nn), (B,1); got %s" % ([x.shape for x in parts],))
-        ids = np.ascontiguousarray(np.concatenate(parts, 1).reshape(-1)).astype(np.int32)       # train.py:252's order, per query
+            raise ValueError("step_ids: ids must be (B,1), (B,P), (B,Nn), (B,1); got %s" % ([tuple(x.shape) for x in parts],))
+        if on_device:
+            joined = _joined_along_dim1(parts)
+            ids_t = (joined if joined is not None and joined.is_contiguous() else torch.cat(parts, 1)).reshape(-1)
+        else:
+            ids_t = torch.from_numpy(np.ascontiguousarray(np.concatenate(parts, 1).reshape(-1)).astype(np.int32))   # train.py:252's order
         self._ensure_built(bank.n)
         bn_decay = get_bn_decay(self.global_step, p.get("BATCH_NUM_QUERIES", B), p.get("DECAY_STEP", 200000))
         lr = get_learning_rate(epoch, p.get("BASE_LEARNING_RATE", 5e-5))
         t = self.global_step + 1
         sizes = [int(x.shape[1]) for x in parts]
         if graph:
-            loss = self._graphed_step(None, None, None, None, lr, bn_decay, t, bank=(bank, torch.from_numpy(ids), B, sizes))
+            loss = self._graphed_step(None, None, None, None, lr, bn_decay, t, bank=(bank, ids_t, B, sizes))
             src = self._graph["source"]
         else:
-            src = self._bank_source(bank, ids.size, B, sizes, bank.device)
-            src["ids"].copy_(torch.from_numpy(ids))
+            src = self._bank_source(bank, int(ids_t.numel()), B, sizes, bank.device)
+            src["ids"].copy_(ids_t)
             loss = self._eager_step(*src["in"], lr, bn_decay, t, source=src)
         self.store.bump(self.outer or None)
         self.global_step += 1
@@ -481,7 +492,8 @@ class TrainStep:
         return out
 
     def _graphed_step(self, query, positives, negatives, other_neg, lr, bn_decay, t, bank=None):
-        """``bank`` (step_ids): (CloudBank, ids (T,) int32 on the host, B, [1, P, Nn, 1]) instead of the four tensors."""
+        """``bank`` (step_ids): (CloudBank, ids (T,) int32 on the host or on the bank's device, B, [1, P, Nn, 1]) instead of the four
+        tensors."""
         from . import distributed as D
         inputs = (query, positives, negatives, other_neg)
         if bank is not None:

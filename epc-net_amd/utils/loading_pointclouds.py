@@ -137,6 +137,30 @@ def get_query_tuple_ids(idx, dict_value, num_pos, num_neg, QUERY_DICT, hard_neg=
     return [idx, pos_indices, neg_indices, [possible_negs[0]]]
 
 
+def query_dict_from_poses(poses, r_pos: float = 10.0, r_neg: float = 50.0, names: Optional[Sequence[str]] = None) -> Dict[int, dict]:
+    """generate_training_tuples_baseline.py:52-62 without its pandas / sklearn pass and without its final shuffle of each list: the
+    training dict {i: {'query', 'positives', 'negatives'}} from (T, 2) float64 poses (northing, easting), positives = the other records
+    within ``r_pos`` (inclusive), negatives = every record that is not within ``r_neg``, both ascending.  The radius lists come from the
+    device (``ops.pose_radius_lists``); the Python lists are built here, on the host -- this form costs O(T^2) list entries and serves
+    small sets and the existing host path; ``Trainer(poses=...)`` needs no dict at all.  ``names``: the 'query' file names (default
+    "<i>.bin")."""
+    from .. import ops
+    poses = np.asarray(poses) if not hasattr(poses, "is_cuda") else poses
+    T = int(poses.shape[0])
+    out: Dict[int, dict] = {}
+    everyone = np.arange(T)
+    for a in range(0, T, 2048):                              # bounds the padded r_neg table: 2048 x (longest row) int32
+        near, near_len = (t.cpu().numpy() for t in ops.pose_radius_lists(poses[a:a + 2048], poses, r_pos))
+        far, far_len = (t.cpu().numpy() for t in ops.pose_radius_lists(poses[a:a + 2048], poses, r_neg))
+        for i in range(near.shape[0]):
+            key = a + i
+            pos = near[i, :near_len[i]]
+            out[key] = {"query": names[key] if names is not None else "%d.bin" % key,
+                        "positives": pos[pos != key].tolist(),
+                        "negatives": np.setdiff1d(everyone, far[i, :far_len[i]], assume_unique=True).tolist()}
+    return out
+
+
 def get_random_hard_negatives(query_vec, random_negs: Sequence[int], num_to_take: int, latent_vectors,
                               search=None) -> List[int]:
     """train.py:857-869: the ``num_to_take`` sampled negatives whose cached descriptors are nearest to the query's.
