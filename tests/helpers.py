@@ -23,29 +23,31 @@ def pkg(name=""):
     return importlib.import_module("epc-net_amd" + ("." + name if name else ""))
 
 
-def make_store(arch, weights, device):
+def make_store(arch, weights, device, params=None):
     """Variable store holding `weights` (oracle names, relative to OUTER) under the reference's full names."""
     V = pkg("variables")
     st = V.reset_default_store(device=device, seed=0)
     M = pkg("models." + arch)
     with V.variable_scope(OUTER):
-        M.declare_variables(PARAMS, 4096)
+        M.declare_variables(params or PARAMS, 4096)
     st.load_state_dict({OUTER + "/" + k: v for k, v in weights.items()}, strict=True)
     return st
 
 
-def make_engine(arch, weights, device="cuda", micro_batch=0, precision=None, in_flight=None):
+def make_engine(arch, weights, device="cuda", micro_batch=0, precision=None, in_flight=None, params=None):
     """`precision`: None = the PRODUCT default (engine.py: 'f32', the f32-equivalent split arithmetic) / 'f32' / 'fast' (EPC-Net's
-    f16 + f6 kernels, an explicit opt-in; EPC-Net-L ignores it).  Tests whose subject is the fast path pass 'fast'."""
+    f16 + f6 kernels, an explicit opt-in; EPC-Net-L ignores it).  Tests whose subject is the fast path pass 'fast'.
+    `params`: the configuration (default PARAMS) -- the weights must have been drawn for it."""
     E = pkg("engine")
-    st = make_store(arch, weights, device)
-    return E.InferenceEngine(arch, PARAMS, st, outer=OUTER, micro_batch=micro_batch, precision=precision, in_flight=in_flight), st
+    st = make_store(arch, weights, device, params)
+    return E.InferenceEngine(arch, params or PARAMS, st, outer=OUTER, micro_batch=micro_batch, precision=precision, in_flight=in_flight), st
 
 
 def run_stages(eng, xyz):
     """Run the pipeline stage by stage through the C ABI, returning every intermediate as a torch tensor.
     EPC-Net's block chain runs on fp16 rows (x16 -> out16 / x_next16), EPC-Net-L's on f32 rows: `xs` / `cat` are
     returned in the dtype the stage wrote."""
+    import stage_ref as R          # (the fragment decoders; it imports this module)
     L = pkg("lib")
     E = pkg("engine")
     lib = L.lib()
@@ -98,12 +100,8 @@ def run_stages(eng, xyz):
                                              assign.data_ptr(), assignf.data_ptr(), apart.data_ptr(), status.data_ptr(), st))
             L.check(lib.epc_vlad_aggregate_fwd(featf.data_ptr(), assignf.data_ptr(), rnorm.data_ptr(), apart.data_ptr(),
                                                off(6), nc, n, vlad.data_ptr(), colss.data_ptr(), st))
-            # unpack the fragment order (include/epcnet.h): [tile g][chunk c][half s][lane l][q] ->
-            # feat[32g + (l&31)][32c + 16s + 8(q>>2) + 4(l>>5) + (q&3)]   (fp16: 11 significant bits)
-            ff = featf.float().reshape(M // 32, 32, 2, 2, 32, 2, 4)        # (g, c, s, h, j, q>>2, q&3)
-            feat = ff.permute(0, 4, 1, 2, 5, 3, 6).reshape(nc, n, 1024)    # (g, j, c, s, q>>2, h, q&3) -> point-major
-            af = assignf.float().reshape(M // 32, 2, 2, 2, 32, 8) / 16384.0
-            aprime = af.permute(0, 2, 3, 5, 1, 4).reshape(nc, n, 64) * rnorm.reshape(nc, n, 1)   # assign * rnorm
+            feat = R.decode_feat_f16(featf, M).reshape(nc, n, 1024)
+            aprime = R.decode_assign_f16(assignf, M).reshape(nc, n, 64) * rnorm.reshape(nc, n, 1)   # assign * rnorm
         else:
             featf = torch.empty((M // 32, 32, 3, 64, 16), dtype=torch.uint8, device=dev)
             assignf = torch.empty((M // 32, 2, 2, 2, 64, 8), dtype=torch.bfloat16, device=dev)
@@ -111,16 +109,8 @@ def run_stages(eng, xyz):
                                                  assign.data_ptr(), assignf.data_ptr(), apart.data_ptr(), st))
             L.check(lib.epc_vlad_aggregate_f32_fwd(featf.data_ptr(), assignf.data_ptr(), rnorm.data_ptr(),
                                                    apart.data_ptr(), off(6), nc, n, vlad.data_ptr(), colss.data_ptr(), st))
-            # 3-byte values (include/epcnet.h): the 48 bytes of lane l of (tile g, chunk c) -- its three 16-byte pieces
-            # concatenated -- are 16 little-endian values; with li = l & 15, q = l >> 4, value 4t + r (t = 2g2 + p) ->
-            # feat[32g + 16p + li][32c + 16g2 + 4q + r]   (conv5_f32.hip's 16x16x32 accumulator order)
-            by = featf.permute(0, 1, 3, 2, 4).reshape(M // 32, 32, 64, 16, 3).to(torch.int32)       # (g, c, l, value, byte)
-            bits = (by[..., 0] << 8) | (by[..., 1] << 16) | (by[..., 2] << 24)
-            ff = bits.view(torch.float32).reshape(M // 32, 32, 4, 16, 2, 2, 4)                       # (g, c, q, li, g2, p, r)
-            feat = ff.permute(0, 5, 3, 1, 4, 2, 6).reshape(nc, n, 1024)                              # (g, p, li, c, g2, q, r)
-            # [tile g][t][s][part][lane l][q] -> a[32g + 16s + 8(l>>5) + q][32t + (l&31)], hi + lo
-            af = assignf.float().sum(3).reshape(M // 32, 2, 2, 2, 32, 8)   # (g, t, s, h, j, q)
-            aprime = af.permute(0, 2, 3, 5, 1, 4).reshape(nc, n, 64) * rnorm.reshape(nc, n, 1)
+            feat = R.decode_feat_b3(featf, M).reshape(nc, n, 1024)
+            aprime = R.decode_assign_bf16x2(assignf, M).reshape(nc, n, 64) * rnorm.reshape(nc, n, 1)
         wsb = lib.epc_vlad_head_workspace_bytes(nc, cfg.groups)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         L.check(lib.epc_vlad_head_fwd(vlad.data_ptr(), colss.data_ptr(), off(6), cfg.groups, nc, desc.data_ptr(),
