@@ -213,17 +213,28 @@ class InferenceEngine:
         return out
 
     def forward_scans(self, points: torch.Tensor, offsets: torch.Tensor, num_points: int = 4096, normalize: bool = True,
-                      out: Optional[torch.Tensor] = None):
+                      out: Optional[torch.Tensor] = None, ground=None):
         """Descriptors of RAW scans: ``points`` (total, 3) float32 and ``offsets`` (B + 1,) int32 on the device (``ops.pack_scans``), any
         number of points per scan -> ``(descriptors (B, FEATURE_OUTPUT_DIM), status (B,) int32)``.  Runs ``ops.grid_downsample`` (to
         ``num_points`` points per cloud; include/epcnet.h: epc_grid_downsample) and then ``forward`` on the same stream, no host round
         trip in between -- bit-identical to ``forward(ops.grid_downsample(points, offsets, num_points, normalize)[0])``, and capturable
         in a graph (the offsets are read when the kernel runs).  ``status`` holds the down-sampler's words: a scan flagged
         EPC_STATUS_NO_GRID reaches the network as NaN rows, so its descriptor is NaN and ``last_status`` reports
-        EPC_STATUS_NONFINITE_INPUT for it."""
+        EPC_STATUS_NONFINITE_INPUT for it.
+
+        ``ground=True``, or a dict of ``ops.remove_ground``'s keyword arguments, removes the ground plane of every scan first
+        (include/epcnet_scans.h), on the same stream and into a copy of the rows: the networks were trained on clouds without their
+        ground.  ``status`` is then the down-sampler's word ORed with the removal's (EPC_STATUS_NO_GROUND: no plane was found, the
+        scan went on as it came).  ``None``, the default, is the path above unchanged."""
         from . import ops
-        xyz, status, _ = ops.grid_downsample(points, offsets, num_points, normalize=normalize)
-        return self.forward(xyz, out=out), status
+        if ground is None or ground is False:
+            xyz, status, _ = ops.grid_downsample(points, offsets, num_points, normalize=normalize)
+            return self.forward(xyz, out=out), status
+        if ground is not True and not isinstance(ground, dict):
+            raise L.EpcNetError(-1, "forward_scans: `ground` is None, True or a dict of ops.remove_ground's arguments")
+        kept, st_ground, _, _ = ops.remove_ground(points, offsets, **({} if ground is True else ground))
+        xyz, status, _ = ops.grid_downsample(kept, offsets, num_points, normalize=normalize)
+        return self.forward(xyz, out=out), status | st_ground
 
     def last_status(self, xyz_or_count) -> "list[int]":
         """Per-cloud EPC_STATUS_* words of the last pass of the most recent ``forward`` call on this engine's own

@@ -1548,6 +1548,52 @@ def grid_downsample(points, offsets, n, normalize=True, out=None):
     return out, status, info
 
 
+def remove_ground(points, offsets, threshold=0.2, max_tilt_deg=15.0, hypotheses=256, draws=8, min_share=0.05, max_z=float("inf"), seed=0,
+                  out=None):
+    """Ragged raw scans -> the same rows without the ground (include/epcnet_scans.h: epcnet_ground_remove; numpy restatement:
+    tests/ground_ref.py): ``(points_out (total, 3) float32, status (B,) int32, plane (B, 4) float32, info (B, 4) int32)``, all device
+    tensors, four launches on the current stream, no host read.  Per scan a deterministic plane RANSAC (``hypotheses`` planes, each vertex
+    the lowest of ``draws`` hashed rows) finds the largest plane tilted at most ``max_tilt_deg`` against z -- the frame is the sensor's,
+    z up -- and below ``max_z`` at the sensor's axis; the rows within ``threshold`` metres of it AND every row below it become NaN
+    rows, which ``grid_downsample`` drops: the result goes to ``grid_downsample``, ``InferenceEngine.forward_scans`` or a bank as it is.
+    One plane, not a terrain model.  A scan whose best plane holds fewer than 3 or fewer than ``min_share`` of its finite rows gets the
+    status word EPC_STATUS_NO_GROUND, a NaN ``plane`` and its rows back unchanged.  ``plane``: n_x, n_y, n_z, d0 (not normalised);
+    ``info``: finite rows, valid hypotheses, the best one, its score.  ``out=points`` runs in place.  ``hypotheses``: a multiple of 64
+    in [64, 1024]; ``draws`` in [1, 16]."""
+    import math
+    for name, t, dt in (("points", points, torch.float32), ("offsets", offsets, torch.int32)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise EpcNetError(-1, "remove_ground: %s must live on a ROCm device (no CPU fallback)" % name)
+        if t.dtype != dt or not t.is_contiguous():
+            raise EpcNetError(-1, "remove_ground: %s must be a contiguous %s tensor, got %s" % (name, dt, t.dtype))
+    if points.dim() != 2 or int(points.shape[1]) != 3 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise EpcNetError(-1, "remove_ground: expected points (total, 3) and offsets (B + 1,), got %s and %s"
+                          % (tuple(points.shape), tuple(offsets.shape)))
+    L.require_gpu()
+    B, rows, H, dev = int(offsets.numel()) - 1, int(points.shape[0]), int(hypotheses), points.device
+    need = int(L.lib().epcnet_ground_workspace_bytes(B, H, rows))
+    if need == 0:
+        raise EpcNetError(-1, "remove_ground: hypotheses must be a multiple of 64 in [64, 1024] and B <= 65535, got %d and %d" % (H, B))
+    if not 0.0 <= float(max_tilt_deg) < 90.0:
+        raise EpcNetError(-1, "remove_ground: max_tilt_deg must be in [0, 90), got %r" % (max_tilt_deg,))
+    cos2 = math.cos(math.radians(float(max_tilt_deg))) ** 2         # in double; the call rounds it once to float32
+    if out is None:
+        out = torch.empty_like(points)
+    elif (not torch.is_tensor(out) or not out.is_cuda or tuple(out.shape) != tuple(points.shape) or out.dtype != torch.float32
+          or not out.is_contiguous()):
+        raise EpcNetError(-1, "remove_ground: `out` must be a contiguous float32 device tensor of points' shape")
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    plane = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    src, dst = points, out
+    if rows == 0:                                                    # (pointers the library can check; no row of them is touched)
+        src = dst = torch.zeros((1, 3), dtype=torch.float32, device=dev)
+    L.run.epcnet_ground_remove(src, offsets, rows, B, H, int(draws), float(threshold), cos2, float(max_z), float(min_share), int(seed),
+                               dst, plane, info, status, ws, ws.numel())
+    return out, status, plane, info
+
+
 def _device_poses(name, poses, device=None):
     """(rows, 2) float64 poses (numpy or torch, host or device) -> a contiguous device tensor.  Any other dtype is refused, not
     converted: float32 has a 0.5 m spacing at UTM northings, and a silent round trip through it would move the relations."""
