@@ -1485,7 +1485,7 @@ class SquaredError(torch.autograd.Function):
 
 
 def morton_sort(xyz):
-    """Z-order every cloud of (B, N, 3) (epc_morton_sort): a pure re-ordering, legal because the whole network is
+    """Order every cloud of (B, N, 3) along the Hilbert curve (epc_morton_sort): a pure re-ordering, legal because the whole network is
     permutation-equivariant and the pooling invariant; it makes the kNN culling and the gathers cache-local."""
     L.require_gpu()
     xyz = xyz.contiguous().float()
