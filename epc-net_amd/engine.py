@@ -236,6 +236,30 @@ class InferenceEngine:
         xyz, status, _ = ops.grid_downsample(kept, offsets, num_points, normalize=normalize)
         return self.forward(xyz, out=out), status | st_ground
 
+    def forward_trajectory(self, points: torch.Tensor, offsets: torch.Tensor, poses: torch.Tensor, along: Optional[torch.Tensor] = None,
+                           num_points: int = 4096, normalize: bool = True, ground=None, submaps: Optional[dict] = None,
+                           out: Optional[torch.Tensor] = None):
+        """Descriptors of POSED scans: ``points`` / ``offsets`` as ``forward_scans`` takes them, in the order the scans were taken,
+        ``poses`` (S, 12) or (S, 3, 4) float64 on the device and, optionally, the travelled distance ``along`` (S,) float64 ->
+        ``(descriptors (max_submaps, FEATURE_OUTPUT_DIM), status (max_submaps,) int32, sub_pose (max_submaps, 12) float64, num_out (2,)
+        int32)``.  Runs ``ops.build_submaps`` (include/epcnet_submaps.h; ``submaps``: a dict of its keyword arguments -- length, spacing,
+        the crop, the capacities) and then exactly what ``forward_scans`` does on the submaps, on the same stream with no host read in
+        between: bit-identical to ``forward_scans(*ops.build_submaps(...)[:2], ...)`` and capturable in a graph.  ``ground`` is
+        ``forward_scans``' argument: the plane is removed per SUBMAP, after the build, which is what the benchmark's preparation did
+        (per scan, before the build, works too: call ``ops.remove_ground`` on the scans first).  ``status`` is the three stages' words ORed
+        together: EPC_STATUS_NO_SUBMAP / EPC_STATUS_NO_ROOM of the build, EPC_STATUS_NO_GROUND, EPC_STATUS_NO_GRID; a slot that is no
+        submap has no rows, hence no grid and a NaN descriptor.  ``num_out[0]`` says how many leading slots are submaps;
+        ``sub_pose[:, [3, 7]]`` are their (x, y)."""
+        from . import ops
+        if submaps is not None and not isinstance(submaps, dict):
+            raise L.EpcNetError(-1, "forward_trajectory: `submaps` is None or a dict of ops.build_submaps' arguments")
+        kw = dict(submaps or {})
+        if "out" in kw or "return_along" in kw:
+            raise L.EpcNetError(-1, "forward_trajectory: `submaps` holds build_submaps' parameters, not its `out` or `return_along`")
+        sub_points, sub_offsets, st_build, sub_pose, _, num_out = ops.build_submaps(points, offsets, poses, along=along, **kw)
+        desc, status = self.forward_scans(sub_points, sub_offsets, num_points=num_points, normalize=normalize, out=out, ground=ground)
+        return desc, status | st_build, sub_pose, num_out
+
     def last_status(self, xyz_or_count) -> "list[int]":
         """Per-cloud EPC_STATUS_* words of the last pass of the most recent ``forward`` call on this engine's own
         workspace (include/epcnet.h: epc_net_last_status; synchronises the stream).  A non-zero word = that cloud's

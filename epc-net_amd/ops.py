@@ -1594,6 +1594,91 @@ def remove_ground(points, offsets, threshold=0.2, max_tilt_deg=15.0, hypotheses=
     return out, status, plane, info
 
 
+def build_submaps(points, offsets, poses, along=None, length=20.0, spacing=10.0, min_range=0.0, max_range=100.0, z_min=float("-inf"),
+                  z_max=float("inf"), max_submaps=None, out_rows=None, out=None, return_along=False):
+    """Posed scans -> travel-length submaps (include/epcnet_submaps.h: epcnet_submap_build; numpy restatement: tests/submap_ref.py):
+    ``(sub_points (out_rows, 3) float32, sub_offsets (max_submaps + 1,) int32, status (max_submaps,) int32, sub_pose (max_submaps, 12)
+    float64, info (max_submaps, 4) int32, num_out (2,) int32)``, all device tensors, on the current stream, no host read, capturable.
+    ``points`` / ``offsets``: the packed scans of ``pack_scans`` in the order they were taken; ``poses``: (S, 12) or (S, 3, 4) FLOAT64
+    device tensor, row-major ``[R | t]`` sensor to world -- any other dtype is refused, never converted (float32 UTM coordinates are
+    0.5 m apart); ``along`` (S,) float64: the travelled distance at each scan, non-decreasing; ``None`` computes the running sum of
+    ``|t_i - t_(i-1)|`` with torch in float64 on the device (outside the header's bit-for-bit contract; ``return_along=True`` appends
+    it to the result).
+
+    Submap k covers the scans whose ``along`` lies in ``[along[0] + k * spacing, along[0] + k * spacing + length)`` and is expressed in
+    the frame of the first scan at or behind its middle (``sub_pose[k]``; ``sub_pose[:, [3, 7]]`` is the (T, 2) array
+    ``Trainer(poses=)``, ``PoseTuples`` and ``retrieval.truth_from_poses`` take).  A row goes (three NaN words, which ``remove_ground``
+    and ``grid_downsample`` treat as absent; nothing is compacted) when its range in the SENSOR frame is below ``min_range``, its x-y
+    distance from the submap's origin is above ``max_range`` (default 100 m: beyond what a spinning automotive sensor returns, so that
+    only non-finite and runaway rows go; must be finite) or its z in the submap's frame is outside ``[z_min, z_max]``.
+    ``sub_points, sub_offsets`` go to ``remove_ground``, ``grid_downsample`` or ``InferenceEngine.forward_scans`` as they are;
+    ground removal also works per scan before this call (its NaN rows pass through as NaN rows).
+
+    ``status``: 0, EPC_STATUS_NO_SUBMAP (the slot lies behind the trajectory's end, or the whole call failed: bad offsets, a
+    non-finite or decreasing ``along``, no scan) or EPC_STATUS_NO_ROOM (more than 2^20 rows, or ``out_rows`` is full: zero rows).
+    ``info``: lo, hi, ref, rows per slot; ``num_out``: the submaps among the slots, and whether the trajectory holds more.  The
+    capacities default to LOOSE upper bounds by design -- ``max_submaps = S`` (at most 65535) and ``out_rows = rows * (ceil(length /
+    spacing) + 1)`` -- because the true numbers are device data; a long trajectory should pass its own."""
+    import ctypes
+    import math
+    for name, t, dt in (("points", points, torch.float32), ("offsets", offsets, torch.int32), ("poses", poses, torch.float64),
+                        ("along", along, torch.float64)):
+        if t is None and name == "along":
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise EpcNetError(-1, "build_submaps: %s must live on a ROCm device (no CPU fallback)" % name)
+        if t.dtype != dt or not t.is_contiguous():
+            raise EpcNetError(-1, "build_submaps: %s must be a contiguous %s tensor, got %s%s" % (
+                name, dt, t.dtype, " (float32 UTM coordinates are 0.5 m apart: poses are never converted)" if dt is torch.float64 else ""))
+    if points.dim() != 2 or int(points.shape[1]) != 3 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise EpcNetError(-1, "build_submaps: expected points (total, 3) and offsets (S + 1,), got %s and %s"
+                          % (tuple(points.shape), tuple(offsets.shape)))
+    S, rows, dev = int(offsets.numel()) - 1, int(points.shape[0]), points.device
+    if tuple(poses.shape) not in ((S, 12), (S, 3, 4)):
+        raise EpcNetError(-1, "build_submaps: poses must be (%d, 12) or (%d, 3, 4) = [R | t] per scan, got %s" % (S, S, tuple(poses.shape)))
+    poses = poses.reshape(S, 12)
+    L.require_gpu()
+    if along is None:
+        t = poses[:, 3::4]
+        along = torch.zeros(S, dtype=torch.float64, device=dev)
+        if S > 1:
+            along[1:] = torch.cumsum((t[1:] - t[:-1]).square().sum(1).sqrt(), 0)
+    elif tuple(along.shape) != (S,):
+        raise EpcNetError(-1, "build_submaps: along must be (%d,), got %s" % (S, tuple(along.shape)))
+    values = [float(v) for v in (length, spacing, min_range, max_range, z_min, z_max)]
+    if not (math.isfinite(values[0]) and values[0] > 0 and math.isfinite(values[1]) and values[1] > 0):
+        raise EpcNetError(-1, "build_submaps: length and spacing must be finite and > 0, got %r and %r" % (length, spacing))
+    if max_submaps is None:
+        max_submaps = min(max(S, 1), 65535)
+    if out_rows is None:
+        out_rows = out.shape[0] if torch.is_tensor(out) else rows * (math.ceil(values[0] / values[1]) + 1)
+    max_submaps, out_rows = int(max_submaps), int(out_rows)
+    need = int(L.lib().epcnet_submap_workspace_bytes(S, max_submaps, rows, out_rows))
+    if need == 0:
+        raise EpcNetError(-1, "build_submaps: need S <= 2^24, 1 <= max_submaps <= 65535 and 0 <= out_rows < 2^31, got %d, %d and %d "
+                              "(pass max_submaps / out_rows for a long trajectory)" % (S, max_submaps, out_rows))
+    if out is None:
+        out = torch.empty((out_rows, 3), dtype=torch.float32, device=dev)
+    elif (not torch.is_tensor(out) or not out.is_cuda or tuple(out.shape) != (out_rows, 3) or out.dtype != torch.float32
+          or not out.is_contiguous()):
+        raise EpcNetError(-1, "build_submaps: `out` must be a contiguous float32 device tensor of shape (%d, 3)" % out_rows)
+    sub_offsets = torch.empty(max_submaps + 1, dtype=torch.int32, device=dev)
+    status = torch.empty(max_submaps, dtype=torch.int32, device=dev)
+    sub_pose = torch.empty((max_submaps, 12), dtype=torch.float64, device=dev)
+    info = torch.empty((max_submaps, 4), dtype=torch.int32, device=dev)
+    num_out = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    params = (ctypes.c_double * L.EPC_SUBMAP_PARAMS)(*values, 0.0, 0.0)  # (lib.run passes ctypes objects on: the header's `const double* params` in host memory)
+    spare = None                                       # (pointers the library can check; nothing of them is touched)
+    if rows == 0 or out_rows == 0 or S == 0:
+        spare = torch.zeros(12, dtype=torch.float64, device=dev)
+    L.run.epcnet_submap_build(points if rows else spare.view(torch.float32), offsets, rows, S, poses if S else spare,
+                              along if S else spare, params, max_submaps, out_rows, out if out_rows else spare.view(torch.float32),
+                              sub_offsets, num_out, sub_pose, info, status, ws, ws.numel())
+    result = (out, sub_offsets, status, sub_pose, info, num_out)
+    return result + (along,) if return_along else result
+
+
 def _device_poses(name, poses, device=None):
     """(rows, 2) float64 poses (numpy or torch, host or device) -> a contiguous device tensor.  Any other dtype is refused, not
     converted: float32 has a 0.5 m spacing at UTM northings, and a silent round trip through it would move the relations."""
