@@ -260,6 +260,32 @@ class InferenceEngine:
         desc, status = self.forward_scans(sub_points, sub_offsets, num_points=num_points, normalize=normalize, out=out, ground=ground)
         return desc, status | st_build, sub_pose, num_out
 
+    def forward_stamped(self, points: torch.Tensor, offsets: torch.Tensor, scan_time: torch.Tensor, pose_time: torch.Tensor,
+                        pose: torch.Tensor, point_dt: Optional[torch.Tensor] = None, max_gap: float = 0.5, num_points: int = 4096,
+                        normalize: bool = True, ground=None, submaps: Optional[dict] = None, out: Optional[torch.Tensor] = None):
+        """Descriptors of TIMESTAMPED scans and odometry on its own clock: ``points`` / ``offsets`` as ``forward_scans`` takes them, in
+        the order the scans were taken, ``scan_time`` (S,) int64 ns, ``pose_time`` (P,) int64 ns with ``pose`` (P, 7) float64 ``tx ty tz
+        qw qx qy qz`` and, for a spinning sensor, ``point_dt`` (total,) int32 ns per row -> ``(descriptors (max_submaps,
+        FEATURE_OUTPUT_DIM), status (max_submaps,) int32, sub_pose (max_submaps, 12) float64, num_out (2,) int32, scan_status (S,)
+        int32)``.  Runs ``ops.deskew_scans`` (include/epcnet_stamps.h), ``ops.travel_along`` on its poses, ``ops.build_submaps`` with that
+        ``along`` and then exactly what ``forward_scans`` does on the submaps, on one stream with no host read in between: bit-identical
+        to those calls made one by one, and capturable in a graph.  ``scan_status`` holds the de-skewer's words per SCAN
+        (EPC_STATUS_NO_POSE, EPC_STATUS_PART_POSE); ``status`` the later stages' per submap, as ``forward_trajectory`` returns them.  A scan
+        without a pose contributes NaN rows only; a submap whose reference scan has no pose ends as a NaN descriptor.  ``submaps`` holds
+        ``build_submaps``' parameters, but not ``along``."""
+        from . import ops
+        if submaps is not None and not isinstance(submaps, dict):
+            raise L.EpcNetError(-1, "forward_stamped: `submaps` is None or a dict of ops.build_submaps' arguments")
+        kw = dict(submaps or {})
+        if "out" in kw or "return_along" in kw or "along" in kw:
+            raise L.EpcNetError(-1, "forward_stamped: `submaps` holds build_submaps' parameters, not its `out`, `along` or `return_along`")
+        moved, scan_pose, scan_status = ops.deskew_scans(points, offsets, scan_time, pose_time, pose, point_dt=point_dt, max_gap=max_gap)
+        along = ops.travel_along(scan_pose, scan_status)
+        sub_points, sub_offsets, st_build, sub_pose, _, num_out = ops.build_submaps(points if moved is None else moved, offsets, scan_pose,
+                                                                                    along=along, **kw)
+        desc, status = self.forward_scans(sub_points, sub_offsets, num_points=num_points, normalize=normalize, out=out, ground=ground)
+        return desc, status | st_build, sub_pose, num_out, scan_status
+
     def last_status(self, xyz_or_count) -> "list[int]":
         """Per-cloud EPC_STATUS_* words of the last pass of the most recent ``forward`` call on this engine's own
         workspace (include/epcnet.h: epc_net_last_status; synchronises the stream).  A non-zero word = that cloud's

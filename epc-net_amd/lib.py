@@ -34,7 +34,7 @@ _POINTEES = {"float*": torch.float32, "double*": torch.float64, "int32_t*": torc
 
 def parse_header(text: str, need_status: bool = True):
     """``(functions, constants, status)`` of the text of include/epcnet.h (or, with ``need_status=False``, of a further header in the
-    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h, include/epcnet_scans.h, include/epcnet_submaps.h): ``functions[name] = (return type, [parameter
+    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h, include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h): ``functions[name] = (return type, [parameter
     types], [parameter names])`` in header order, the types as C type names without ``const`` and spaces around ``*`` -- a key
     of ``_SCALARS``, or any type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME>
     <integer>``; ``status``: the members of ``enum epc_status``.  Raises ValueError on whatever it does not understand."""
@@ -109,6 +109,18 @@ if (set(_submap_functions) & (set(_functions) | set(_pose_functions) | set(_scan
     raise ImportError("epcnet_submaps.h declares a name an earlier header declares")
 _constants.update(_submap_constants)
 SUBMAP_EXPORTS = list(_submap_functions)
+# the fifth header (timestamped scans: odometry interpolated at the stamps, sweeps de-skewed): read, bound and listed like the fourth.
+# Its times are `long long*`, which _POINTEES does not know: ops checks the int64 dtypes itself
+STAMPS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_stamps.h")
+if not os.path.exists(STAMPS_HEADER_PATH):
+    raise ImportError("%s is missing: the binding of the stamp entries is derived from it" % STAMPS_HEADER_PATH)
+with open(STAMPS_HEADER_PATH) as _f:
+    _stamp_functions, _stamp_constants, _ = parse_header(_f.read(), need_status=False)
+if (set(_stamp_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions))
+        or set(_stamp_constants) & set(_constants)):
+    raise ImportError("epcnet_stamps.h declares a name an earlier header declares")
+_constants.update(_stamp_constants)
+STAMP_EXPORTS = list(_stamp_functions)
 globals().update(_constants, **_status)     # EPC_OK, EPC_EINVAL, EPC_KNN_CAP, EPC_PRECISION_FAST, EPC_NUM_STAGES ... as module attributes
 # every symbol include/epcnet.h declares, in its order (tests check the library exports exactly these)
 EXPORTS = list(_functions)
@@ -158,7 +170,7 @@ _lib = ctypes.CDLL(LIB_PATH)
 # a pointer to a structure mirrored above keeps its type check; every other pointer is a void*
 _POINTERS = {"epc_cfg*": POINTER(EpcCfg), "epc_chain_fwd_args*": POINTER(ChainFwdArgs)}
 for _name, (_ret, _params, _) in (list(_functions.items()) + list(_pose_functions.items()) + list(_scan_functions.items())
-                                  + list(_submap_functions.items())):
+                                  + list(_submap_functions.items()) + list(_stamp_functions.items())):
     _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
     _fn.restype = c_char_p if _ret == "char*" else _SCALARS[_ret]
     _fn.argtypes = [_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
@@ -257,8 +269,8 @@ for _name in LAUNCHING:
 for _name, (_ret, _t, _pn) in _pose_functions.items():          # every entry of include/epcnet_poses.h launches
     assert _ret == "int" and (_t[-1], _pn[-1]) == ("void*", "stream"), "%s does not take a stream last and return a status" % _name
     setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))
-for _name, (_ret, _t, _pn) in list(_scan_functions.items()) + list(_submap_functions.items()):
-    # include/epcnet_scans.h and include/epcnet_submaps.h: the entries that take a stream launch
+for _name, (_ret, _t, _pn) in list(_scan_functions.items()) + list(_submap_functions.items()) + list(_stamp_functions.items()):
+    # include/epcnet_scans.h, include/epcnet_submaps.h and include/epcnet_stamps.h: the entries that take a stream launch
     if _t and (_t[-1], _pn[-1]) == ("void*", "stream"):
         assert _ret == "int", "%s takes a stream and does not return a status" % _name
         setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))

@@ -1679,6 +1679,153 @@ def build_submaps(points, offsets, poses, along=None, length=20.0, spacing=10.0,
     return result + (along,) if return_along else result
 
 
+def _stamp_tensor(who, name, t, dtype, shape=None):
+    """The refusals the stamp entries share: a contiguous device tensor of exactly ``dtype`` -- times are never converted."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise EpcNetError(-1, "%s: %s must live on a ROCm device (no CPU fallback)" % (who, name))
+    if t.dtype != dtype or not t.is_contiguous():
+        hint = ""
+        if dtype is torch.int64:
+            hint = " (stamps are integer nanoseconds and are never converted: a float64 second count near 1.7e9 is 2.4e-7 s apart; " \
+                   "convert it yourself, e.g. torch.round(t * 1e9).to(torch.int64), if that is good enough)"
+        elif dtype is torch.int32:
+            hint = " (offsets inside a sweep are integer nanoseconds: convert yourself, e.g. torch.round(dt * 1e9).to(torch.int32))"
+        elif dtype is torch.float64:
+            hint = " (float32 UTM coordinates are 0.5 m apart: poses are never converted)"
+        raise EpcNetError(-1, "%s: %s must be a contiguous %s tensor, got %s%s" % (who, name, dtype, t.dtype, hint))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise EpcNetError(-1, "%s: %s must be %s, got %s" % (who, name, tuple(shape), tuple(t.shape)))
+
+
+def _max_gap_ns(who, max_gap):
+    ns = int(round(float(max_gap) * 1e9))
+    if not 1 <= ns < 2 ** 31:
+        raise EpcNetError(-1, "%s: max_gap must lie in [1e-9, 2.147] seconds, got %r" % (who, max_gap))
+    return ns
+
+
+def _odometry(who, pose_time, pose):
+    _stamp_tensor(who, "pose_time", pose_time, torch.int64)
+    if pose_time.dim() != 1:
+        raise EpcNetError(-1, "%s: pose_time must be (P,), got %s" % (who, tuple(pose_time.shape)))
+    P = int(pose_time.numel())
+    _stamp_tensor(who, "pose", pose, torch.float64, (P, 7))
+    if not 2 <= P <= 2 ** 24:
+        raise EpcNetError(-1, "%s: need 2 <= P <= 2^24 poses, got %d" % (who, P))
+    return P
+
+
+def interpolate_poses(pose_time, pose, query_time, max_gap=0.5):
+    """Odometry at other stamps (include/epcnet_stamps.h: epcnet_pose_interp; numpy restatement: tests/stamps_ref.py): ``(poses (Q, 12)
+    float64, status (Q,) int32)``, device tensors, on the current stream, no host read, capturable.  ``pose_time`` (P,) INT64 nanoseconds,
+    strictly increasing; ``pose`` (P, 7) FLOAT64 ``tx ty tz qw qx qy qz`` sensor to world; ``query_time`` (Q,) int64 nanoseconds.  Float
+    stamps are refused, never converted.  Row i is ``[R | t]`` at ``query_time[i]`` -- what ``build_submaps`` takes --: the translation
+    interpolated linearly, the rotation by normalised linear interpolation on the shorter arc.  Nothing is extrapolated and no bracket
+    longer than ``max_gap`` seconds is interpolated across: such a query gets a NaN pose and EPC_STATUS_NO_POSE (every query does when
+    ``pose_time`` is not strictly increasing)."""
+    who = "interpolate_poses"
+    P = _odometry(who, pose_time, pose)
+    _stamp_tensor(who, "query_time", query_time, torch.int64)
+    if query_time.dim() != 1:
+        raise EpcNetError(-1, "%s: query_time must be (Q,), got %s" % (who, tuple(query_time.shape)))
+    gap = _max_gap_ns(who, max_gap)
+    L.require_gpu()
+    Q, dev = int(query_time.numel()), pose.device
+    if Q > 2 ** 24:
+        raise EpcNetError(-1, "%s: need Q <= 2^24 queries, got %d" % (who, Q))
+    out = torch.empty((Q, 12), dtype=torch.float64, device=dev)
+    status = torch.empty(Q, dtype=torch.int32, device=dev)
+    if Q:
+        L.run.epcnet_pose_interp(pose_time, pose, P, query_time, Q, gap, out, status)
+    return out, status
+
+
+def deskew_scans(points, offsets, scan_time, pose_time, pose, point_dt=None, max_gap=0.5, out=None):
+    """Timestamped scans -> the pose of every scan and, with ``point_dt``, the rows of every sweep moved into the sensor frame of the
+    sweep's own stamp (include/epcnet_stamps.h: epcnet_scan_deskew; numpy restatement: tests/stamps_ref.py): ``(points_out (total, 3)
+    float32 or None, scan_pose (S, 12) float64, status (S,) int32)``, device tensors, on the current stream, no host read, capturable.
+    ``points`` / ``offsets``: the packed scans of ``pack_scans``; ``scan_time`` (S,) INT64 nanoseconds: the instant each scan is
+    expressed in afterwards (typically the sweep's start); ``point_dt`` (total,) INT32 nanoseconds from the scan's time, may be
+    negative; ``None`` (a 2-D line scanner) only interpolates and returns ``None`` for the points; ``pose_time`` (P,) int64, strictly
+    increasing, and ``pose`` (P, 7) FLOAT64 ``tx ty tz qw qx qy qz``: the odometry on its own clock.  Float stamps and float32 poses are
+    refused, never converted.  ``scan_pose`` is what ``build_submaps`` takes as ``poses``, ``travel_along(scan_pose, status)`` its
+    ``along``.
+
+    ``status``: EPC_STATUS_NO_POSE -- the scan's time lies outside the odometry or inside a bracket longer than ``max_gap`` seconds (or
+    the whole call failed: bad offsets, ``pose_time`` not strictly increasing): NaN pose, NaN rows --, EPC_STATUS_PART_POSE: some rows
+    had no pose at their own time and became NaN rows.  Nothing is compacted: ``offsets`` goes on with ``points_out``.  ``out`` must
+    not be ``points``."""
+    who = "deskew_scans"
+    _stamp_tensor(who, "points", points, torch.float32)
+    _stamp_tensor(who, "offsets", offsets, torch.int32)
+    if points.dim() != 2 or int(points.shape[1]) != 3 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise EpcNetError(-1, "%s: expected points (total, 3) and offsets (S + 1,), got %s and %s"
+                          % (who, tuple(points.shape), tuple(offsets.shape)))
+    S, rows, dev = int(offsets.numel()) - 1, int(points.shape[0]), points.device
+    _stamp_tensor(who, "scan_time", scan_time, torch.int64, (S,))
+    P = _odometry(who, pose_time, pose)
+    if point_dt is not None:
+        _stamp_tensor(who, "point_dt", point_dt, torch.int32, (rows,))
+    elif out is not None:
+        raise EpcNetError(-1, "%s: `out` without point_dt: nothing is de-skewed" % who)
+    gap = _max_gap_ns(who, max_gap)
+    L.require_gpu()
+    need = int(L.lib().epcnet_deskew_workspace_bytes(S, P, rows))
+    if need == 0:
+        raise EpcNetError(-1, "%s: need S <= 2^24 scans and fewer than 2^31 rows, got %d and %d" % (who, S, rows))
+    if point_dt is None:
+        pass
+    elif out is None:
+        out = torch.empty_like(points)
+    elif (not torch.is_tensor(out) or not out.is_cuda or tuple(out.shape) != tuple(points.shape) or out.dtype != torch.float32
+          or not out.is_contiguous() or out.data_ptr() == points.data_ptr()):
+        raise EpcNetError(-1, "%s: `out` must be a contiguous float32 device tensor of points' shape, and not points itself" % who)
+    scan_pose = torch.empty((S, 12), dtype=torch.float64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    src, dst, dt, st_ = points, out, point_dt, scan_time
+    if rows == 0:                                                    # (pointers the library can check; no row of them is touched)
+        src = torch.zeros((1, 3), dtype=torch.float32, device=dev)
+        dst = None if point_dt is None else torch.zeros((1, 3), dtype=torch.float32, device=dev)
+        dt = None if point_dt is None else torch.zeros(1, dtype=torch.int32, device=dev)
+    if S == 0:
+        st_ = torch.zeros(1, dtype=torch.int64, device=dev)
+        scan_pose_arg, status_arg = torch.zeros(12, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    else:
+        scan_pose_arg, status_arg = scan_pose, status
+    L.run.epcnet_scan_deskew(src, offsets, rows, S, dt, st_, pose_time, pose, P, gap, dst, scan_pose_arg, status_arg, ws, ws.numel())
+    return out, scan_pose, status
+
+
+def travel_along(poses12, status=None):
+    """The travelled distance at each scan from poses that may have gaps: ``along`` (S,) float64 for ``build_submaps``, built with torch
+    in float64 on the device, no host read, capturable (like ``build_submaps``' own ``along=None`` it lies outside the headers'
+    bit-for-bit contracts).  ``poses12``: (S, 12) or (S, 3, 4) float64 ``[R | t]``; ``status`` (S,) int32 or None.  A scan is VALID when
+    its translation is finite and its status lacks EPC_STATUS_NO_POSE.  The result is the running sum of the steps between consecutive
+    valid scans' translations; an invalid scan takes the value of the last valid scan before it, 0 if there is none.
+    (``build_submaps(along=None)`` turns one NaN pose into a whole-call failure: pass this instead.)"""
+    who = "travel_along"
+    _stamp_tensor(who, "poses12", poses12, torch.float64)
+    S = int(poses12.shape[0]) if poses12.dim() else -1
+    if tuple(poses12.shape) not in ((S, 12), (S, 3, 4)):
+        raise EpcNetError(-1, "%s: poses12 must be (S, 12) or (S, 3, 4), got %s" % (who, tuple(poses12.shape)))
+    t = poses12.reshape(S, 12)[:, 3::4]
+    valid = torch.isfinite(t).all(1)
+    if status is not None:
+        _stamp_tensor(who, "status", status, torch.int32, (S,))
+        valid = valid & ((status & L.EPC_STATUS_NO_POSE) == 0)
+    along = torch.zeros(S, dtype=torch.float64, device=poses12.device)
+    if S > 1:
+        index = torch.arange(S, device=poses12.device)
+        last = torch.cummax(torch.where(valid, index, torch.full_like(index, -1)), 0).values      # the last valid scan at or before i
+        prev = last[:-1]                                                 # ... strictly before scan i, for i = 1 .. S - 1
+        safe = torch.where(valid[:, None], t, torch.zeros_like(t))
+        step = (safe[1:] - safe[prev.clamp(min=0)]).square().sum(1).sqrt()
+        step = torch.where(valid[1:] & (prev >= 0), step, torch.zeros_like(step))
+        along[1:] = torch.cumsum(step, 0)
+    return along
+
+
 def _device_poses(name, poses, device=None):
     """(rows, 2) float64 poses (numpy or torch, host or device) -> a contiguous device tensor.  Any other dtype is refused, not
     converted: float32 has a 0.5 m spacing at UTM northings, and a silent round trip through it would move the relations."""
