@@ -28,15 +28,17 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "epcnet.h")
 
 _SCALARS = {"int": c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "float": c_float,
             "size_t": ctypes.c_size_t, "int32_t": c_int32, "uint32_t": ctypes.c_uint32}
+# what include/epcnet_revisits.h passes by value besides: the reader of every other header goes on refusing a `double` parameter
+_REVISIT_SCALARS = dict(_SCALARS, double=ctypes.c_double)
 # the dtype a tensor must have where the header declares a typed pointee (``run``); any dtype goes at every other pointer
 _POINTEES = {"float*": torch.float32, "double*": torch.float64, "int32_t*": torch.int32, "int*": torch.int32, "long*": torch.int64}
 
 
-def parse_header(text: str, need_status: bool = True):
+def parse_header(text: str, need_status: bool = True, scalars=_SCALARS):
     """``(functions, constants, status)`` of the text of include/epcnet.h (or, with ``need_status=False``, of a further header in the
-    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h, include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h): ``functions[name] = (return type, [parameter
+    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h, include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h): ``functions[name] = (return type, [parameter
     types], [parameter names])`` in header order, the types as C type names without ``const`` and spaces around ``*`` -- a key
-    of ``_SCALARS``, or any type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME>
+    of ``scalars``, or any type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME>
     <integer>``; ``status``: the members of ``enum epc_status``.  Raises ValueError on whatever it does not understand."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)         # extern "C" { and its }
@@ -59,11 +61,11 @@ def parse_header(text: str, need_status: bool = True):
         if not m or m.group(2) in functions:
             raise ValueError("epcnet.h: not a declaration, or a second one of its name: %r" % " ".join(decl.split()))
         ret, name, params, names = ctype(m.group(1)), m.group(2), [], []
-        if ret not in _SCALARS and ret != "char*":
+        if ret not in scalars and ret != "char*":
             raise ValueError("epcnet.h: %s: unknown return type %r" % (name, ret))
         for p in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
             pm = re.fullmatch(r"\s*(.*[\s*])(\w+)\s*", p, flags=re.S)              # the type, then the parameter's name
-            if not pm or (ctype(pm.group(1)) not in _SCALARS and "*" not in pm.group(1)):
+            if not pm or (ctype(pm.group(1)) not in scalars and "*" not in pm.group(1)):
                 raise ValueError("epcnet.h: %s: unknown parameter type in %r" % (name, " ".join(p.split())))
             params.append(ctype(pm.group(1)))
             names.append(pm.group(2))
@@ -121,6 +123,18 @@ if (set(_stamp_functions) & (set(_functions) | set(_pose_functions) | set(_scan_
     raise ImportError("epcnet_stamps.h declares a name an earlier header declares")
 _constants.update(_stamp_constants)
 STAMP_EXPORTS = list(_stamp_functions)
+# the sixth header (revisit search: the k nearest descriptors among the rows at least min_travel behind each query): read, bound and listed
+# like the fifth.  Its `along` values are `double*` (a float64 tensor, _POINTEES) and min_travel is a `double` by value
+REVISITS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_revisits.h")
+if not os.path.exists(REVISITS_HEADER_PATH):
+    raise ImportError("%s is missing: the binding of the revisit entries is derived from it" % REVISITS_HEADER_PATH)
+with open(REVISITS_HEADER_PATH) as _f:
+    _revisit_functions, _revisit_constants, _ = parse_header(_f.read(), need_status=False, scalars=_REVISIT_SCALARS)
+if (set(_revisit_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions) | set(_stamp_functions))
+        or set(_revisit_constants) & set(_constants)):
+    raise ImportError("epcnet_revisits.h declares a name an earlier header declares")
+_constants.update(_revisit_constants)
+REVISIT_EXPORTS = list(_revisit_functions)
 globals().update(_constants, **_status)     # EPC_OK, EPC_EINVAL, EPC_KNN_CAP, EPC_PRECISION_FAST, EPC_NUM_STAGES ... as module attributes
 # every symbol include/epcnet.h declares, in its order (tests check the library exports exactly these)
 EXPORTS = list(_functions)
@@ -170,10 +184,10 @@ _lib = ctypes.CDLL(LIB_PATH)
 # a pointer to a structure mirrored above keeps its type check; every other pointer is a void*
 _POINTERS = {"epc_cfg*": POINTER(EpcCfg), "epc_chain_fwd_args*": POINTER(ChainFwdArgs)}
 for _name, (_ret, _params, _) in (list(_functions.items()) + list(_pose_functions.items()) + list(_scan_functions.items())
-                                  + list(_submap_functions.items()) + list(_stamp_functions.items())):
+                                  + list(_submap_functions.items()) + list(_stamp_functions.items()) + list(_revisit_functions.items())):
     _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
-    _fn.restype = c_char_p if _ret == "char*" else _SCALARS[_ret]
-    _fn.argtypes = [_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
+    _fn.restype = c_char_p if _ret == "char*" else _REVISIT_SCALARS[_ret]
+    _fn.argtypes = [_REVISIT_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
 
 
 def lib() -> ctypes.CDLL:
@@ -226,7 +240,7 @@ def _converter(where: str, ctype: str):
                 raise EpcNetError(-1, "%s: the header declares %s there, the tensor is %s" % (where, dtype, a.dtype))
             return a.data_ptr()
         return pointer
-    cast = float if ctype == "float" else int
+    cast = float if ctype in ("float", "double") else int
 
     def scalar(a):
         if type(a) is cast:
@@ -269,8 +283,10 @@ for _name in LAUNCHING:
 for _name, (_ret, _t, _pn) in _pose_functions.items():          # every entry of include/epcnet_poses.h launches
     assert _ret == "int" and (_t[-1], _pn[-1]) == ("void*", "stream"), "%s does not take a stream last and return a status" % _name
     setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))
-for _name, (_ret, _t, _pn) in list(_scan_functions.items()) + list(_submap_functions.items()) + list(_stamp_functions.items()):
-    # include/epcnet_scans.h, include/epcnet_submaps.h and include/epcnet_stamps.h: the entries that take a stream launch
+for _name, (_ret, _t, _pn) in (list(_scan_functions.items()) + list(_submap_functions.items()) + list(_stamp_functions.items())
+                               + list(_revisit_functions.items())):
+    # include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h and include/epcnet_revisits.h: the entries that take a
+    # stream launch
     if _t and (_t[-1], _pn[-1]) == ("void*", "stream"):
         assert _ret == "int", "%s takes a stream and does not return a status" % _name
         setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))

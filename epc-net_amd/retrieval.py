@@ -4,6 +4,8 @@
                        in inference every cloud's descriptor is independent, so batching changes nothing but speed)
   latent_vectors_bank  train.py:871-965     the same from the records of a cloud bank, by record id (epc_net_forward_bank)
   knn_search           evaluate.py:463,481  sklearn KDTree(database).query(q, k=25) -> epc_pairwise_topk on the GPU
+  revisit_search       (no counterpart)     the same exact search along ONE trajectory: per query only the rows at least min_travel behind
+                       it (epcnet_revisit_search); RevisitIndex is its streaming form
   mine_topk            train.py:857-869     the hard-negative KDTree query over rows named by id (epc_mine_topk)
   get_recall           evaluate.py:455-537  recall@1..25, top-1 % recall, top-1 similarity for one (m, n) run pair
   evaluate_runs        evaluate.py:293-332  average over all ordered pairs m != n
@@ -112,6 +114,115 @@ def knn_search(database: torch.Tensor, queries: torch.Tensor, k: int = NUM_NEIGH
     else:
         L.run.epc_pairwise_topk(L.ptr(database), d, L.ptr(queries), q, dim, k, L.ptr(idx), L.ptr(dist))
     return dist, idx
+
+
+def _revisit_check(name: str, t, dtype, ndim: int, device=None):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.dim() != ndim \
+            or (device is not None and t.device != device):
+        raise L.EpcNetError(-1, "revisit_search: %s must be a contiguous %d-d %s tensor on the ROCm device%s" % (
+            name, ndim, dtype, " (travelled distance is float64 like the poses: it is refused, never converted)"
+            if dtype == torch.float64 else ""))
+
+
+def revisit_search(descriptors: torch.Tensor, along: torch.Tensor, min_travel: float, k: int = 5, *,
+                   queries: Optional[torch.Tensor] = None, q_along: Optional[torch.Tensor] = None, pass_queries: int = 0,
+                   workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Loop-closure candidates along a trajectory (include/epcnet_revisits.h): for every query the exact ``k`` nearest rows of
+    ``descriptors`` (T, D) float32 among those at least ``min_travel`` BEHIND it -- the rows j with ``along[j] <= q_along[i] -
+    min_travel`` in float64; ``along`` (T,) float64, non-decreasing (metres from ``ops.travel_along`` or ``k * spacing``, or seconds).
+    ``queries`` (Q, D) / ``q_along`` (Q,), both or neither: None searches the trajectory against itself, which is causal for
+    ``min_travel > 0`` -- every revisit pair is reported once, by its later member.  Returns (dist (Q, k) float32, idx (Q, k) int32,
+    count (Q,) int32): row i is bit for bit ``knn_search(descriptors[:count[i]], queries[i:i + 1], min(k, count[i]))``, padded with
+    (+inf, -1); ``count[i] == -1`` (and an all-padding row) for a non-finite ``q_along[i]`` or, in EVERY row, when ``along`` holds a
+    non-finite entry or decreases -- decided on the device, nothing is read back, the call is asynchronous and capturable in a graph.
+    ``pass_queries`` (0 or a multiple of 128): queries per pass of the distance matrix; ``workspace``: a uint8 device tensor of at least
+    ``epcnet_revisit_workspace_bytes`` bytes to reuse (what a captured graph needs), else one is allocated."""
+    L.require_gpu()
+    _revisit_check("descriptors", descriptors, torch.float32, 2)
+    dev = descriptors.device
+    _revisit_check("along", along, torch.float64, 1, dev)
+    if (queries is None) != (q_along is None):
+        raise L.EpcNetError(-1, "revisit_search: queries and q_along come together or not at all")
+    if queries is None:
+        queries, q_along = descriptors, along
+    _revisit_check("queries", queries, torch.float32, 2, dev)
+    _revisit_check("q_along", q_along, torch.float64, 1, dev)
+    d, q, dim, k = int(descriptors.shape[0]), int(queries.shape[0]), int(descriptors.shape[1]), int(k)
+    if int(queries.shape[1]) != dim or along.numel() != d or q_along.numel() != q:
+        raise L.EpcNetError(-1, "revisit_search: expected descriptors (T, D), along (T,), queries (Q, D), q_along (Q,)")
+    need = int(L.lib().epcnet_revisit_workspace_bytes(d, q, int(pass_queries)))
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(ws) or not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise L.EpcNetError(-1, "revisit_search: workspace must be a contiguous uint8 tensor on the ROCm device")
+    idx = torch.empty((q, max(k, 0)), dtype=torch.int32, device=dev)
+    dist = torch.empty((q, max(k, 0)), dtype=torch.float32, device=dev)
+    count = torch.empty((q,), dtype=torch.int32, device=dev)
+    def arg(t):          # an empty tensor has no address: the workspace's (aligned, not null) stands in and is never followed
+        return t if t.numel() else ws.data_ptr()
+    L.run.epcnet_revisit_search(arg(descriptors), arg(along), d, arg(queries), arg(q_along), q, dim, float(min_travel), k,
+                                int(pass_queries), arg(idx), arg(dist), arg(count), ws, ws.numel())
+    if workspace is None:
+        ws.record_stream(torch.cuda.current_stream(dev))
+    return dist, idx, count
+
+
+class RevisitIndex:
+    """The streaming form of ``revisit_search`` for a robot that adds a submap at a time: ``capacity`` rows of ``dim`` floats and their
+    travelled distances, allocated once on the device.  ``add(descriptors, along)`` copies the new rows behind the stored ones and
+    searches THEM against everything stored, themselves included -- the prefix rule does the exclusion --, so piecewise adds over a
+    trajectory return, concatenated, the bits of the one batch call.  A failed add (``count == -1``: the stored ``along`` decreases or
+    holds a non-finite entry) has stored its rows regardless: the caller who checks ``count`` drops them with ``truncate``."""
+
+    def __init__(self, capacity: int, dim: int = 256, min_travel: float = 100.0, k: int = 5, device=None):
+        L.require_gpu()
+        self.capacity, self.dim, self.min_travel, self.k = int(capacity), int(dim), float(min_travel), int(k)
+        if self.capacity < 0 or self.capacity > (1 << 22) or self.dim <= 0 or self.dim % 8 or not 0 < self.k <= 56 \
+                or not (self.min_travel >= 0.0 and self.min_travel != float("inf")):
+            raise L.EpcNetError(-1, "RevisitIndex: need 0 <= capacity <= 2^22, dim a positive multiple of 8, 0 < k <= 56 and a finite "
+                                    "min_travel >= 0")
+        self._desc = torch.empty((self.capacity, self.dim), dtype=torch.float32,
+                                 device=torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device()))
+        self.device = self._desc.device                      # with its index, as every tensor on it reports it
+        self._along = torch.empty((self.capacity,), dtype=torch.float64, device=self.device)
+        self._n = 0
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def descriptors(self) -> torch.Tensor:
+        """The stored rows (len, dim): a view of the index's buffer, to be read only."""
+        return self._desc[:self._n]
+
+    @property
+    def along(self) -> torch.Tensor:
+        """The stored travelled distances (len,): a view of the index's buffer, to be read only."""
+        return self._along[:self._n]
+
+    def truncate(self, n: int) -> None:
+        """Keep the first ``n`` rows (what drops the rows of a failed ``add``)."""
+        n = int(n)
+        if n < 0 or n > self._n:
+            raise L.EpcNetError(-1, "RevisitIndex.truncate: %d is outside [0, %d]" % (n, self._n))
+        self._n = n
+
+    def add(self, descriptors: torch.Tensor, along: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """New rows (m, dim) float32 with their ``along`` (m,) float64 -> (dist, idx, count) of ``revisit_search`` for them."""
+        _revisit_check("descriptors", descriptors, torch.float32, 2, self.device)
+        _revisit_check("along", along, torch.float64, 1, self.device)
+        m = int(descriptors.shape[0])
+        if int(descriptors.shape[1]) != self.dim or along.numel() != m:
+            raise L.EpcNetError(-1, "RevisitIndex.add: expected descriptors (m, %d) and along (m,)" % self.dim)
+        if self._n + m > self.capacity:
+            raise L.EpcNetError(-1, "RevisitIndex.add: %d rows on top of %d exceed the capacity %d (the index never reallocates)"
+                                % (m, self._n, self.capacity))
+        a, b = self._n, self._n + m
+        self._desc[a:b].copy_(descriptors)
+        self._along[a:b].copy_(along)
+        self._n = b
+        return revisit_search(self._desc[:b], self._along[:b], self.min_travel, self.k, queries=self._desc[a:b], q_along=self._along[a:b])
 
 
 def recall_from_indices(indices: np.ndarray, database_output: np.ndarray, queries_output: np.ndarray,
