@@ -211,6 +211,22 @@ int epc_sort_launch(const float* xyz, int num_clouds, int n, float* xyz_sorted, 
         }                                                                         \
     } while (0)
 
+// ---- host helpers that serve every launcher of the library ------------------------------------------------
+static inline bool epc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Opt a kernel in to `bytes` of dynamic LDS (more than the default 64 KB needs it).  A launcher that is not itself the entry point
+// passes the entry point's name on; EPC_SET_DYN_LDS is the form for an entry point's own body.
+static inline int epc_set_dyn_lds(const void* kernel, size_t bytes, const char* who) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) return EPC_OK;
+    epc_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+    return EPC_EHIP;
+}
+#define EPC_SET_DYN_LDS(kernel, bytes)                                                                  \
+    do {                                                                                                \
+        if (epc_set_dyn_lds(reinterpret_cast<const void*>(kernel), bytes, __func__) != EPC_OK) return EPC_EHIP; \
+    } while (0)
+
 // ---- packed inference-weight layout (floats) --------------------------------------------------------------
 // A "layer pack" for a Cin->Cout 1x1 conv consumed by mfma32 in the transposed orientation
 //   out^T[ch][pt] = sum_k Wf[k][ch] * in[pt][k]

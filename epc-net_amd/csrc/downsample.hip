@@ -17,7 +17,7 @@
 // [4T, 4T + 20N) kept keys, kept counts, three sums.  N = 4096: 144 KB of the CU's 160 KB.
 // Integer LDS atomics only: order-independent, hence deterministic.  Every float operation of the quantisation and of the output is
 // rounded once (contract off; the division is hipcc's default correctly rounded one).
-#include "train_common.h"
+#include "scan_common.h"
 
 #define GD_THREADS 1024
 #define GD_WAVES (GD_THREADS / 64)
@@ -49,7 +49,7 @@ struct gd_scratch {            // static LDS: block reductions, the probes' dist
 // the point's three coordinates as dwords (rows are 12 bytes and a cloud may start at any row: no 16-byte alignment)
 __device__ __forceinline__ bool gd_load(const float* __restrict__ pc, int j, float& x, float& y, float& z) {
     x = pc[3 * j], y = pc[3 * j + 1], z = pc[3 * j + 2];
-    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
+    return epc_finite3(x, y, z);
 }
 
 // u = min((int)(((p - lo) * s) * 4096), R * 4096 - 1) per axis, each operation rounded once
@@ -112,29 +112,6 @@ __device__ __forceinline__ int gd_block_max(int v, int* slot) {
     for (int w = 1; w < GD_WAVES; ++w) t = max(t, slot[w]);
     return t;
 }
-// exclusive prefix of v in thread order; total = the block's sum
-__device__ __forceinline__ int gd_block_scan(int v, int* slot, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    __syncthreads();
-    if (lane == 63) slot[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < GD_WAVES; ++w) {
-        const int t = slot[w];
-        base += w < wave ? t : 0;
-        total += t;
-    }
-    return base + incl - v;
-}
-
 // D(R) >= limit?  Key-only table; the pass stops once `limit` distinct keys are in.  With counts != nullptr every point also adds
 // one to its key's count (the pass at R*).  Returns the number of distinct keys seen, exact when below `limit`.
 __device__ __forceinline__ int gd_probe(const float* __restrict__ pc, int M, float lox, float loy, float loz, float e, int R, int limit,
@@ -260,7 +237,7 @@ __global__ __launch_bounds__(GD_THREADS) void grid_downsample_kernel(const float
                 }
             }
             int total;
-            int at = gd_block_scan(mine, sc.i, total);   // (its barriers: every slot has been read before any pair is written)
+            int at = block_scan<GD_WAVES>(mine, sc.i, total);   // (its barriers: every slot has been read before any pair is written)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if (k[r] != GD_EMPTY) pairs[at++] = ((unsigned long long)k[r] << 32) | c[r];
@@ -308,7 +285,7 @@ __global__ __launch_bounds__(GD_THREADS) void grid_downsample_kernel(const float
         for (int r = 0; r < 8; ++r) above += cnt[r] > cstar ? 1 : 0, equal += cnt[r] == cstar ? 1 : 0;
         const int ties_kept = N - gd_block_sum(above, sc.i);
         int unused;
-        int tie_rank = gd_block_scan(equal, sc.i, unused);
+        int tie_rank = block_scan<GD_WAVES>(equal, sc.i, unused);
         int kept = 0;
         unsigned keep_mask = 0u;
 #pragma unroll
@@ -318,7 +295,7 @@ __global__ __launch_bounds__(GD_THREADS) void grid_downsample_kernel(const float
             keep_mask |= k ? 1u << r : 0u;
             kept += k ? 1 : 0;
         }
-        int at = gd_block_scan(kept, sc.i, unused);
+        int at = block_scan<GD_WAVES>(kept, sc.i, unused);
         unsigned* kkey = tab + T;              // the N kept keys in ascending order, their counts, the three sums
         unsigned* kcnt = kkey + N;
         unsigned* ksum = kcnt + N;
@@ -428,7 +405,7 @@ __global__ __launch_bounds__(GD_THREADS) void grid_downsample_kernel(const float
             }
         }
     } else {
-        const float nan = __int_as_float(0x7fc00000);
+        const float nan = epc_nan_f32();
         for (int i = tid; i < 3 * N; i += GD_THREADS) out[i] = nan;
     }
 
@@ -455,11 +432,7 @@ extern "C" int epc_grid_downsample(const float* points, const int32_t* offsets, 
     EPC_CHECK_ARG(num_clouds >= 0, "num_clouds must not be negative");
     EPC_CHECK_ARG(n >= GD_MIN_N && n <= GD_MAX_N && n % 32 == 0, "n must be a multiple of 32 in [32, 4096]");
     EPC_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, "workspace must be 4-byte aligned");
-    if (workspace_bytes < epc_grid_downsample_workspace_bytes(num_clouds, n)) {
-        epc_set_error("epc_grid_downsample: workspace of %zu bytes, %zu needed", workspace_bytes,
-                      epc_grid_downsample_workspace_bytes(num_clouds, n));
-        return EPC_ENOMEM;
-    }
+    EPC_CHECK_WORKSPACE_BYTES(workspace_bytes, epc_grid_downsample_workspace_bytes(num_clouds, n));
     if (num_clouds == 0) return EPC_OK;
     const size_t lds_bytes = gd_lds_bytes(n);
     if (int rc = epc_set_dyn_lds(reinterpret_cast<const void*>(grid_downsample_kernel), lds_bytes, "epc_grid_downsample")) return rc;

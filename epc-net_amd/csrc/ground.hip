@@ -16,7 +16,7 @@
 //   ground_select_kernel   one workgroup per scan: arg-max (ties: smaller h), acceptance, plane / info / status, the chosen plane
 //   ground_mark_kernel     flat tiles again: e for the chosen plane, NaN rows out; in place safe (the vertices were read in launch 1)
 // Integer atomics only: order-independent, hence deterministic.
-#include "train_common.h"
+#include "scan_common.h"
 #include "../../include/epcnet_scans.h"
 
 #define GR_THREADS 256
@@ -28,15 +28,6 @@
 #define GR_MAX_H 1024
 #define GR_META 4              // per scan: begin, M, ok, offsets valid
 #define GR_CHOSEN 8            // per scan: n_x n_y n_z d0 thr (float bits), accepted, 2 spare
-
-__host__ __device__ __forceinline__ uint32_t gr_mix(uint32_t x) {      // mix of include/epcnet_poses.h
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
 
 // the workspace, in 4-byte words: meta | finite | chosen | scores | planes (per scan 5 arrays of H: n_x n_y n_z d0 thr)
 struct gr_ws {
@@ -60,9 +51,6 @@ __host__ __device__ __forceinline__ size_t gr_ws_words(int B, int H) {
     return (size_t)(B > 0 ? B : 1) * (GR_META + 4 + GR_CHOSEN + 6 * (size_t)H);
 }
 
-__device__ __forceinline__ bool gr_finite3(float x, float y, float z) {
-    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
 __device__ __forceinline__ float gr_dot(float nx, float ny, float nz, float x, float y, float z) {
 #pragma clang fp contract(off)
     return (nx * x + ny * y) + nz * z;
@@ -78,29 +66,16 @@ __device__ __forceinline__ int gr_inlier(float nx, float ny, float nz, float d0,
     return e * e <= thr ? 1 : 0;
 }
 
-// the first scan whose end lies behind row r (B when there is none); the offsets are non-decreasing here
-__device__ __forceinline__ int gr_first_scan(const int32_t* __restrict__ offsets, int B, int r) {
-    int lo = 0, hi = B;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid + 1] > r)
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    return lo;
-}
-
 // ---- launch 1: offsets, vertices, planes, zeroed counters ---------------------------------------------------------------------------
 __global__ __launch_bounds__(GR_THREADS) void ground_build_kernel(const float* __restrict__ points, const int32_t* __restrict__ offsets,
                                                                   int num_rows, int B, int H, int K, float t, float cos2_tilt, float max_z,
                                                                   uint32_t seed_lo, uint32_t seed_hi, gr_ws ws) {
     __shared__ int bad;
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (tid == 0) bad = (offsets[0] < 0 || offsets[B] > num_rows) ? 1 : 0;
+    if (tid == 0) bad = 0;
     __syncthreads();
     int mine = 0;
-    for (int i = tid; i < B; i += GR_THREADS) mine |= offsets[i] > offsets[i + 1] ? 1 : 0;
+    for (int i = tid; i < B; i += GR_THREADS) mine |= offsets_rule_bad(offsets, B, num_rows, i) ? 1 : 0;      // (B >= 1: index 0 is visited)
     if (mine) atomicOr(&bad, 1);
     __syncthreads();
     const bool valid = bad == 0;
@@ -116,20 +91,20 @@ __global__ __launch_bounds__(GR_THREADS) void ground_build_kernel(const float* _
         ws.finite[b] = 0;
     }
     const float* pc = points + (size_t)begin * 3;
-    uint32_t s = gr_mix(seed_lo);
-    s = gr_mix(s ^ seed_hi);
+    uint32_t s = epc_mix32(seed_lo);
+    s = epc_mix32(s ^ seed_hi);
     for (int h = tid; h < H; h += GR_THREADS) {
 #pragma clang fp contract(off)
-        const uint32_t sh = gr_mix(s ^ (uint32_t)h);
+        const uint32_t sh = epc_mix32(s ^ (uint32_t)h);
         float p[3][3];
         bool vertices = M > 0;
         for (int j = 0; j < 3 && vertices; ++j) {
             bool have = false;
             float bx = 0.f, by = 0.f, bz = 0.f;
             for (int k = 0; k < K; ++k) {
-                const uint32_t r = (uint32_t)(((unsigned long long)gr_mix(sh ^ (uint32_t)(K * j + k)) * (unsigned long long)M) >> 32);
+                const uint32_t r = (uint32_t)(((unsigned long long)epc_mix32(sh ^ (uint32_t)(K * j + k)) * (unsigned long long)M) >> 32);
                 const float x = pc[3 * (size_t)r], y = pc[3 * (size_t)r + 1], z = pc[3 * (size_t)r + 2];
-                if (gr_finite3(x, y, z) && (!have || z < bz)) have = true, bx = x, by = y, bz = z;
+                if (epc_finite3(x, y, z) && (!have || z < bz)) have = true, bx = x, by = y, bz = z;
             }
             p[j][0] = bx, p[j][1] = by, p[j][2] = bz;
             vertices = have;
@@ -167,13 +142,13 @@ __global__ __launch_bounds__(GS_THREADS) void ground_score_kernel(const float* _
     const long long t0l = (long long)blockIdx.x * GR_TILE;
     const int t0 = (int)t0l;
     const int t1 = (int)(t0l + GR_TILE < (long long)num_rows ? t0l + GR_TILE : (long long)num_rows);
-    const float nan = __int_as_float(0x7fc00000);
+    const float nan = epc_nan_f32();
     for (int i = tid; i < GR_TILE; i += GS_THREADS) {
         float x = nan, y = nan, z = nan;
         if (t0 + i < t1) {
             const float* p = points + (size_t)(t0 + i) * 3;
             x = p[0], y = p[1], z = p[2];
-            if (!gr_finite3(x, y, z)) x = y = z = nan;
+            if (!epc_finite3(x, y, z)) x = y = z = nan;
         }
         lx[i] = x, ly[i] = y, lz[i] = z;
     }
@@ -182,7 +157,7 @@ __global__ __launch_bounds__(GS_THREADS) void ground_score_kernel(const float* _
     __syncthreads();
 
     const int groups = H >> 6;
-    for (int b = gr_first_scan(offsets, B, t0); b < B; ++b) {
+    for (int b = first_scan_behind(offsets, 0, B, t0); b < B; ++b) {
         const int begin = offsets[b], end = offsets[b + 1];
         if (begin >= t1) break;
         if (ws.meta[b * GR_META + 2] == 0) continue;   // a scan of more than 2^20 rows: failed alone
@@ -281,7 +256,7 @@ __global__ __launch_bounds__(GR_THREADS) void ground_select_kernel(int H, float 
 #pragma clang fp contract(off)
         accepted = score >= 3 && (float)score >= min_share * (float)finite;
     }
-    const float nan = __int_as_float(0x7fc00000);
+    const float nan = epc_nan_f32();
     float w[5] = {nan, nan, nan, nan, -1.0f};
     if (accepted)
 #pragma unroll
@@ -319,9 +294,9 @@ __global__ __launch_bounds__(GR_THREADS) void ground_mark_kernel(const float* po
         gr_copy_rows(points, out, t0, t1);
         return;
     }
-    const float nan = __int_as_float(0x7fc00000);
+    const float nan = epc_nan_f32();
     int cur = t0;
-    for (int b = gr_first_scan(offsets, B, t0); b < B; ++b) {
+    for (int b = first_scan_behind(offsets, 0, B, t0); b < B; ++b) {
         const int begin = offsets[b], end = offsets[b + 1];
         if (begin >= t1) break;
         const int r0 = begin > cur ? begin : cur, r1 = end < t1 ? end : t1;
@@ -338,7 +313,7 @@ __global__ __launch_bounds__(GR_THREADS) void ground_mark_kernel(const float* po
                 const size_t o = (size_t)r * 3;
                 const float x = points[o], y = points[o + 1], z = points[o + 2];
                 const float e = gr_e(nx, ny, nz, d0, x, y, z);
-                const bool gone = gr_finite3(x, y, z) && (e < 0.f || e * e <= thr);
+                const bool gone = epc_finite3(x, y, z) && (e < 0.f || e * e <= thr);
                 if (gone)
                     out[o] = nan, out[o + 1] = nan, out[o + 2] = nan;
                 else if (out != points)
@@ -372,12 +347,7 @@ extern "C" int epcnet_ground_remove(const float* points, const int32_t* offsets,
     EPC_CHECK_ARG(cos2_tilt > 0.f && cos2_tilt <= 1.f, "cos2_tilt must be in (0, 1]");
     EPC_CHECK_ARG(max_z == max_z, "max_z must not be NaN (+Inf: no limit)");
     EPC_CHECK_ARG(min_share >= 0.f && min_share <= 1.f, "min_share must be in [0, 1]");
-    EPC_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
-    const size_t need = epcnet_ground_workspace_bytes(num_clouds, hypotheses, num_rows);
-    if (workspace_bytes < need) {
-        epc_set_error("epcnet_ground_remove: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-        return EPC_ENOMEM;
-    }
+    EPC_CHECK_WORKSPACE(workspace, workspace_bytes, epcnet_ground_workspace_bytes(num_clouds, hypotheses, num_rows));
     hipStream_t st = (hipStream_t)stream;
     if (num_clouds == 0) {                             // no scan: every row lies inside none
         if (points_out != points && num_rows > 0 &&

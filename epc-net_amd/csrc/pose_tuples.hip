@@ -13,7 +13,7 @@
 // in; it ends as soon as the values up to and including that bin are exactly k (at Oxford size: 2 passes, rarely 3).  The values are
 // recomputed per pass (a subtraction pair, two products, five integer multiplies), never stored.
 // float64 throughout, every operation rounded once (contract off), so numpy decides every relation alike.
-#include "train_common.h"
+#include "scan_common.h"
 #include "../../include/epcnet_poses.h"
 
 #define PT_THREADS 1024
@@ -25,28 +25,20 @@
 #define PR_WAVES (PR_THREADS / 64)
 #define PT_NONE (~0ull)
 
-__host__ __device__ __forceinline__ uint32_t pt_mix(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
 struct pt_seed {
     uint32_t seed_lo, seed_hi, step_lo, step_hi;
 };
-// the state in front of the record id: hash(c) = pt_mix(state ^ c)
+// the state in front of the record id: hash(c) = epc_mix32(state ^ c)
 __device__ __forceinline__ uint32_t pt_state(const pt_seed& sd, uint32_t key, uint32_t stream) {
-    uint32_t s = pt_mix(sd.seed_lo);
-    s = pt_mix(s ^ sd.seed_hi);
-    s = pt_mix(s ^ sd.step_lo);
-    s = pt_mix(s ^ sd.step_hi);
-    s = pt_mix(s ^ key);
-    return pt_mix(s ^ stream);
+    uint32_t s = epc_mix32(sd.seed_lo);
+    s = epc_mix32(s ^ sd.seed_hi);
+    s = epc_mix32(s ^ sd.step_lo);
+    s = epc_mix32(s ^ sd.step_hi);
+    s = epc_mix32(s ^ key);
+    return epc_mix32(s ^ stream);
 }
 __device__ __forceinline__ unsigned long long pt_value(uint32_t state, int c) {
-    return ((unsigned long long)pt_mix(state ^ (uint32_t)c) << 32) | (unsigned long long)(uint32_t)c;
+    return ((unsigned long long)epc_mix32(state ^ (uint32_t)c) << 32) | (unsigned long long)(uint32_t)c;
 }
 __device__ __forceinline__ double pt_d2(const double2& a, const double2& b) {
 #pragma clang fp contract(off)
@@ -155,29 +147,6 @@ struct pt_shared {
     double2 negpose[EPC_TUPLE_MAX_IDS];
 };
 
-// exclusive prefix of v in thread order; total = the block's sum
-__device__ __forceinline__ int pt_block_scan(int v, int* slot, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    __syncthreads();           // the previous scan's readers are done with `slot`
-    if (lane == 63) slot[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < PT_WAVES; ++w) {
-        const int t = slot[w];
-        base += w < wave ? t : 0;
-        total += t;
-    }
-    return base + incl - v;
-}
-
 // the positives of the key (c != key, within r_pos) / its negatives (strictly outside r_neg), with their values of one stream
 struct pt_positive {
     const double2* poses;
@@ -220,7 +189,7 @@ __device__ __forceinline__ unsigned long long pt_threshold(const F& member, int 
         __syncthreads();
         const int h0 = (int)sh.hist[2 * tid], h1 = (int)sh.hist[2 * tid + 1];
         int total;
-        const int before = pt_block_scan(h0 + h1, sh.scan, total);
+        const int before = block_scan<PT_WAVES>(h0 + h1, sh.scan, total);
         if (hi == 64 && total <= need) {       // fewer members than asked for: all of them
             selected = total;
             return PT_NONE;

@@ -4,7 +4,7 @@
 // numpy's.
 //
 // offsets, the times and the poses are device data: every grid is sized from num_scans (num_queries), num_poses and num_rows alone.
-//   stamps_zero_kernel    clears the workspace's head (a launch, not a memset: see there)
+//   scan_clear_words      clears the workspace's head (scan_common.h: a launch, not a memset)
 //   stamps_check_kernel   one thread per scan and per pose: the offsets' rule, pose_time strictly increasing; an integer OR into one word
 //                         that the launch before it cleared
 //   stamps_scan_kernel    one thread per scan (query): the bracket index j_i by binary search, the pose at the scan's time, the status
@@ -16,7 +16,7 @@
 //                         1 - 3 steps; the result is the definition's unique index whatever the order), blends, builds Rp and transforms
 //                         its row of the image in place (stride 3 dwords: no bank conflict); the image leaves as whole dwords.  The only
 //                         atomic is the integer OR of EPC_STATUS_PART_POSE.
-#include "train_common.h"
+#include "scan_common.h"
 #include "../../include/epcnet_stamps.h"
 
 #define ST_THREADS 256
@@ -38,7 +38,8 @@ __device__ __forceinline__ unsigned long long st_fraction(unsigned long long num
     return q;
 }
 
-// the pose at time tau in bracket j as [R | t] in m[12]; false, and twelve NaN words, when it is invalid
+// the pose at time tau in bracket j as [R | t] in m[12]; false, and twelve NaN words, when it is invalid.  (Not sm_pair_entry of
+// submap.hip: another published definition)
 __device__ __forceinline__ bool st_pose_at(const long long* __restrict__ pose_time, const double* __restrict__ pose, int j, long long tau,
                                            long long max_gap, double* m) {
 #pragma clang fp contract(off)
@@ -81,14 +82,15 @@ __device__ __forceinline__ bool st_pose_at(const long long* __restrict__ pose_ti
         }
     }
     if (!ok) {
-        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        const double nan = epc_nan_f64();
 #pragma unroll
         for (int c = 0; c < 12; ++c) m[c] = nan;
     }
     return ok;
 }
 
-// q_a of one row: the pose (rp) at the row's own time, the pose (rs) at its scan's
+// q_a of one row: the pose (rp) at the row's own time, the pose (rs) at its scan's.  (Not sm_row of submap.hip: another layout, another
+// association of the sums)
 __device__ __forceinline__ void st_row(const double* rp, const double* __restrict__ rs, float xf, float yf, float zf, float* ox, float* oy,
                                        float* oz) {
 #pragma clang fp contract(off)
@@ -101,23 +103,12 @@ __device__ __forceinline__ void st_row(const double* rp, const double* __restric
     *oz = (float)((rs[2] * w0 + rs[6] * w1) + rs[10] * w2);
 }
 
-// ---- launch 0: the word the check counts in ---------------------------------------------------------------------------------------------
-// A kernel, not hipMemsetAsync: seen on an MI355X, a memset node of a captured graph wrote other bytes than its value from the
-// second replay on (tests/test_gpu_stamps.py replays its graph twice for this).
-__global__ void stamps_zero_kernel(int32_t* words, int count) {
-    if ((int)threadIdx.x < count) words[threadIdx.x] = 0;
-}
-
 // ---- launch 1: the whole-call failures ------------------------------------------------------------------------------------------------
 // offsets may be NULL (epcnet_pose_interp: the order of pose_time alone)
 __global__ __launch_bounds__(ST_THREADS) void stamps_check_kernel(const int32_t* __restrict__ offsets, long long num_rows, int num_scans,
                                                                   const long long* __restrict__ pose_time, int num_poses, int32_t* flag) {
     const long long i = (long long)blockIdx.x * ST_THREADS + threadIdx.x;
-    int bad = 0;
-    if (offsets) {
-        if (i == 0) bad = (offsets[0] < 0 || (long long)offsets[num_scans] > num_rows) ? 1 : 0;
-        if (i < num_scans) bad |= offsets[i] > offsets[i + 1] ? 1 : 0;
-    }
+    int bad = (offsets && offsets_rule_bad(offsets, num_scans, num_rows, i)) ? 1 : 0;
     if (i + 1 < num_poses) bad |= pose_time[i] < pose_time[i + 1] ? 0 : 1;
     if (bad) atomicOr(flag, EPC_STATUS_NO_POSE);
 }
@@ -151,7 +142,7 @@ __global__ __launch_bounds__(ST_THREADS) void stamps_scan_kernel(const long long
         for (int c = 0; c < 12; ++c) pose_out[(size_t)i * 12 + c] = m[c];
         if (!ok) j = -1;
     } else {
-        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        const double nan = epc_nan_f64();
         for (int c = 0; c < 12; ++c) pose_out[(size_t)i * 12 + c] = nan;
     }
     status[i] = j >= 0 ? 0 : EPC_STATUS_NO_POSE;
@@ -211,17 +202,9 @@ __global__ __launch_bounds__(ST_THREADS) void stamps_row_kernel(const float* __r
     for (int d = 3 * a + tid; d < 3 * b; d += ST_THREADS) img[d] = src[d];
     for (int r = a + tid; r < b; r += ST_THREADS) dts[r] = point_dt[(size_t)t0 + r];
 
-    int i = 0;                                         // thread 0's walk: the scan of tile-local row `at`
+    int i = 0;                                         // thread 0's walk: the scan of tile-local row `at` (submap.hip's walk steps over slots too)
     if (tid == 0) {
-        int lo = 0, hi = num_scans - 1;                // the first scan whose end lies behind row r_lo (it exists: r_lo < last)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if ((long long)offsets[mid + 1] > r_lo)
-                hi = mid;
-            else
-                lo = mid + 1;
-        }
-        i = lo;
+        i = first_scan_behind(offsets, 0, num_scans - 1, r_lo);          // the first scan whose end lies behind row r_lo (it exists: r_lo < last)
     }
     for (int at = a; at < b;) {
         if (tid == 0) {
@@ -247,15 +230,8 @@ __global__ __launch_bounds__(ST_THREADS) void stamps_row_kernel(const float* __r
         for (int p = tid; p < np; p += ST_THREADS) p_j[p] = scan_j[p_scan[p]], p_time[p] = scan_time[p_scan[p]];
         __syncthreads();
         for (int row = at + tid; row < b1; row += ST_THREADS) {
-            int lo = 0, hi = np - 1;                   // the last pair that begins at or before the row
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (p_out[mid] <= row)
-                    lo = mid;
-                else
-                    hi = mid - 1;
-            }
-            const float nanf = __int_as_float(0x7fc00000);
+            const int lo = pair_of_row(p_out, np, row);
+            const float nanf = epc_nan_f32();
             float ox = nanf, oy = nanf, oz = nanf;
             const int js = p_j[lo];
             if (js >= 0) {                             // the scan's pose is valid
@@ -264,7 +240,8 @@ __global__ __launch_bounds__(ST_THREADS) void stamps_row_kernel(const float* __r
                 const bool ok = st_pose_at(pose_time, pose, st_bracket(pose_time, num_poses, js, tau), tau, max_gap, m);
                 if (!ok) atomicOr(&status[p_scan[lo]], EPC_STATUS_PART_POSE);
                 const float x = img[3 * row], y = img[3 * row + 1], z = img[3 * row + 2];
-                if (ok && __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z)) st_row(m, sp[lo], x, y, z, &ox, &oy, &oz);
+                const bool finite = epc_finite3(x, y, z);      // (named: inside the condition hipcc takes 126 VGPRs for this kernel, not 68)
+                if (ok && finite) st_row(m, sp[lo], x, y, z, &ox, &oy, &oz);
             }
             img[3 * row] = ox, img[3 * row + 1] = oy, img[3 * row + 2] = oz;
         }
@@ -296,8 +273,7 @@ extern "C" int epcnet_pose_interp(const long long* pose_time, const double* pose
     if (num_queries == 0) return EPC_OK;
     hipStream_t st = (hipStream_t)stream;
     // status[0] is the check's word until query 0 is written, behind all the others
-    hipLaunchKernelGGL(stamps_zero_kernel, dim3(1), dim3(64), 0, st, status, 1);
-    EPC_CHECK_LAUNCH();
+    if (int rc = scan_clear_words_launch(status, 1, st, __func__)) return rc;
     hipLaunchKernelGGL(stamps_check_kernel, dim3(st_blocks(num_poses)), dim3(ST_THREADS), 0, st, (const int32_t*)nullptr, 0ll, 0, pose_time,
                        num_poses, status);
     EPC_CHECK_LAUNCH();
@@ -323,17 +299,11 @@ extern "C" int epcnet_scan_deskew(const float* points, const int32_t* offsets, l
     EPC_CHECK_ARG(num_scans >= 0 && num_scans <= (1 << 24), "need 0 <= num_scans <= 2^24");
     EPC_CHECK_ARG(num_poses >= 2 && num_poses <= (1 << 24), "need 2 <= num_poses <= 2^24");
     EPC_CHECK_ARG(max_gap_ns >= 1 && max_gap_ns < 2147483648ll, "need 1 <= max_gap_ns < 2^31");
-    EPC_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
-    const size_t need = epcnet_deskew_workspace_bytes(num_scans, num_poses, num_rows);
-    if (workspace_bytes < need) {
-        epc_set_error("epcnet_scan_deskew: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-        return EPC_ENOMEM;
-    }
+    EPC_CHECK_WORKSPACE(workspace, workspace_bytes, epcnet_deskew_workspace_bytes(num_scans, num_poses, num_rows));
     hipStream_t st = (hipStream_t)stream;
     int32_t* head = reinterpret_cast<int32_t*>(workspace);
     int32_t* scan_j = head + ST_HEAD;
-    hipLaunchKernelGGL(stamps_zero_kernel, dim3(1), dim3(64), 0, st, head, ST_HEAD);
-    EPC_CHECK_LAUNCH();
+    if (int rc = scan_clear_words_launch(head, ST_HEAD, st, __func__)) return rc;
     const int most = num_scans > num_poses ? num_scans : num_poses;
     hipLaunchKernelGGL(stamps_check_kernel, dim3(st_blocks(most)), dim3(ST_THREADS), 0, st, offsets, num_rows, num_scans, pose_time,
                        num_poses, head);

@@ -3,8 +3,9 @@
 // one rounding to float32 at the end and integer counts, so the result is the same bits on every run and equal to numpy's.
 //
 // offsets, poses and along are device data: every grid is sized from num_scans, max_submaps and out_rows alone.
+//   scan_clear_words       clears the workspace's head (scan_common.h: a launch, not a memset)
 //   submap_check_kernel    one thread per scan: the offsets' rule, along finite and non-decreasing; an integer OR into one word that the
-//                          call's memset cleared
+//                          launch before it cleared
 //   submap_seg_kernel      one thread per slot (and one for slot max_submaps, which only says whether the trajectory goes on): c, s, e,
 //                          the three lower bounds in `along`, rows_k, sub_pose, sub_info
 //   submap_layout_kernel   ONE workgroup: the exclusive integer scan of rows_k in chunks of its width with a running carry, the fit rule,
@@ -16,7 +17,7 @@
 //                          dword d of the source: a submap's rows are contiguous in the source) into an LDS image, every thread
 //                          transforms rows of the image in place (stride 3 dwords: no bank conflict), and the image leaves as whole
 //                          dwords again.  No global atomics, no float atomics anywhere.
-#include "train_common.h"
+#include "scan_common.h"
 #include "../../include/epcnet_submaps.h"
 
 #define SM_THREADS 256
@@ -50,11 +51,9 @@ struct sm_params {
 __global__ __launch_bounds__(SM_THREADS) void submap_check_kernel(const int32_t* __restrict__ offsets, const double* __restrict__ along,
                                                                   long long num_rows, int num_scans, sm_ws ws) {
     const long long i = (long long)blockIdx.x * SM_THREADS + threadIdx.x;
-    int bad = 0;
-    if (i == 0) bad = (num_scans == 0 || offsets[0] < 0 || (long long)offsets[num_scans] > num_rows) ? 1 : 0;
+    int bad = ((i == 0 && num_scans == 0) || offsets_rule_bad(offsets, num_scans, num_rows, i)) ? 1 : 0;      // no scan: a failed call
     if (i < num_scans) {
         const double a = along[i];
-        bad |= offsets[i] > offsets[i + 1] ? 1 : 0;
         bad |= __builtin_isfinite(a) ? 0 : 1;
         if (i + 1 < num_scans) bad |= a <= along[i + 1] ? 0 : 1;          // (a NaN behind it is bad in its own thread)
     }
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(SM_THREADS) void submap_seg_kernel(const int32_t* _
     int32_t* g = ws.seg + (size_t)k * 4;
     g[0] = lo, g[1] = hi, g[2] = ref, g[3] = rows;
     if (k == max_submaps) return;                      // the slot behind the last one has no outputs
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = epc_nan_f64();
     for (int c = 0; c < 12; ++c) sub_pose[(size_t)k * 12 + c] = ref >= 0 ? poses[(size_t)ref * 12 + c] : nan;
     if (sub_info) {
         int32_t* o = sub_info + (size_t)k * 4;
@@ -106,27 +105,6 @@ __global__ __launch_bounds__(SM_THREADS) void submap_seg_kernel(const int32_t* _
 }
 
 // ---- launch 3: the layout -------------------------------------------------------------------------------------------------------------
-// inclusive scan of one value per thread over the workgroup; `part` holds one word per wave
-__device__ __forceinline__ long long sm_block_scan(long long v, long long* part, long long* total) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const long long o = __shfl_up(v, off);
-        if (lane >= off) v += o;
-    }
-    __syncthreads();                                   // (the last chunk's readers of `part` are done)
-    if (lane == 63) part[wave] = v;
-    __syncthreads();
-    long long before = 0, all = 0;
-    for (int w = 0; w < SM_SCAN_THREADS / 64; ++w) {
-        const long long p = part[w];
-        before += w < wave ? p : 0;
-        all += p;
-    }
-    *total = all;
-    return v + before;
-}
-
 __global__ __launch_bounds__(SM_SCAN_THREADS) void submap_layout_kernel(int max_submaps, long long out_rows, sm_ws ws,
                                                                         int32_t* __restrict__ sub_offsets, int32_t* __restrict__ num_out,
                                                                         int32_t* __restrict__ status) {
@@ -142,9 +120,10 @@ __global__ __launch_bounds__(SM_SCAN_THREADS) void submap_layout_kernel(int max_
         const int k = base + tid;
         const int rows = k < max_submaps ? ws.seg[(size_t)k * 4 + 3] : 0;
         const bool is_submap = k < max_submaps && ws.seg[(size_t)k * 4] >= 0;
+        const long long v = rows > 0 ? rows : 0;
         long long total;
-        const long long incl = carry + sm_block_scan(rows > 0 ? rows : 0, part, &total);
-        if (k < max_submaps) ws.P[k] = incl - (rows > 0 ? rows : 0);
+        const long long excl = carry + block_scan<SM_SCAN_THREADS / 64>(v, part, total), incl = excl + v;
+        if (k < max_submaps) ws.P[k] = excl;
         if (is_submap) {
             ++my_count;
             if (incl <= out_rows && incl > my_fit) my_fit = incl;          // P[k + 1] of a submap that fits (P is monotone: the largest)
@@ -174,7 +153,7 @@ __global__ __launch_bounds__(SM_SCAN_THREADS) void submap_layout_kernel(int max_
 }
 
 // ---- launch 4: the rows ---------------------------------------------------------------------------------------------------------------
-// q_a and the keep rule of one row; returns the three output words
+// q_a and the keep rule of one row; returns the three output words.  (Not st_row of stamps.hip: another layout, another association)
 __device__ __forceinline__ void sm_row(const double* __restrict__ m, const sm_params& pr, float xf, float yf, float zf, float* ox,
                                        float* oy, float* oz) {
 #pragma clang fp contract(off)
@@ -184,13 +163,13 @@ __device__ __forceinline__ void sm_row(const double* __restrict__ m, const sm_pa
     const double q1 = ((m[3] * x + m[4] * y) + m[5] * z) + m[10];
     const double q2 = ((m[6] * x + m[7] * y) + m[8] * z) + m[11];
     const bool keep = rr >= pr.min2 && (q0 * q0 + q1 * q1) <= pr.max2 && pr.z_min <= q2 && q2 <= pr.z_max;
-    const float nan = __int_as_float(0x7fc00000);
+    const float nan = epc_nan_f32();
     *ox = keep ? (float)q0 : nan;
     *oy = keep ? (float)q1 : nan;
     *oz = keep ? (float)q2 : nan;
 }
 
-// entry e of a pair's M | u: M[a][b] at 3a + b, u[a] at 9 + a
+// entry e of a pair's M | u: M[a][b] at 3a + b, u[a] at 9 + a.  (Not st_pose_at of stamps.hip: another published definition)
 __device__ __forceinline__ double sm_pair_entry(const double* __restrict__ Ri, const double* __restrict__ Rr, int e) {
 #pragma clang fp contract(off)
     if (e < 9) {
@@ -218,29 +197,13 @@ __global__ __launch_bounds__(SM_THREADS) void submap_gather_kernel(const float* 
     if (t0 >= total) return;                           // (uniform)
     const int rows_here = (int)(t0 + SM_TILE < total ? SM_TILE : total - t0);
 
-    // thread 0's walk: the slot k and the scan i of tile-local row `at`
+    // thread 0's walk: the slot k and the scan i of tile-local row `at`.  (Not shared with the walk of stamps.hip: this one steps over slots too)
     int k = 0, i = 0;
     if (tid == 0) {
-        int lo = 0, hi = max_submaps;                  // the first slot whose end lies behind row t0 (it exists: t0 < total)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if ((long long)sub_offsets[mid + 1] > t0)
-                hi = mid;
-            else
-                lo = mid + 1;
-        }
-        k = lo;
+        k = first_scan_behind(sub_offsets, 0, max_submaps, t0);          // the first slot whose end lies behind row t0 (it exists: t0 < total)
         const int32_t* g = ws.seg + (size_t)k * 4;
         const int src = offsets[g[0]] + (int)(t0 - sub_offsets[k]);
-        lo = g[0], hi = g[1];                          // the first scan of the slot whose end lies behind row src
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (offsets[mid + 1] > src)
-                hi = mid;
-            else
-                lo = mid + 1;
-        }
-        i = lo;
+        i = first_scan_behind(offsets, g[0], g[1], src);                 // the first scan of the slot whose end lies behind row src
     }
     for (int at = 0; at < rows_here;) {
         if (tid == 0) {
@@ -277,26 +240,12 @@ __global__ __launch_bounds__(SM_THREADS) void submap_gather_kernel(const float* 
         // the batch's dwords in: dword d of the tile from the pair that holds its row
         for (int d = 3 * b0 + tid; d < 3 * b1; d += SM_THREADS) {
             const int row = d / 3;
-            int lo = 0, hi = np - 1;                   // the last pair that begins at or before the row
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (p_out[mid] <= row)
-                    lo = mid;
-                else
-                    hi = mid - 1;
-            }
+            const int lo = pair_of_row(p_out, np, row);
             img[d] = points[(size_t)p_src[lo] * 3 + (size_t)(d - 3 * p_out[lo])];
         }
         __syncthreads();
         for (int row = b0 + tid; row < b1; row += SM_THREADS) {
-            int lo = 0, hi = np - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (p_out[mid] <= row)
-                    lo = mid;
-                else
-                    hi = mid - 1;
-            }
+            const int lo = pair_of_row(p_out, np, row);
             float ox, oy, oz;
             sm_row(mu[lo], pr, img[3 * row], img[3 * row + 1], img[3 * row + 2], &ox, &oy, &oz);
             img[3 * row] = ox, img[3 * row + 1] = oy, img[3 * row + 2] = oz;
@@ -337,12 +286,7 @@ extern "C" int epcnet_submap_build(const float* points, const int32_t* offsets, 
     EPC_CHECK_ARG(__builtin_isfinite(max_range) && max_range > 0.0, "max_range must be finite and > 0");
     EPC_CHECK_ARG(z_min == z_min && z_max == z_max, "z_min and z_max must not be NaN (-Inf, +Inf: no limit)");
     EPC_CHECK_ARG(params[6] == 0.0 && params[7] == 0.0, "the two reserved parameters must be 0");
-    EPC_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
-    const size_t need = epcnet_submap_workspace_bytes(num_scans, max_submaps, num_rows, out_rows);
-    if (workspace_bytes < need) {
-        epc_set_error("epcnet_submap_build: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-        return EPC_ENOMEM;
-    }
+    EPC_CHECK_WORKSPACE(workspace, workspace_bytes, epcnet_submap_workspace_bytes(num_scans, max_submaps, num_rows, out_rows));
     sm_params pr;
     {
 #pragma clang fp contract(off)
@@ -355,10 +299,7 @@ extern "C" int epcnet_submap_build(const float* points, const int32_t* offsets, 
     }
     hipStream_t st = (hipStream_t)stream;
     const sm_ws ws = sm_carve(workspace, max_submaps);
-    if (hipMemsetAsync(ws.head, 0, SM_HEAD * sizeof(int32_t), st) != hipSuccess) {
-        epc_set_error("epcnet_submap_build: memset failed");
-        return EPC_EHIP;
-    }
+    if (int rc = scan_clear_words_launch(ws.head, SM_HEAD, st, __func__)) return rc;
     const int check_blocks = num_scans > 0 ? (num_scans + SM_THREADS - 1) / SM_THREADS : 1;
     hipLaunchKernelGGL(submap_check_kernel, dim3(check_blocks), dim3(SM_THREADS), 0, st, offsets, along, num_rows, num_scans, ws);
     EPC_CHECK_LAUNCH();

@@ -1,7 +1,7 @@
 // ONE definition of the primitives the training step's three kernel families share -- the per-layer operators (train_ops.hip,
 // train_head.hip, train_hidden.hip), the streamed conv5 / VLAD head (train_head_common.h) and the fused backbone chain
 // (train_chain_common.h) -- so that kernels under a bit-for-bit contract with each other round alike (as conv1_quad of common.h
-// does for the inference path).  The two host helpers at the end serve every launcher of the library.
+// does for the inference path).  (The launchers' host helpers, epc_aligned16 and epc_set_dyn_lds, are in common.h.)
 #pragma once
 #include "common.h"
 
@@ -131,19 +131,3 @@ __device__ __forceinline__ float4 neighbour_mean_of(const float4* z4, const floa
     }
     return make_float4(acc.x / kdiv, acc.y / kdiv, acc.z / kdiv, acc.w / kdiv);
 }
-
-// ---- host ------------------------------------------------------------------------------------------------------------------
-static inline bool epc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// Opt a kernel in to `bytes` of dynamic LDS (more than the default 64 KB needs it).  A launcher that is not itself the entry point
-// passes the entry point's name on; EPC_SET_DYN_LDS is the form for an entry point's own body.
-static inline int epc_set_dyn_lds(const void* kernel, size_t bytes, const char* who) {
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) return EPC_OK;
-    epc_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-    return EPC_EHIP;
-}
-#define EPC_SET_DYN_LDS(kernel, bytes)                                                                  \
-    do {                                                                                                \
-        if (epc_set_dyn_lds(reinterpret_cast<const void*>(kernel), bytes, __func__) != EPC_OK) return EPC_EHIP; \
-    } while (0)

@@ -77,7 +77,7 @@ extern "C" {
  * or num_scans == 0, then EVERY slot is no submap: EPC_STATUS_NO_SUBMAP, NaN pose, info -1 -1 -1 0, num_out 0 0, every sub_offsets 0,
  * no row of points_out written.  A stationary trajectory (a constant `along`) is valid and has no submap.
  *
- * Four launches and one 16-byte memset on `stream`, sized from num_scans, max_submaps and out_rows alone; the call zeroes what it
+ * Five launches and no memset on `stream` (the first clears the workspace's 16-byte head), sized from num_scans, max_submaps and out_rows alone; the call zeroes what it
  * counts in: capturable in a graph and replayable on other points, offsets, poses and along (params are read at the call: they are
  * part of the capture).  Integer atomics only.  EPC_EINVAL, with nothing launched and nothing written, unless 0 <= num_rows,
  * 0 <= num_scans <= 2^24, 1 <= max_submaps <= 65535, 0 <= out_rows < 2^31, length and spacing are finite and > 0, 0 <= min_range,

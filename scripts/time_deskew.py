@@ -6,7 +6,6 @@ cost of the stamps stage.  HIP events around `--steps` calls, `--regions` region
 runs eagerly on one stream.  One JSON line, stamped with the SHA-256 of the loaded library.
 Usage (GPU box): python scripts/time_deskew.py [--steps K] [--regions R] [--warmup W] [--out FILE]"""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -17,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import _timing  # noqa: E402
 import bench  # noqa: E402
 import downsample_ref as D  # noqa: E402
 import helpers as H  # noqa: E402
@@ -92,21 +92,8 @@ arms = {
                                                    num_points=args.n, submaps=sub, out=desc),
     "forward_trajectory": lambda: eng.forward_trajectory(moved, offsets, poses12, along=along, num_points=args.n, submaps=sub, out=desc),
 }
-for fn in arms.values():
-    for _ in range(args.warmup):
-        fn()
-torch.cuda.synchronize()
-times = {k: [] for k in arms}
-for _ in range(args.regions):
-    for k, fn in arms.items():
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        start.record()
-        for _ in range(args.steps):
-            fn()
-        end.record()
-        end.synchronize()
-        times[k].append(start.elapsed_time(end) / args.steps)
+times = {k: [t * 1e3 / args.steps for t in v]
+         for k, v in _timing.alternate(arms, args.steps, args.regions, args.warmup, events=True).items()}
 ms = {k: statistics.median(v) for k, v in times.items()}
 row_ms = ms["deskew"] - ms["poses_only"]
 copy_gb_s = 2 * 28 * rows / ms["copy_28B_per_row"] / 1e6           # a copy reads and writes its bytes
@@ -120,11 +107,5 @@ line = {"workload": "epcnet_scan_deskew on %d sweeps x %d rows, %d poses; forwar
                        "copy_gb_per_s": round(copy_gb_s, 1), "byte_floor_ms": round(floor_ms, 4), "over_floor": round(row_ms / floor_ms, 3),
                        "gb_per_s": round(28 * rows / row_ms / 1e6, 1)},
         "engine": {"forward_stamped_ms": round(ms["forward_stamped"], 4), "forward_trajectory_ms": round(ms["forward_trajectory"], 4),
-                   "difference_ms": round(ms["forward_stamped"] - ms["forward_trajectory"], 4)},
-        "lib_sha256": bench.lib_sha256()}
-text = json.dumps(line)
-print(text)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+                   "difference_ms": round(ms["forward_stamped"] - ms["forward_trajectory"], 4)}}
+_timing.emit(line, args.out)

@@ -5,19 +5,16 @@ median region.  Also the kernel's registers / LDS / scratch as the compiler repo
 --no-resources).  One JSON line, stamped with the SHA-256 of the loaded library.
 Usage (GPU box): python scripts/time_downsample.py [--steps K] [--regions R] [--warmup W] [--out FILE]"""
 import argparse
-import json
 import os
-import re
 import statistics
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
+import _timing  # noqa: E402
 import bench  # noqa: E402
 import downsample_ref as R  # noqa: E402
 
@@ -36,18 +33,12 @@ args = ap.parse_args()
 def kernel_resources():
     """Registers, static LDS and scratch of grid_downsample_kernel from hipcc's resource remarks; the dynamic LDS from the launch's own
     formula (csrc/downsample.hip: table of T = pow2 >= 4n slots, then pairs + kept keys, counts and sums)."""
-    csrc = os.path.join(ROOT, "epc-net_amd", "csrc")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=on", "-fno-slp-vectorize",
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(csrc, "downsample.hip"), "-o", os.devnull]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    grab = lambda name: int(re.search(r"\b%s:\s*(\d+)" % re.escape(name), text).group(1))
+    k = _timing.kernel_resources("downsample.hip", r"grid_downsample_kernel")["grid_downsample_kernel"]
     T = 4096
     while T < 4 * args.n:
         T *= 2
-    return {"vgprs": grab("VGPRs"), "sgprs": grab("TotalSGPRs"), "scratch_bytes_per_lane": grab("ScratchSize [bytes/lane]"),
-            "vgpr_spills": grab("VGPRs Spill"), "lds_static_bytes": grab("LDS Size [bytes/block]"),
-            "lds_dynamic_bytes": max(8 * T, 4 * T + 20 * args.n), "threads": 1024}
+    return {"vgprs": k["vgprs"], "sgprs": k["sgprs"], "scratch_bytes_per_lane": k["scratch_bytes_per_lane"], "vgpr_spills": k["vgpr_spills"],
+            "lds_static_bytes": k["lds_bytes"], "lds_dynamic_bytes": max(8 * T, 4 * T + 20 * args.n), "threads": 1024}
 
 
 ops, E = bench.pkg("ops"), bench.pkg("engine")
@@ -59,19 +50,7 @@ xyz, status, info = ops.grid_downsample(points, offsets, args.n)
 out = torch.empty((args.scans, 256), dtype=torch.float32, device=dev)
 arms = {"downsample": lambda: ops.grid_downsample(points, offsets, args.n, out=xyz),
         "forward": lambda: eng.forward(xyz, out=out)}
-for fn in arms.values():
-    for _ in range(args.warmup):
-        fn()
-torch.cuda.synchronize()
-times = {k: [] for k in arms}
-for _ in range(args.regions):
-    for k, fn in arms.items():
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            fn()
-        torch.cuda.synchronize()
-        times[k].append(time.perf_counter() - t0)
+times = _timing.alternate(arms, args.steps, args.regions, args.warmup)
 ms = {k: statistics.median(v) / args.steps * 1e3 for k, v in times.items()}
 info_h = info.cpu()
 line = {"workload": "%d scenes x %d points -> %d (ops.grid_downsample), then InferenceEngine.forward (EPC-Net, f32) on the %d results"
@@ -85,11 +64,5 @@ line = {"workload": "%d scenes x %d points -> %d (ops.grid_downsample), then Inf
         "descriptors_finite": bool(torch.isfinite(out).all()),
         "regions_s": {k: [round(t, 5) for t in v] for k, v in times.items()},
         "steps_per_region": args.steps,
-        "kernel": None if args.no_resources else kernel_resources(),
-        "lib_sha256": bench.lib_sha256()}
-text = json.dumps(line)
-print(text)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+        "kernel": None if args.no_resources else kernel_resources()}
+_timing.emit(line, args.out)

@@ -7,19 +7,16 @@ scorer's cost model: 9 non-fused lane operations per (row, hypothesis) against h
 stamped with the SHA-256 of the loaded library.
 Usage (GPU box): python scripts/time_ground.py [--steps K] [--regions R] [--warmup W] [--out FILE]"""
 import argparse
-import json
 import os
-import re
 import statistics
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
+import _timing  # noqa: E402
 import bench  # noqa: E402
 import downsample_ref as R  # noqa: E402
 
@@ -40,21 +37,9 @@ args = ap.parse_args()
 
 def kernel_resources():
     """Registers, LDS and scratch of the four kernels of csrc/ground.hip from hipcc's resource remarks."""
-    csrc = os.path.join(ROOT, "epc-net_amd", "csrc")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=on", "-fno-slp-vectorize",
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(csrc, "ground.hip"), "-o", os.devnull]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out = {}
-    for block in text.split("Function Name:")[1:]:
-        name = re.search(r"ground_\w+_kernel", block)
-        if not name:
-            continue
-        grab = lambda key: int(re.search(r"\b%s:\s*(\d+)" % re.escape(key), block).group(1))
-        out[name.group(0)] = {"vgprs": grab("VGPRs"), "sgprs": grab("TotalSGPRs"), "scratch_bytes_per_lane": grab("ScratchSize [bytes/lane]"),
-                              "vgpr_spills": grab("VGPRs Spill"), "lds_bytes": grab("LDS Size [bytes/block]"),
-                              "waves_per_simd": grab("Occupancy [waves/SIMD]"),
-                              "threads": 1024 if name.group(0) == "ground_score_kernel" else 256}
+    out = _timing.kernel_resources("ground.hip", r"ground_\w+_kernel")
+    for name, k in out.items():
+        k["threads"] = 1024 if name == "ground_score_kernel" else 256
     return out
 
 
@@ -76,19 +61,7 @@ arms = {"ground_batch": lambda: ops.remove_ground(points, offsets, hypotheses=ar
         "forward_scans_ground": lambda: eng.forward_scans(points, offsets, num_points=args.n, out=out, ground=ground)}
 if args.only:
     arms = {k: arms[k] for k in args.only.split(",")}
-for fn in arms.values():
-    for _ in range(args.warmup):
-        fn()
-torch.cuda.synchronize()
-times = {k: [] for k in arms}
-for _ in range(args.regions):
-    for k, fn in arms.items():
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            fn()
-        torch.cuda.synchronize()
-        times[k].append(time.perf_counter() - t0)
+times = _timing.alternate(arms, args.steps, args.regions, args.warmup)
 ms = {k: statistics.median(v) / args.steps * 1e3 for k, v in times.items()}
 pairs = float(args.scans) * args.points * args.hypotheses
 model_ms = pairs * 9 / 78.6e12 * 1e3
@@ -106,11 +79,5 @@ line = {"workload": "%d scenes x %d rows and 1 scene x %d rows (ops.remove_groun
         "descriptors_finite": bool(torch.isfinite(out).all()),
         "regions_s": {k: [round(t, 5) for t in v] for k, v in times.items()},
         "steps_per_region": args.steps,
-        "kernels": None if args.no_resources else kernel_resources(),
-        "lib_sha256": bench.lib_sha256()}
-text = json.dumps(line)
-print(text)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+        "kernels": None if args.no_resources else kernel_resources()}
+_timing.emit(line, args.out)

@@ -7,13 +7,9 @@ every region between device synchronisations; the median region.  Also the kerne
 (the Makefile's flags; skipped with --no-resources).  One JSON line, stamped with the SHA-256 of the loaded library.
 Usage (GPU box): python scripts/time_submap.py [--steps K] [--regions R] [--warmup W] [--out FILE]"""
 import argparse
-import json
 import os
-import re
 import statistics
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -21,6 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import _timing  # noqa: E402
 import bench  # noqa: E402
 import downsample_ref as D  # noqa: E402
 import submap_ref as R  # noqa: E402
@@ -33,25 +30,6 @@ ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--no-resources", action="store_true")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file")
 args = ap.parse_args()
-
-
-def kernel_resources():
-    """Registers, LDS and scratch of the four kernels of csrc/submap.hip from hipcc's resource remarks."""
-    csrc = os.path.join(ROOT, "epc-net_amd", "csrc")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=on", "-fno-slp-vectorize",
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(csrc, "submap.hip"), "-o", os.devnull]
-    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    out = {}
-    for block in text.split("Function Name:")[1:]:
-        name = re.search(r"submap_\w+_kernel", block)
-        if not name:
-            continue
-        grab = lambda key: int(re.search(r"\b%s:\s*(\d+)" % re.escape(key), block).group(1))
-        out[name.group(0)] = {"vgprs": grab("VGPRs"), "sgprs": grab("TotalSGPRs"), "scratch_bytes_per_lane": grab("ScratchSize [bytes/lane]"),
-                              "vgpr_spills": grab("VGPRs Spill"), "lds_bytes": grab("LDS Size [bytes/block]"),
-                              "waves_per_simd": grab("Occupancy [waves/SIMD]")}
-    return out
 
 
 ops = bench.pkg("ops")
@@ -93,19 +71,7 @@ for w in loads:
     arms["copy_" + n] = lambda w=w: w["copy_dst"].copy_(w["copy_src"])
     arms["ground_" + n] = lambda w=w: ops.remove_ground(w["out"], w["sub_offsets"], out=w["kept"])
     arms["downsample_" + n] = lambda w=w: ops.grid_downsample(w["kept"], w["sub_offsets"], args.n, out=w["xyz"])
-for fn in arms.values():
-    for _ in range(args.warmup):
-        fn()
-torch.cuda.synchronize()
-times = {k: [] for k in arms}
-for _ in range(args.regions):
-    for k, fn in arms.items():
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            fn()
-        torch.cuda.synchronize()
-        times[k].append(time.perf_counter() - t0)
+times = _timing.alternate(arms, args.steps, args.regions, args.warmup)
 ms = {k: statistics.median(v) / args.steps * 1e3 for k, v in times.items()}
 line = {"workload": "ops.build_submaps on 64 scans x 32768 rows (4 m every 2 m) and 2000 scans x 2000 rows (20 m every 10 m), a "
                     "device-to-device copy of the output's bytes, ops.remove_ground and ops.grid_downsample -> %d on the result" % args.n,
@@ -122,11 +88,5 @@ for w in loads:
                "build_over_copy": round(ms["build_" + n] / ms["copy_" + n], 3),
                "share_of_build_ground_downsample": round(ms["build_" + n] / front, 4),
                "ground_status_nonzero": w["ground_status_nonzero"], "downsample_status_nonzero": w["downsample_status_nonzero"]}
-line["kernels"] = None if args.no_resources else kernel_resources()
-line["lib_sha256"] = bench.lib_sha256()
-text = json.dumps(line)
-print(text)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+line["kernels"] = None if args.no_resources else _timing.kernel_resources("submap.hip", r"submap_\w+_kernel")
+_timing.emit(line, args.out)
