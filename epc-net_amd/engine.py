@@ -226,19 +226,27 @@ class InferenceEngine:
         (include/epcnet_scans.h), on the same stream and into a copy of the rows: the networks were trained on clouds without their
         ground.  ``status`` is then the down-sampler's word ORed with the removal's (EPC_STATUS_NO_GROUND: no plane was found, the
         scan went on as it came).  ``None``, the default, is the path above unchanged."""
+        return self._forward_scans(points, offsets, num_points, normalize, out, ground, False)[:2]
+
+    def _forward_scans(self, points, offsets, num_points, normalize, out, ground, clouds):
+        """``forward_scans`` -> (descriptors, status, metric): with ``clouds`` the rows that fed the network go through a second
+        ``ops.grid_downsample(..., normalize=False)`` on the same stream -- (B, num_points, 3) float32 in the sensor's units, NaN rows where
+        the scan has no grid --, else ``metric`` is None and nothing more is launched."""
         from . import ops
         if ground is None or ground is False:
-            xyz, status, _ = ops.grid_downsample(points, offsets, num_points, normalize=normalize)
-            return self.forward(xyz, out=out), status
-        if ground is not True and not isinstance(ground, dict):
-            raise L.EpcNetError(-1, "forward_scans: `ground` is None, True or a dict of ops.remove_ground's arguments")
-        kept, st_ground, _, _ = ops.remove_ground(points, offsets, **({} if ground is True else ground))
+            kept, st_ground = points, None
+        else:
+            if ground is not True and not isinstance(ground, dict):
+                raise L.EpcNetError(-1, "forward_scans: `ground` is None, True or a dict of ops.remove_ground's arguments")
+            kept, st_ground, _, _ = ops.remove_ground(points, offsets, **({} if ground is True else ground))
         xyz, status, _ = ops.grid_downsample(kept, offsets, num_points, normalize=normalize)
-        return self.forward(xyz, out=out), status | st_ground
+        desc = self.forward(xyz, out=out)
+        metric = ops.grid_downsample(kept, offsets, num_points, normalize=False)[0] if clouds else None
+        return desc, (status if st_ground is None else status | st_ground), metric
 
     def forward_trajectory(self, points: torch.Tensor, offsets: torch.Tensor, poses: torch.Tensor, along: Optional[torch.Tensor] = None,
                            num_points: int = 4096, normalize: bool = True, ground=None, submaps: Optional[dict] = None,
-                           out: Optional[torch.Tensor] = None):
+                           out: Optional[torch.Tensor] = None, clouds: bool = False):
         """Descriptors of POSED scans: ``points`` / ``offsets`` as ``forward_scans`` takes them, in the order the scans were taken,
         ``poses`` (S, 12) or (S, 3, 4) float64 on the device and, optionally, the travelled distance ``along`` (S,) float64 ->
         ``(descriptors (max_submaps, FEATURE_OUTPUT_DIM), status (max_submaps,) int32, sub_pose (max_submaps, 12) float64, num_out (2,)
@@ -249,7 +257,9 @@ class InferenceEngine:
         (per scan, before the build, works too: call ``ops.remove_ground`` on the scans first).  ``status`` is the three stages' words ORed
         together: EPC_STATUS_NO_SUBMAP / EPC_STATUS_NO_ROOM of the build, EPC_STATUS_NO_GROUND, EPC_STATUS_NO_GRID; a slot that is no
         submap has no rows, hence no grid and a NaN descriptor.  ``num_out[0]`` says how many leading slots are submaps;
-        ``sub_pose[:, [3, 7]]`` are their (x, y)."""
+        ``sub_pose[:, [3, 7]]`` are their (x, y).  ``clouds=True`` appends the submaps' METRIC clouds (max_submaps, num_points, 3) float32 --
+        a second ``ops.grid_downsample(..., normalize=False)`` of the same rows on the same stream, in the frame of ``sub_pose`` -- which is
+        what ``retrieval.verify_revisits`` aligns; the default returns exactly the four above."""
         from . import ops
         if submaps is not None and not isinstance(submaps, dict):
             raise L.EpcNetError(-1, "forward_trajectory: `submaps` is None or a dict of ops.build_submaps' arguments")
@@ -257,12 +267,13 @@ class InferenceEngine:
         if "out" in kw or "return_along" in kw:
             raise L.EpcNetError(-1, "forward_trajectory: `submaps` holds build_submaps' parameters, not its `out` or `return_along`")
         sub_points, sub_offsets, st_build, sub_pose, _, num_out = ops.build_submaps(points, offsets, poses, along=along, **kw)
-        desc, status = self.forward_scans(sub_points, sub_offsets, num_points=num_points, normalize=normalize, out=out, ground=ground)
-        return desc, status | st_build, sub_pose, num_out
+        desc, status, metric = self._forward_scans(sub_points, sub_offsets, num_points, normalize, out, ground, clouds)
+        return (desc, status | st_build, sub_pose, num_out) + ((metric,) if clouds else ())
 
     def forward_stamped(self, points: torch.Tensor, offsets: torch.Tensor, scan_time: torch.Tensor, pose_time: torch.Tensor,
                         pose: torch.Tensor, point_dt: Optional[torch.Tensor] = None, max_gap: float = 0.5, num_points: int = 4096,
-                        normalize: bool = True, ground=None, submaps: Optional[dict] = None, out: Optional[torch.Tensor] = None):
+                        normalize: bool = True, ground=None, submaps: Optional[dict] = None, out: Optional[torch.Tensor] = None,
+                        clouds: bool = False):
         """Descriptors of TIMESTAMPED scans and odometry on its own clock: ``points`` / ``offsets`` as ``forward_scans`` takes them, in
         the order the scans were taken, ``scan_time`` (S,) int64 ns, ``pose_time`` (P,) int64 ns with ``pose`` (P, 7) float64 ``tx ty tz
         qw qx qy qz`` and, for a spinning sensor, ``point_dt`` (total,) int32 ns per row -> ``(descriptors (max_submaps,
@@ -272,7 +283,8 @@ class InferenceEngine:
         to those calls made one by one, and capturable in a graph.  ``scan_status`` holds the de-skewer's words per SCAN
         (EPC_STATUS_NO_POSE, EPC_STATUS_PART_POSE); ``status`` the later stages' per submap, as ``forward_trajectory`` returns them.  A scan
         without a pose contributes NaN rows only; a submap whose reference scan has no pose ends as a NaN descriptor.  ``submaps`` holds
-        ``build_submaps``' parameters, but not ``along``."""
+        ``build_submaps``' parameters, but not ``along``.  ``clouds=True`` appends the submaps' metric clouds, as ``forward_trajectory``
+        does."""
         from . import ops
         if submaps is not None and not isinstance(submaps, dict):
             raise L.EpcNetError(-1, "forward_stamped: `submaps` is None or a dict of ops.build_submaps' arguments")
@@ -283,8 +295,8 @@ class InferenceEngine:
         along = ops.travel_along(scan_pose, scan_status)
         sub_points, sub_offsets, st_build, sub_pose, _, num_out = ops.build_submaps(points if moved is None else moved, offsets, scan_pose,
                                                                                     along=along, **kw)
-        desc, status = self.forward_scans(sub_points, sub_offsets, num_points=num_points, normalize=normalize, out=out, ground=ground)
-        return desc, status | st_build, sub_pose, num_out, scan_status
+        desc, status, metric = self._forward_scans(sub_points, sub_offsets, num_points, normalize, out, ground, clouds)
+        return (desc, status | st_build, sub_pose, num_out, scan_status) + ((metric,) if clouds else ())
 
     def last_status(self, xyz_or_count) -> "list[int]":
         """Per-cloud EPC_STATUS_* words of the last pass of the most recent ``forward`` call on this engine's own

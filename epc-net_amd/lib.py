@@ -28,7 +28,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "epcnet.h")
 
 _SCALARS = {"int": c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "float": c_float,
             "size_t": ctypes.c_size_t, "int32_t": c_int32, "uint32_t": ctypes.c_uint32}
-# what include/epcnet_revisits.h passes by value besides: the reader of every other header goes on refusing a `double` parameter
+# what include/epcnet_revisits.h and include/epcnet_pairs.h pass by value besides: the reader of every other header goes on refusing a
+# `double` parameter
 _REVISIT_SCALARS = dict(_SCALARS, double=ctypes.c_double)
 # the dtype a tensor must have where the header declares a typed pointee (``run``); any dtype goes at every other pointer
 _POINTEES = {"float*": torch.float32, "double*": torch.float64, "int32_t*": torch.int32, "int*": torch.int32, "long*": torch.int64}
@@ -36,7 +37,7 @@ _POINTEES = {"float*": torch.float32, "double*": torch.float64, "int32_t*": torc
 
 def parse_header(text: str, need_status: bool = True, scalars=_SCALARS):
     """``(functions, constants, status)`` of the text of include/epcnet.h (or, with ``need_status=False``, of a further header in the
-    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h, include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h): ``functions[name] = (return type, [parameter
+    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h, include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h, include/epcnet_pairs.h): ``functions[name] = (return type, [parameter
     types], [parameter names])`` in header order, the types as C type names without ``const`` and spaces around ``*`` -- a key
     of ``scalars``, or any type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME>
     <integer>``; ``status``: the members of ``enum epc_status``.  Raises ValueError on whatever it does not understand."""
@@ -135,6 +136,19 @@ if (set(_revisit_functions) & (set(_functions) | set(_pose_functions) | set(_sca
     raise ImportError("epcnet_revisits.h declares a name an earlier header declares")
 _constants.update(_revisit_constants)
 REVISIT_EXPORTS = list(_revisit_functions)
+# the seventh header (pair registration: ICP of candidate pairs of clouds from seed poses): read, bound and listed like the sixth, with
+# the scalars that allow a `double` by value (max_dist); its two status bits join the EPC_* constants
+PAIRS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_pairs.h")
+if not os.path.exists(PAIRS_HEADER_PATH):
+    raise ImportError("%s is missing: the binding of the pair entries is derived from it" % PAIRS_HEADER_PATH)
+with open(PAIRS_HEADER_PATH) as _f:
+    _pair_functions, _pair_constants, _ = parse_header(_f.read(), need_status=False, scalars=_REVISIT_SCALARS)
+if (set(_pair_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions) | set(_stamp_functions)
+                            | set(_revisit_functions))
+        or set(_pair_constants) & set(_constants)):
+    raise ImportError("epcnet_pairs.h declares a name an earlier header declares")
+_constants.update(_pair_constants)
+PAIR_EXPORTS = list(_pair_functions)
 globals().update(_constants, **_status)     # EPC_OK, EPC_EINVAL, EPC_KNN_CAP, EPC_PRECISION_FAST, EPC_NUM_STAGES ... as module attributes
 # every symbol include/epcnet.h declares, in its order (tests check the library exports exactly these)
 EXPORTS = list(_functions)
@@ -184,7 +198,8 @@ _lib = ctypes.CDLL(LIB_PATH)
 # a pointer to a structure mirrored above keeps its type check; every other pointer is a void*
 _POINTERS = {"epc_cfg*": POINTER(EpcCfg), "epc_chain_fwd_args*": POINTER(ChainFwdArgs)}
 for _name, (_ret, _params, _) in (list(_functions.items()) + list(_pose_functions.items()) + list(_scan_functions.items())
-                                  + list(_submap_functions.items()) + list(_stamp_functions.items()) + list(_revisit_functions.items())):
+                                  + list(_submap_functions.items()) + list(_stamp_functions.items()) + list(_revisit_functions.items())
+                                  + list(_pair_functions.items())):
     _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
     _fn.restype = c_char_p if _ret == "char*" else _REVISIT_SCALARS[_ret]
     _fn.argtypes = [_REVISIT_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
@@ -284,9 +299,9 @@ for _name, (_ret, _t, _pn) in _pose_functions.items():          # every entry of
     assert _ret == "int" and (_t[-1], _pn[-1]) == ("void*", "stream"), "%s does not take a stream last and return a status" % _name
     setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))
 for _name, (_ret, _t, _pn) in (list(_scan_functions.items()) + list(_submap_functions.items()) + list(_stamp_functions.items())
-                               + list(_revisit_functions.items())):
-    # include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h and include/epcnet_revisits.h: the entries that take a
-    # stream launch
+                               + list(_revisit_functions.items()) + list(_pair_functions.items())):
+    # include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h and include/epcnet_pairs.h: the
+    # entries that take a stream launch
     if _t and (_t[-1], _pn[-1]) == ("void*", "stream"):
         assert _ret == "int", "%s takes a stream and does not return a status" % _name
         setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))

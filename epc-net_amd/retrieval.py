@@ -6,6 +6,8 @@
   knn_search           evaluate.py:463,481  sklearn KDTree(database).query(q, k=25) -> epc_pairwise_topk on the GPU
   revisit_search       (no counterpart)     the same exact search along ONE trajectory: per query only the rows at least min_travel behind
                        it (epcnet_revisit_search); RevisitIndex is its streaming form
+  register_pairs       (no counterpart)     point-to-point ICP of candidate pairs of metric clouds from seed poses, and how well each pair
+                       fits (epcnet_pair_register); verify_revisits runs it on revisit_search's candidates, yaw_seeds builds hypotheses
   mine_topk            train.py:857-869     the hard-negative KDTree query over rows named by id (epc_mine_topk)
   get_recall           evaluate.py:455-537  recall@1..25, top-1 % recall, top-1 similarity for one (m, n) run pair
   evaluate_runs        evaluate.py:293-332  average over all ordered pairs m != n
@@ -223,6 +225,110 @@ class RevisitIndex:
         self._along[a:b].copy_(along)
         self._n = b
         return revisit_search(self._desc[:b], self._along[:b], self.min_travel, self.k, queries=self._desc[a:b], q_along=self._along[a:b])
+
+
+def _pair_check(name: str, t, dtype, ndim: int, device=None, last=None):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise L.EpcNetError(-1, "register_pairs: %s must live on a ROCm device (no CPU fallback)" % name)
+    if t.dtype != dtype or not t.is_contiguous():
+        raise L.EpcNetError(-1, "register_pairs: %s must be a contiguous %s tensor, got %s%s" % (
+            name, dtype, t.dtype, " (poses are float64: they are refused, never converted)" if dtype == torch.float64 else ""))
+    if t.dim() != ndim or (last is not None and int(t.shape[-1]) != last) or (device is not None and t.device != device):
+        raise L.EpcNetError(-1, "register_pairs: %s must be %d-d%s on the clouds' device, got %s" % (
+            name, ndim, "" if last is None else " with a last dimension of %d" % last, tuple(t.shape)))
+
+
+def register_pairs(clouds: torch.Tensor, pairs: torch.Tensor, seeds: Optional[torch.Tensor] = None, max_dist: float = 1.0,
+                   iterations: int = 16, min_pairs: int = 32, workspace: Optional[torch.Tensor] = None):
+    """Geometric verification of candidate pairs (include/epcnet_pairs.h): for every row (source, target) of ``pairs`` (P, 2) int32 the
+    rigid alignment of cloud ``source`` onto cloud ``target`` by point-to-point ICP, and how well the two fit.  ``clouds`` (C, n, 3)
+    float32 in METRIC units (``ops.grid_downsample(..., normalize=False)``; a row with a non-finite word is absent; n a multiple of 32 in
+    [32, 4096]); ``seeds`` (P, H, 12) float64 row-major ``[R | t]`` source -> target hypotheses, None = the identity: the seed with the
+    most correspondences within ``max_dist`` metres is refined ``iterations`` times.  Returns ``(pose (P, 12) float64, fit (P, 2)
+    float64: mean squared residual and overlap, info (P, 4) int32: best seed, correspondences, source rows, target rows, status (P,)
+    int32)``; EPC_STATUS_NO_PAIR: an index outside [0, C) -- the -1 of ``revisit_search`` -- or no finite seed; EPC_STATUS_NO_FIT: fewer
+    than ``min_pairs`` correspondences; both leave a NaN pose and fit.  Bit for bit tests/register_ref.py; only contiguous device tensors
+    of the exact dtype are taken, float32 seeds are refused, never converted; nothing is read back, the call is asynchronous and
+    capturable in a graph.  ``workspace``: a uint8 device tensor of at least ``epcnet_pair_register_workspace_bytes`` bytes to reuse
+    (what a captured graph needs), else one is allocated."""
+    L.require_gpu()
+    _pair_check("clouds", clouds, torch.float32, 3, None, 3)
+    dev = clouds.device
+    _pair_check("pairs", pairs, torch.int32, 2, dev, 2)
+    C, n, P = int(clouds.shape[0]), int(clouds.shape[1]), int(pairs.shape[0])
+    H = 1
+    if seeds is not None:
+        _pair_check("seeds", seeds, torch.float64, 3, dev, 12)
+        H = int(seeds.shape[1])
+        if int(seeds.shape[0]) != P:
+            raise L.EpcNetError(-1, "register_pairs: seeds must be (P, H, 12) for pairs (P, 2), got %s" % (tuple(seeds.shape),))
+    need = int(L.lib().epcnet_pair_register_workspace_bytes(P, H, n))
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(ws) or not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise L.EpcNetError(-1, "register_pairs: workspace must be a contiguous uint8 tensor on the ROCm device")
+    pose = torch.empty((P, 12), dtype=torch.float64, device=dev)
+    fit = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    info = torch.empty((P, 4), dtype=torch.int32, device=dev)
+    status = torch.empty((P,), dtype=torch.int32, device=dev)
+
+    def arg(t):          # an empty tensor has no address: the workspace's (aligned, not null) stands in and is never followed
+        return t if t.numel() else ws.data_ptr()
+    L.run.epcnet_pair_register(arg(clouds), C, n, arg(pairs), P, None if seeds is None else arg(seeds), H, float(max_dist), int(iterations),
+                               int(min_pairs), arg(pose), arg(fit), arg(info), arg(status), ws, ws.numel())
+    if workspace is None:
+        ws.record_stream(torch.cuda.current_stream(dev))
+    return pose, fit, info, status
+
+
+def yaw_seeds(num: int, base: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """``num`` hypotheses that differ by a turn about z: ``base @ Rz(2 pi m / num)``, m = 0 .. num - 1, as (..., num, 12) float64 for a
+    ``base`` (..., 12) float64 (None: the identity, on ``device``) -- a revisit driven in the other direction is seed num / 2.  Built
+    with torch in float64: outside the bit contract, like ``ops.travel_along``; ``register_pairs``' contract is seeds -> result."""
+    num = int(num)
+    if num < 1 or num > 64:
+        raise L.EpcNetError(-1, "yaw_seeds: 1 <= num <= 64")
+    if base is None:
+        base = torch.tensor([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=torch.float64, device=device)
+    if not torch.is_tensor(base) or base.dtype != torch.float64 or base.shape[-1] != 12:
+        raise L.EpcNetError(-1, "yaw_seeds: base must be a float64 tensor (..., 12)")
+    a = torch.arange(num, dtype=torch.float64, device=base.device) * (2.0 * np.pi / num)
+    c, s, o, l = torch.cos(a), torch.sin(a), torch.zeros_like(a), torch.ones_like(a)
+    c[0], s[0] = 1.0, 0.0                                                    # m = 0 is the base itself, to the bit
+    rz = torch.stack([c, -s, o, o, s, c, o, o, o, o, l, o, o, o, o, l], -1).reshape(num, 4, 4)
+    m = base.reshape(base.shape[:-1] + (3, 4))
+    return (m.unsqueeze(-3) @ rz).reshape(base.shape[:-1] + (num, 12)).contiguous()
+
+
+def verify_revisits(clouds: torch.Tensor, idx: torch.Tensor, sub_pose: Optional[torch.Tensor] = None, yaw: int = 1, **kw):
+    """``register_pairs`` on the candidates of ``revisit_search``: ``clouds`` (T, n, 3) float32 metric (``forward_trajectory(...,
+    clouds=True)``), ``idx`` (Q, k) int32 with Q <= T -- query i is cloud i -- -> the pairs (i, idx[i, j]), formed on the device.  With
+    ``sub_pose`` (T, 12) float64 every pair is seeded with the odometry's relative pose ``inv(sub_pose[idx[i, j]]) @ sub_pose[i]``, else
+    with the identity; ``yaw`` > 1 multiplies the seed by ``yaw_seeds(yaw)``.  Returns ``(pose (Q, k, 12), fit (Q, k, 2), info (Q, k, 4),
+    status (Q, k))``; a -1 of ``idx`` (and a NaN ``sub_pose``) is flagged EPC_STATUS_NO_PAIR.  No host read; ``kw`` goes to
+    ``register_pairs``."""
+    _pair_check("idx", idx, torch.int32, 2, clouds.device if torch.is_tensor(clouds) else None)
+    Q, k = int(idx.shape[0]), int(idx.shape[1])
+    dev = idx.device
+    if not torch.is_tensor(clouds) or clouds.dim() != 3 or Q > int(clouds.shape[0]) or (
+            sub_pose is not None and torch.is_tensor(sub_pose) and sub_pose.dim() == 2 and int(sub_pose.shape[0]) != int(clouds.shape[0])):
+        raise L.EpcNetError(-1, "verify_revisits: expected clouds (T, n, 3), idx (Q, k) with Q <= T and sub_pose (T, 12)")
+    src = torch.arange(Q, dtype=torch.int32, device=dev).unsqueeze(1).expand(Q, k)
+    pairs = torch.stack([src, idx], -1).reshape(Q * k, 2).contiguous()
+    seeds = None
+    if sub_pose is not None:
+        _pair_check("sub_pose", sub_pose, torch.float64, 2, dev, 12)
+        m = sub_pose.reshape(-1, 3, 4)
+        bottom = torch.tensor([0, 0, 0, 1], dtype=torch.float64, device=dev).expand(m.shape[0], 1, 4)
+        inv = torch.cat([m[:, :, :3].transpose(1, 2), -(m[:, :, :3].transpose(1, 2) @ m[:, :, 3:])], 2)
+        tgt = idx.reshape(-1).to(torch.int64).clamp(min=0, max=max(m.shape[0] - 1, 0))
+        rel = inv[tgt] @ torch.cat([m, bottom], 1)[src.reshape(-1).to(torch.int64)]          # (Q k, 3, 4)
+        seeds = yaw_seeds(yaw, rel.reshape(Q * k, 12))
+    elif int(yaw) != 1:
+        seeds = yaw_seeds(yaw, device=dev).unsqueeze(0).expand(Q * k, int(yaw), 12).contiguous()
+    pose, fit, info, status = register_pairs(clouds, pairs, seeds, **kw)
+    return pose.reshape(Q, k, 12), fit.reshape(Q, k, 2), info.reshape(Q, k, 4), status.reshape(Q, k)
 
 
 def recall_from_indices(indices: np.ndarray, database_output: np.ndarray, queries_output: np.ndarray,
