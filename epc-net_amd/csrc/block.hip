@@ -16,7 +16,9 @@
 // point on the lane) are directly the next layer's B operands.  The gather runs whole rows (f32: 16 lanes x float4,
 // 4 points per wave-instruction; fp16: 8 lanes x 16 B, 8 points), results go through a per-wave LDS staging tile to
 // switch between the row layout and the MFMA layout.
+#include <type_traits>
 #include "train_common.h"
+#include "../../include/epcnet_forms.h"
 
 #define BLK_WAVES 12  // f32 kernel: 12 x 8.7 KB staging tiles + the 49-KB weight pack = 154 KB (3 waves per SIMD)
 #define BLK_THREADS (64 * BLK_WAVES)
@@ -44,6 +46,13 @@ __device__ __forceinline__ void kahan_add(float& sum, float& comp, float v) {
     const float t = sum + y;
     comp = (t - sum) - y;
     sum = t;
+}
+
+// 16-byte store with the non-temporal hint: data this kernel's neighbours will not read again
+__device__ __forceinline__ void st4_stream(float* p, float4 v) {
+    typedef float f32x4_t __attribute__((ext_vector_type(4)));
+    const f32x4_t w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, reinterpret_cast<f32x4_t*>(p));
 }
 
 __device__ __forceinline__ void relu16(f32x16& a) {
@@ -172,7 +181,39 @@ __device__ __forceinline__ int list_entry(const void* lists, size_t slot, bool u
     return u16 ? (int)reinterpret_cast<const unsigned short*>(lists)[slot] : reinterpret_cast<const int32_t*>(lists)[slot];
 }
 
+// A point's first 20 list entries from its list row parked in LDS (the f32 kernel's tile prologue), as the row's words: ten
+// words of two 2-byte entries or twenty 4-byte entries.  The 16 lanes of a point read the same address (a broadcast).
+template <bool U16>
+struct Nb20Words {
+    unsigned int w[U16 ? EPC_KNN_SELECT / 2 : EPC_KNN_SELECT];
+    __device__ __forceinline__ void load(const float* row) {
+        static_assert(EPC_KNN_SELECT == 20, "five uint4 / two uint4 + one uint2 per row");
+        const uint4* r = reinterpret_cast<const uint4*>(row);
+        if (U16) {
+            const uint4 a = r[0], b = r[1];
+            const uint2 c = *reinterpret_cast<const uint2*>(row + 8);
+            w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w, w[8] = c.x, w[9] = c.y;
+        } else {
+#pragma unroll
+            for (int m4 = 0; m4 < EPC_KNN_SELECT / 4; ++m4) {
+                const uint4 t = r[m4];
+                w[4 * m4] = t.x, w[4 * m4 + 1] = t.y, w[4 * m4 + 2] = t.z, w[4 * m4 + 3] = t.w;
+            }
+        }
+    }
+    __device__ __forceinline__ int entry(int m) const {
+        return U16 ? (int)((m & 1) ? w[m >> 1] >> 16 : w[m >> 1] & 0xffffu) : (int)w[m];
+    }
+};
+
 // ---- f32 rows, scaled split-fp16 layers (EPC_PRECISION_F32 and EPC-Net-L; f32-equivalent at every stage boundary) ----
+// FORM 1 (what epc_proxyconv_block_fwd launches) feeds the gather from a tile prologue: the tile's 32 counts and its list
+// block arrive in coalesced wave loads, one round trip, and a tile whose 32 lists all hold exactly 20 entries (every tile of
+// an ordinary cloud) runs its eight passes in a straight line with no branch between them -- a pass is ONE global round
+// trip, its rows, where the per-pass lookups make four (count, list, rows, own row).  Tiles with ties or overflowing rows,
+// and FORM 0 (epcnet_block_fwd_form only), run the per-pass lookups.  Same sums in the same order: the forms agree
+// bit for bit (tests/test_gpu_block_feed.py).
+template <int FORM>
 __global__ __launch_bounds__(BLK_THREADS) void proxyconv_block_kernel(
     const float* __restrict__ x, const float* __restrict__ xyz, const void* __restrict__ idx, int idx_u16,
     const int32_t* __restrict__ cnt, const float* __restrict__ kth, int cap, const float* __restrict__ pack,
@@ -219,6 +260,9 @@ __global__ __launch_bounds__(BLK_THREADS) void proxyconv_block_kernel(
         const float q0 = a * rk;
         return __builtin_fmaf(__builtin_fmaf(-q0, kdiv, a), rk, q0);
     };
+    // FORM 1 reads a tile's list block as a whole (32 rows of `cap` slots); its extent is EPC_KNN_CAP's, another `cap` (the
+    // launch refuses it) takes the per-pass lookups
+    const bool cap_ok = cap == EPC_KNN_CAP;
   for (;;) {   // (no workgroup barriers inside)
     int t_draw = 0;
     if (lane == 0) t_draw = atomicAdd(&s_next_tile, 1);
@@ -234,6 +278,78 @@ __global__ __launch_bounds__(BLK_THREADS) void proxyconv_block_kernel(
 
     // ---- gather-mean, 4 points per pass ----
     float4 xm[8];
+    // Tile prologue: the 32 counts (lane & 31) and the first 2 KB of the list block -- all of it with 2-byte entries, the rows
+    // of points 0..15 with 4-byte entries -- in one round trip.
+    int c32 = 0;
+    uint4 l0 = make_uint4(0, 0, 0, 0), l1 = l0;
+    const uint4* lb = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(idx) +
+                                                     (size_t)tile * (32 * EPC_KNN_CAP) * (u16 ? 2 : 4));
+    if (FORM == 1 && cap_ok) {
+        c32 = cnt[g0 + (lane & 31)];
+        l0 = lb[lane];
+        l1 = lb[64 + lane];
+    }
+    // every list of the tile holds exactly its 20 entries: no tie tail, no overflowing row (one ballot covers both)
+    const bool fast = FORM == 1 && cap_ok && !__any(c32 > EPC_KNN_SELECT);
+    // Park each point's list in that point's own row of the staging tile: row j is written (t = xm - x) by pass j / 4, after
+    // that pass has read its lists -- LDS requests of one wave execute in order -- so the lists need no LDS of their own.
+    // (i = the uint4's index in the tile's list block, rb = bytes per list row)
+    auto park = [&](int i, const uint4& w, int rb) {
+        *reinterpret_cast<uint4*>(st + (16 * i / rb) * ST_STRIDE + (16 * i % rb) / 4) = w;
+    };
+    // The straight-line passes.  Pass s + 1's list words are read from LDS before pass s's sums, and v[m] is requested again
+    // right after it has been added; the own row is requested ahead of its pass's rows, so that waiting for row m never waits
+    // for anything younger than the rows behind it (requests retire in issue order).  The compiler regroups these requests
+    // into batches of its own; holding it to the written order was measured and is no faster.
+    auto fast_passes = [&](auto u16_c) {
+        constexpr bool U16 = decltype(u16_c)::value;
+        constexpr int rb = (U16 ? 2 : 4) * EPC_KNN_CAP;
+        uint4 l2 = l0, l3 = l0;
+        if (!U16) {   // 4-byte entries: the rows of points 16..31, first read in pass 3
+            l2 = lb[128 + lane];
+            l3 = lb[192 + lane];
+        }
+        park(lane, l0, rb);
+        park(64 + lane, l1, rb);
+        Nb20Words<U16> nb;
+        float4 v[EPC_KNN_SELECT];
+        nb.load(st + p * ST_STRIDE);
+        float4 own = row32(g0 + p - cloud_base);
+#pragma unroll
+        for (int m = 0; m < EPC_KNN_SELECT; ++m) v[m] = row32(nb.entry(m));
+        if (!U16) {
+            park(128 + lane, l2, rb);
+            park(192 + lane, l3, rb);
+        }
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            float4 own_n = own;
+            if (s < 7) {
+                nb.load(st + (4 * (s + 1) + p) * ST_STRIDE);
+                own_n = row32(g0 + 4 * (s + 1) + p - cloud_base);
+            }
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int m = 0; m < EPC_KNN_SELECT; ++m) {  // ascending j, one rounding per add
+                acc.x += v[m].x;
+                acc.y += v[m].y;
+                acc.z += v[m].z;
+                acc.w += v[m].w;
+                if (s < 7) v[m] = row32(nb.entry(m));
+            }
+            acc.x = div_k(acc.x), acc.y = div_k(acc.y), acc.z = div_k(acc.z), acc.w = div_k(acc.w);
+            xm[s] = acc;
+            st4(st + (4 * s + p) * ST_STRIDE + 4 * q,
+                make_float4(acc.x - own.x, acc.y - own.y, acc.z - own.z, acc.w - own.w));
+            own = own_n;
+        }
+    };
+    if (fast) {
+        if (u16)
+            fast_passes(std::true_type{});
+        else
+            fast_passes(std::false_type{});
+    } else {
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const int g = g0 + 4 * s + p;
@@ -293,6 +409,7 @@ __global__ __launch_bounds__(BLK_THREADS) void proxyconv_block_kernel(
         st4(st + (4 * s + p) * ST_STRIDE + 4 * q,
             make_float4(acc.x - xi4.x, acc.y - xi4.y, acc.z - xi4.z, acc.w - xi4.w));
     }
+    }
 
     // ---- conv_a, conv_b ----
     f16x8 bh[4], bl[4];
@@ -312,7 +429,9 @@ __global__ __launch_bounds__(BLK_THREADS) void proxyconv_block_kernel(
         float* row = st + (4 * s + p) * ST_STRIDE + 4 * q;
         const float4 t = ld4(row);
         const float4 o = make_float4(t.x + xm[s].x, t.y + xm[s].y, t.z + xm[s].z, t.w + xm[s].w);
-        st4(out + (size_t)(g0 + 4 * s + p) * out_stride + out_off + 4 * q, o);
+        // streaming store: the concat slice is next read by conv5, four launches on -- kept out of the L2's way, the lines stay
+        // with the rows the neighbouring tiles gather (x_next below is the next block's gather source and stays cached)
+        st4_stream(out + (size_t)(g0 + 4 * s + p) * out_stride + out_off + 4 * q, o);
         st4(row, o);
     }
     if (!has_next) continue;
@@ -584,11 +703,12 @@ extern "C" int epc_conv1_fwd(const float* xyz, const void* packed_conv1, int num
     return epc_conv1_launch(xyz, packed_conv1, num_points_total, x, x16, nullptr, 0, stream);
 }
 
-extern "C" int epc_proxyconv_block_fwd(const float* x, const void* x16, const float* xyz, const void* idx, int idx_u16,
-                                       const int32_t* cnt, const float* kth, int cap, const void* packed_block,
-                                       int has_next, int num_clouds, int n, int knn, float* out, void* out16,
-                                       int out_stride, int out_off, float* x_next, void* x_next16, int32_t* status,
-                                       void* stream) {
+// epc_proxyconv_block_fwd and epcnet_block_fwd_form (include/epcnet_forms.h): `form` is the f32 kernel's FORM (the fp16 kernel has one form)
+static int proxyconv_block_fwd_impl(const float* x, const void* x16, const float* xyz, const void* idx, int idx_u16,
+                                    const int32_t* cnt, const float* kth, int cap, const void* packed_block,
+                                    int has_next, int num_clouds, int n, int knn, float* out, void* out16,
+                                    int out_stride, int out_off, float* x_next, void* x_next16, int32_t* status,
+                                    int form, void* stream) {
     const bool f16 = x16 != nullptr;
     EPC_CHECK_ARG(xyz && idx && cnt && kth && packed_block, "null pointer");
     if (f16) {
@@ -605,8 +725,9 @@ extern "C" int epc_proxyconv_block_fwd(const float* x, const void* x16, const fl
     const long total = (long)num_clouds * n;
     EPC_CHECK_ARG(total < (1L << 31), "too many points");
     const size_t lds_bytes = f16 ? (size_t)BLK16_LDS_BYTES : BLK_LDS_FLOATS * sizeof(float);
+    const auto f32_kernel = form == 0 ? proxyconv_block_kernel<0> : proxyconv_block_kernel<1>;
     const void* fn = f16 ? reinterpret_cast<const void*>(proxyconv_block_f16_kernel)
-                         : reinterpret_cast<const void*>(proxyconv_block_kernel);
+                         : reinterpret_cast<const void*>(f32_kernel);
     EPC_SET_DYN_LDS(fn, lds_bytes);
     const int wpb = f16 ? BLK16_WAVES : BLK_WAVES;
     unsigned blocks = (unsigned)((total + wpb * 32 - 1) / (wpb * 32));
@@ -625,9 +746,29 @@ extern "C" int epc_proxyconv_block_fwd(const float* x, const void* x16, const fl
                            (int)total, n, (float)knn, (unsigned short*)out16, out_stride, out_off,
                            (unsigned short*)x_next16, status);
     else
-        hipLaunchKernelGGL(proxyconv_block_kernel, dim3(blocks), dim3(BLK_THREADS), lds_bytes, (hipStream_t)stream, x,
+        hipLaunchKernelGGL(f32_kernel, dim3(blocks), dim3(BLK_THREADS), lds_bytes, (hipStream_t)stream, x,
                            xyz, idx, idx_u16, cnt, kth, cap, (const float*)packed_block, has_next, (int)total, n, (float)knn,
                            out, out_stride, out_off, x_next);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
+}
+
+extern "C" int epc_proxyconv_block_fwd(const float* x, const void* x16, const float* xyz, const void* idx, int idx_u16,
+                                       const int32_t* cnt, const float* kth, int cap, const void* packed_block,
+                                       int has_next, int num_clouds, int n, int knn, float* out, void* out16,
+                                       int out_stride, int out_off, float* x_next, void* x_next16, int32_t* status,
+                                       void* stream) {
+    return proxyconv_block_fwd_impl(x, x16, xyz, idx, idx_u16, cnt, kth, cap, packed_block, has_next, num_clouds, n, knn, out,
+                                    out16, out_stride, out_off, x_next, x_next16, status, 1, stream);
+}
+
+// Test entry point: the f32 kernel in the form the caller names -- 0 = the per-pass lookups, 1 = the tile prologue (what
+// epc_proxyconv_block_fwd runs).  An explicit argument: the library reads no environment and holds no global state.
+extern "C" int epcnet_block_fwd_form(const float* x, const void* x16, const float* xyz, const void* idx, int idx_u16,
+                                     const int32_t* cnt, const float* kth, int cap, const void* packed_block, int has_next,
+                                     int num_clouds, int n, int knn, float* out, void* out16, int out_stride, int out_off,
+                                     float* x_next, void* x_next16, int32_t* status, int form, void* stream) {
+    EPC_CHECK_ARG(form == 0 || form == 1, "form 0 or 1");
+    return proxyconv_block_fwd_impl(x, x16, xyz, idx, idx_u16, cnt, kth, cap, packed_block, has_next, num_clouds, n, knn, out,
+                                    out16, out_stride, out_off, x_next, x_next16, status, form, stream);
 }

@@ -149,6 +149,18 @@ if (set(_pair_functions) & (set(_functions) | set(_pose_functions) | set(_scan_f
     raise ImportError("epcnet_pairs.h declares a name an earlier header declares")
 _constants.update(_pair_constants)
 PAIR_EXPORTS = list(_pair_functions)
+# the eighth header (test / tuning entries that name a kernel's form): read, bound and listed like the others
+FORMS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_forms.h")
+if not os.path.exists(FORMS_HEADER_PATH):
+    raise ImportError("%s is missing: the binding of the form entries is derived from it" % FORMS_HEADER_PATH)
+with open(FORMS_HEADER_PATH) as _f:
+    _form_functions, _form_constants, _ = parse_header(_f.read(), need_status=False)
+if (set(_form_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions) | set(_stamp_functions)
+                            | set(_revisit_functions) | set(_pair_functions))
+        or set(_form_constants) & set(_constants)):
+    raise ImportError("epcnet_forms.h declares a name an earlier header declares")
+_constants.update(_form_constants)
+FORM_EXPORTS = list(_form_functions)
 globals().update(_constants, **_status)     # EPC_OK, EPC_EINVAL, EPC_KNN_CAP, EPC_PRECISION_FAST, EPC_NUM_STAGES ... as module attributes
 # every symbol include/epcnet.h declares, in its order (tests check the library exports exactly these)
 EXPORTS = list(_functions)
@@ -199,7 +211,7 @@ _lib = ctypes.CDLL(LIB_PATH)
 _POINTERS = {"epc_cfg*": POINTER(EpcCfg), "epc_chain_fwd_args*": POINTER(ChainFwdArgs)}
 for _name, (_ret, _params, _) in (list(_functions.items()) + list(_pose_functions.items()) + list(_scan_functions.items())
                                   + list(_submap_functions.items()) + list(_stamp_functions.items()) + list(_revisit_functions.items())
-                                  + list(_pair_functions.items())):
+                                  + list(_pair_functions.items()) + list(_form_functions.items())):
     _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
     _fn.restype = c_char_p if _ret == "char*" else _REVISIT_SCALARS[_ret]
     _fn.argtypes = [_REVISIT_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
@@ -299,8 +311,8 @@ for _name, (_ret, _t, _pn) in _pose_functions.items():          # every entry of
     assert _ret == "int" and (_t[-1], _pn[-1]) == ("void*", "stream"), "%s does not take a stream last and return a status" % _name
     setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))
 for _name, (_ret, _t, _pn) in (list(_scan_functions.items()) + list(_submap_functions.items()) + list(_stamp_functions.items())
-                               + list(_revisit_functions.items()) + list(_pair_functions.items())):
-    # include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h and include/epcnet_pairs.h: the
+                               + list(_revisit_functions.items()) + list(_pair_functions.items()) + list(_form_functions.items())):
+    # include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h, include/epcnet_pairs.h and include/epcnet_forms.h: the
     # entries that take a stream launch
     if _t and (_t[-1], _pn[-1]) == ("void*", "stream"):
         assert _ret == "int", "%s takes a stream and does not return a status" % _name
