@@ -28,7 +28,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "epcnet.h")
 
 _SCALARS = {"int": c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "float": c_float,
             "size_t": ctypes.c_size_t, "int32_t": c_int32, "uint32_t": ctypes.c_uint32}
-# what include/epcnet_revisits.h and include/epcnet_pairs.h pass by value besides: the reader of every other header goes on refusing a
+# what include/epcnet_revisits.h, include/epcnet_pairs.h and include/epcnet_trajectory.h pass by value besides: the reader of every other header goes on refusing a
 # `double` parameter
 _REVISIT_SCALARS = dict(_SCALARS, double=ctypes.c_double)
 # the dtype a tensor must have where the header declares a typed pointee (``run``); any dtype goes at every other pointer
@@ -37,7 +37,7 @@ _POINTEES = {"float*": torch.float32, "double*": torch.float64, "int32_t*": torc
 
 def parse_header(text: str, need_status: bool = True, scalars=_SCALARS):
     """``(functions, constants, status)`` of the text of include/epcnet.h (or, with ``need_status=False``, of a further header in the
-    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h, include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h, include/epcnet_pairs.h): ``functions[name] = (return type, [parameter
+    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h, include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h, include/epcnet_pairs.h, include/epcnet_trajectory.h): ``functions[name] = (return type, [parameter
     types], [parameter names])`` in header order, the types as C type names without ``const`` and spaces around ``*`` -- a key
     of ``scalars``, or any type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME>
     <integer>``; ``status``: the members of ``enum epc_status``.  Raises ValueError on whatever it does not understand."""
@@ -149,6 +149,19 @@ if (set(_pair_functions) & (set(_functions) | set(_pose_functions) | set(_scan_f
     raise ImportError("epcnet_pairs.h declares a name an earlier header declares")
 _constants.update(_pair_constants)
 PAIR_EXPORTS = list(_pair_functions)
+# the ninth header (loop closing: the relaxation of a trajectory's pose graph): read, bound and listed like the seventh, with the scalars
+# that allow a `double` by value (the odometry weights); its status bit joins the EPC_* constants
+TRAJECTORY_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_trajectory.h")
+if not os.path.exists(TRAJECTORY_HEADER_PATH):
+    raise ImportError("%s is missing: the binding of the trajectory entries is derived from it" % TRAJECTORY_HEADER_PATH)
+with open(TRAJECTORY_HEADER_PATH) as _f:
+    _trajectory_functions, _trajectory_constants, _ = parse_header(_f.read(), need_status=False, scalars=_REVISIT_SCALARS)
+if (set(_trajectory_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions)
+                                  | set(_stamp_functions) | set(_revisit_functions) | set(_pair_functions))
+        or set(_trajectory_constants) & set(_constants)):
+    raise ImportError("epcnet_trajectory.h declares a name an earlier header declares")
+_constants.update(_trajectory_constants)
+TRAJECTORY_EXPORTS = list(_trajectory_functions)
 # the eighth header (test / tuning entries that name a kernel's form): read, bound and listed like the others
 FORMS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_forms.h")
 if not os.path.exists(FORMS_HEADER_PATH):
@@ -156,7 +169,7 @@ if not os.path.exists(FORMS_HEADER_PATH):
 with open(FORMS_HEADER_PATH) as _f:
     _form_functions, _form_constants, _ = parse_header(_f.read(), need_status=False)
 if (set(_form_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions) | set(_stamp_functions)
-                            | set(_revisit_functions) | set(_pair_functions))
+                            | set(_revisit_functions) | set(_pair_functions) | set(_trajectory_functions))
         or set(_form_constants) & set(_constants)):
     raise ImportError("epcnet_forms.h declares a name an earlier header declares")
 _constants.update(_form_constants)
@@ -211,7 +224,7 @@ _lib = ctypes.CDLL(LIB_PATH)
 _POINTERS = {"epc_cfg*": POINTER(EpcCfg), "epc_chain_fwd_args*": POINTER(ChainFwdArgs)}
 for _name, (_ret, _params, _) in (list(_functions.items()) + list(_pose_functions.items()) + list(_scan_functions.items())
                                   + list(_submap_functions.items()) + list(_stamp_functions.items()) + list(_revisit_functions.items())
-                                  + list(_pair_functions.items()) + list(_form_functions.items())):
+                                  + list(_pair_functions.items()) + list(_trajectory_functions.items()) + list(_form_functions.items())):
     _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
     _fn.restype = c_char_p if _ret == "char*" else _REVISIT_SCALARS[_ret]
     _fn.argtypes = [_REVISIT_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
@@ -311,8 +324,10 @@ for _name, (_ret, _t, _pn) in _pose_functions.items():          # every entry of
     assert _ret == "int" and (_t[-1], _pn[-1]) == ("void*", "stream"), "%s does not take a stream last and return a status" % _name
     setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))
 for _name, (_ret, _t, _pn) in (list(_scan_functions.items()) + list(_submap_functions.items()) + list(_stamp_functions.items())
-                               + list(_revisit_functions.items()) + list(_pair_functions.items()) + list(_form_functions.items())):
-    # include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h, include/epcnet_pairs.h and include/epcnet_forms.h: the
+                               + list(_revisit_functions.items()) + list(_pair_functions.items()) + list(_trajectory_functions.items())
+                               + list(_form_functions.items())):
+    # include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h, include/epcnet_pairs.h,
+    # include/epcnet_trajectory.h and include/epcnet_forms.h: the
     # entries that take a stream launch
     if _t and (_t[-1], _pn[-1]) == ("void*", "stream"):
         assert _ret == "int", "%s takes a stream and does not return a status" % _name

@@ -331,6 +331,87 @@ def verify_revisits(clouds: torch.Tensor, idx: torch.Tensor, sub_pose: Optional[
     return pose.reshape(Q, k, 12), fit.reshape(Q, k, 2), info.reshape(Q, k, 4), status.reshape(Q, k)
 
 
+def _relax_check(name: str, t, dtype, ndim: int, device=None, last=None):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise L.EpcNetError(-1, "relax_trajectory: %s must live on a ROCm device (no CPU fallback)" % name)
+    if t.dtype != dtype or not t.is_contiguous():
+        raise L.EpcNetError(-1, "relax_trajectory: %s must be a contiguous %s tensor, got %s%s" % (
+            name, dtype, t.dtype, " (poses are float64: they are refused, never converted)" if dtype == torch.float64 else ""))
+    if t.dim() != ndim or (last is not None and int(t.shape[-1]) != last) or (device is not None and t.device != device):
+        raise L.EpcNetError(-1, "relax_trajectory: %s must be %d-d%s on the poses' device, got %s" % (
+            name, ndim, "" if last is None else " with a last dimension of %d" % last, tuple(t.shape)))
+
+
+def relax_trajectory(poses: torch.Tensor, pairs: torch.Tensor, rel: torch.Tensor, weights: torch.Tensor,
+                     odo_weights: Tuple[float, float] = (1.0, 100.0), iterations: int = 4, cg_iterations: int = 64,
+                     workspace: Optional[torch.Tensor] = None):
+    """Loop closing (include/epcnet_trajectory.h): relaxes the pose graph of one trajectory -- the chain of odometry edges between
+    consecutive rows of ``poses`` (T, 12) float64 ``[R | t]`` (``sub_pose``; the rows from the first non-finite one on are the NaN slots
+    behind its end) plus the loops ``pairs`` (L, 2) int32 (source, target) with ``rel`` (L, 12) float64 source -> target (what
+    ``register_pairs`` returns) and ``weights`` (L, 2) float64 (w_t, w_r) -- by ``iterations`` Gauss-Newton steps of ``cg_iterations``
+    preconditioned CG iterations each, in chain-increment variables.  ``odo_weights``: (w_t, w_r) of every odometry edge.  Returns
+    ``(poses_out (T, 12) float64, cost (iterations + 1,) float64, loop_chi2 (L,) float64, loop_status (L,) int32: 0 or
+    EPC_STATUS_NO_EDGE, num_out (2,) int32: T_eff and the loops used)``; a loop with an index outside the trajectory (the -1 of
+    ``revisit_search``), a NaN ``rel`` (a flagged pair) or two zero weights is skipped; with no loop used the poses come back bit for
+    bit.  Bit for bit tests/relax_ref.py; only contiguous device tensors of the exact dtype are taken, float32 poses are refused, never
+    converted; nothing is read back, the call is asynchronous and capturable in a graph.  ``workspace``: a uint8 device tensor of at
+    least ``epcnet_trajectory_relax_workspace_bytes`` bytes to reuse (what a captured graph needs), else one is allocated."""
+    L.require_gpu()
+    _relax_check("poses", poses, torch.float64, 2, None, 12)
+    dev = poses.device
+    _relax_check("pairs", pairs, torch.int32, 2, dev, 2)
+    _relax_check("rel", rel, torch.float64, 2, dev, 12)
+    _relax_check("weights", weights, torch.float64, 2, dev, 2)
+    T, nl = int(poses.shape[0]), int(pairs.shape[0])
+    if int(rel.shape[0]) != nl or int(weights.shape[0]) != nl:
+        raise L.EpcNetError(-1, "relax_trajectory: rel must be (L, 12) and weights (L, 2) for pairs (L, 2), got %s and %s" % (
+            tuple(rel.shape), tuple(weights.shape)))
+    need = int(L.lib().epcnet_trajectory_relax_workspace_bytes(T, nl))
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(ws) or not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise L.EpcNetError(-1, "relax_trajectory: workspace must be a contiguous uint8 tensor on the ROCm device")
+    iterations = int(iterations)
+    poses_out = torch.empty((T, 12), dtype=torch.float64, device=dev)
+    cost = torch.empty((max(iterations, 0) + 1,), dtype=torch.float64, device=dev)
+    chi2 = torch.empty((nl,), dtype=torch.float64, device=dev)
+    status = torch.empty((nl,), dtype=torch.int32, device=dev)
+    num_out = torch.empty((2,), dtype=torch.int32, device=dev)
+
+    def arg(t):          # an empty tensor has no address: the workspace's (aligned, not null) stands in and is never followed
+        return t if t.numel() else ws.data_ptr()
+    L.run.epcnet_trajectory_relax(arg(poses), T, arg(pairs), arg(rel), arg(weights), nl, float(odo_weights[0]), float(odo_weights[1]),
+                                  iterations, int(cg_iterations), arg(poses_out), cost, arg(chi2), arg(status), num_out, ws, ws.numel())
+    if workspace is None:
+        ws.record_stream(torch.cuda.current_stream(dev))
+    return poses_out, cost, chi2, status, num_out
+
+
+def close_loops(sub_pose: torch.Tensor, idx: torch.Tensor, pose: torch.Tensor, fit: torch.Tensor, st: torch.Tensor,
+                min_overlap: float = 0.6, max_msr: float = 0.05, loop_weights: Tuple[float, float] = (1.0, 100.0), **kw):
+    """``relax_trajectory`` on what ``verify_revisits`` returned: ``sub_pose`` (T, 12) float64, ``idx`` (Q, k) int32 the candidates of
+    ``revisit_search``, ``pose`` (Q, k, 12), ``fit`` (Q, k, 2) and ``st`` (Q, k) the registration's results.  Query i is the SOURCE of
+    its loops and ``idx[i, j]`` the target; a loop's weights are ``loop_weights`` where the pair is unflagged, its overlap ``fit[..., 1]``
+    is at least ``min_overlap`` and its mean squared residual ``fit[..., 0]`` at most ``max_msr``, else (0, 0), which the relaxation
+    skips.  Formed with torch on the device, outside the bit contract; no host read; ``kw`` goes to ``relax_trajectory``, whose
+    result is returned (the loops in the row-major order of ``idx``)."""
+    _relax_check("idx", idx, torch.int32, 2, sub_pose.device if torch.is_tensor(sub_pose) else None)
+    Q, k = int(idx.shape[0]), int(idx.shape[1])
+    dev = idx.device
+    _relax_check("pose", pose, torch.float64, 3, dev, 12)
+    _relax_check("fit", fit, torch.float64, 3, dev, 2)
+    _relax_check("st", st, torch.int32, 2, dev)
+    if tuple(pose.shape[:2]) != (Q, k) or tuple(fit.shape[:2]) != (Q, k) or tuple(st.shape) != (Q, k):
+        raise L.EpcNetError(-1, "close_loops: expected idx (Q, k), pose (Q, k, 12), fit (Q, k, 2) and st (Q, k)")
+    src = torch.arange(Q, dtype=torch.int32, device=dev).unsqueeze(1).expand(Q, k)
+    pairs = torch.stack([src, idx], -1).reshape(Q * k, 2).contiguous()
+    good = (st == 0) & (fit[..., 1] >= float(min_overlap)) & (fit[..., 0] <= float(max_msr))
+    w = torch.tensor([float(loop_weights[0]), float(loop_weights[1])], dtype=torch.float64, device=dev)
+    weights = (good.reshape(Q * k, 1).to(torch.float64) * w.reshape(1, 2)).contiguous()
+    return relax_trajectory(sub_pose, pairs, pose.reshape(Q * k, 12), weights, **kw)
+
+
 def recall_from_indices(indices: np.ndarray, database_output: np.ndarray, queries_output: np.ndarray,
                         true_neighbors: Sequence[Sequence[int]], num_neighbors: int = NUM_NEIGHBORS):
     """The bookkeeping of evaluate.py:467-537 given each query's sorted neighbour indices -- the reference's per-query Python
