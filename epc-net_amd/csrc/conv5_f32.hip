@@ -48,6 +48,17 @@
 //    aligned to chunk 0 need a 64-interval period, i.e. ONE computing wave per SIMD at a time: at best -6 %.
 //  What the stamps leave (per wave, 212k cycles per tile): prologue 18 %, chain 27 %, epilogue 31 % (1 900 cycles per chunk
 //  beside the partner's chain: a 16x16x32 MFMA blocks the SIMD's vector issue for 8 of its 16 cycles), barrier 12 %.
+//  Round 9 (profiles/r09_conv5_stream_ablations.txt; the kernel's average inside the 64 x 4096 step, two alternating profiled
+//  runs each way) went after the barrier and issue shares without touching the schedule.  Kept (form 1 below): the streaming
+//  hints on the outputs (425.7 -> 421.2 us) and on the cat rows (this kernel +2 us, but the aggregate behind it 156 -> 140.5 us:
+//  more of feat is still in the Infinity Cache when it is read), the epilogue diet (429.2 -> 421.2 us).  Dropped:
+//  * a wave's four W5 pieces dealt contiguously (piece = 4 wave + u), ONE M0 save / restore per chunk, the four pieces by
+//    immediate offsets, scalar source increments: 422.1 vs 421.2 us -- the 5 % "DMA issue" is not the M0 traffic;
+//  * s_setprio 1 for waves 4-7 before the chunk loop: 447 vs 421 us -- the late waves' epilogue then starves the early waves'
+//    MFMA issue, and the chunk barrier charges everyone;
+//  * not built, an L2 warm-ahead of chunk c + 2: every chunk streaming chunk 0's bytes (an L2-resident W5, the upper bound)
+//    moves the kernel by 9 of 476 us alone and by 5 us with the hints in; the kernel's L2 misses (9.1 M lines = 1.16 GB) are its
+//    compulsory cat + feat traffic, the W5 stream already hits.  Without the feat stores the kernel runs 55 us shorter.
 //
 // Tile algebra.  A 32-channel x 32-point chunk tile is 2 x 2 tiles of 16 x 16, a k-step is 32 input channels.
 //   fragment of lane l (q = l >> 4, li = l & 15) for k-step s:  8 consecutive k = 32 s + 8 q + 0..7 of row / column li
@@ -66,6 +77,7 @@
 // cluster weights are packed in that k order (pack.hip pack_wc_bf16x2_kernel).
 #include <type_traits>
 #include "train_common.h"
+#include "../../include/epcnet_forms.h"
 
 #define C5_THREADS 512
 #define C5_WAVES 8
@@ -101,7 +113,7 @@ struct C5fLds {  // VLAD kernel; offsets in floats (4 B)
 // raw values are split IN PLACE into their hi and lo fragment registers -- the raw row and the fragments never coexist.
 // A macro on purpose: as a function taking xh / xl by reference hipcc 7.2 keeps the raw rows and the fragments in separate
 // registers (256 VGPRs + 39 spilled instead of 242).  Declares xh, xl, inv_row in the caller's scope.
-#define C5_LOAD_ROWS_SPLIT_N(NP_, CIN_, cat_, g0_, active_, li_, q_)                                                                    \
+#define C5_LOAD_ROWS_SPLIT_N(NP_, CIN_, cat_, g0_, active_, li_, q_, LD4_)                                                              \
     f16x8 xh[NP_][(CIN_) / 32], xl[NP_][(CIN_) / 32];                                                                                \
     float inv_row[NP_];                                                                                                           \
     {                                                                                                                            \
@@ -109,8 +121,8 @@ struct C5fLds {  // VLAD kernel; offsets in floats (4 B)
         _Pragma("unroll") for (int p = 0; p < (NP_); ++p) {                                                                          \
             const float* row = (cat_) + (size_t)((active_) ? (g0_) + 16 * p + (li_) : 0) * (CIN_) + 8 * (q_);                    \
             _Pragma("unroll") for (int s = 0; s < (CIN_) / 32; ++s) {                                                            \
-                const float4 a = (active_) ? ld4(row + 32 * s) : make_float4(0.f, 0.f, 0.f, 0.f);                                \
-                const float4 b = (active_) ? ld4(row + 32 * s + 4) : make_float4(0.f, 0.f, 0.f, 0.f);                            \
+                const float4 a = (active_) ? LD4_(row + 32 * s) : make_float4(0.f, 0.f, 0.f, 0.f);                               \
+                const float4 b = (active_) ? LD4_(row + 32 * s + 4) : make_float4(0.f, 0.f, 0.f, 0.f);                           \
                 raw[p][s][0] = a.x, raw[p][s][1] = a.y, raw[p][s][2] = a.z, raw[p][s][3] = a.w;                                  \
                 raw[p][s][4] = b.x, raw[p][s][5] = b.y, raw[p][s][6] = b.z, raw[p][s][7] = b.w;                                  \
             }                                                                                                                    \
@@ -126,15 +138,53 @@ struct C5fLds {  // VLAD kernel; offsets in floats (4 B)
             _Pragma("unroll") for (int s = 0; s < (CIN_) / 32; ++s) split8_f16s(raw[p][s], row_s, xh[p][s], xl[p][s]);           \
         }                                                                                                                        \
     }
-#define C5_LOAD_ROWS_SPLIT(CIN_, cat_, g0_, active_, li_, q_) C5_LOAD_ROWS_SPLIT_N(2, CIN_, cat_, g0_, active_, li_, q_)
+#define C5_LOAD_ROWS_SPLIT(CIN_, cat_, g0_, active_, li_, q_, LD4_) C5_LOAD_ROWS_SPLIT_N(2, CIN_, cat_, g0_, active_, li_, q_, LD4_)
 
+// The VLAD kernel has two FORMS (epcnet_conv5_assign_f32_fwd_form, include/epcnet_forms.h): 0 = as it stood, 1 = what ships.  Form 1
+// leaves every output bit as it was (tests/test_gpu_conv5_forms.py) and differs in
+//  * the outputs -- every byte written once and read by the NEXT launch -- stored, and the cat rows -- every byte read once --
+//    loaded with the non-temporal hint;
+//  * the epilogue's vector work: the bf16 split through PACKED conversions, the bias and inverse-scale reads from one base with
+//    immediate offsets, the feat store address from a wave-uniform tile base.
+__device__ __forceinline__ float4 ld4_nt(const float* p) {
+    const f32x4v v = __builtin_nontemporal_load(reinterpret_cast<const f32x4v*>(p));
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+template <bool NT>
+__device__ __forceinline__ void st_u32x4(float* p, u32x4 v) {
+    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
+    else *reinterpret_cast<u32x4*>(p) = v;
+}
+template <bool NT>
+__device__ __forceinline__ void st_f32(float* p, float v) {
+    if constexpr (NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+// split8 (common.h) with the conversions in PAIRS: v_cvt_pk_bf16_f32 rounds two values into one dword, whose halves expanded by
+// shift / mask are the hi parts as floats -- the same instruction and the same subtraction as split8's, so the same bits.
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned int cvt_pk_bf16(float a, float b) {
+    return __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2v{a, b}, bf16x2v));
+}
+__device__ __forceinline__ void split8_pk(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
+    u32x4 h, l;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        h[j] = cvt_pk_bf16(v[2 * j], v[2 * j + 1]);
+        l[j] = cvt_pk_bf16(v[2 * j] - __uint_as_float(h[j] << 16), v[2 * j + 1] - __uint_as_float(h[j] & 0xffff0000u));
+    }
+    hi = __builtin_bit_cast(bf16x8, h);
+    lo = __builtin_bit_cast(bf16x8, l);
+}
 // packed conv5 stage (4-byte units): [W5p CIN*1024][b5f 1024][Wcp 1024*64][cbn_s 64][cbn_t 64][tinv 1024]
-template <int CIN>
-__global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float* __restrict__ cat, const float* __restrict__ pack,
-                                                                    int total_points, float* __restrict__ feat,
-                                                                    float* __restrict__ rnorm, float* __restrict__ assign,
-                                                                    float* __restrict__ assign_frag, float* __restrict__ apart) {
+template <int CIN, int FORM>
+__device__ __forceinline__ void conv5_vlad_f32_body(const float* __restrict__ cat, const float* __restrict__ pack,
+                                                    int total_points, float* __restrict__ feat,
+                                                    float* __restrict__ rnorm, float* __restrict__ assign,
+                                                    float* __restrict__ assign_frag, float* __restrict__ apart) {
     using L = C5fLds<CIN>;
+    constexpr bool NT = FORM == 1;   // the streaming hints
     constexpr int STEPS = CIN / 32;
     static_assert(C5_WAVES * L::T_WAVE <= 2 * L::W5_CHUNK, "the transpose tiles must fit in the W5 buffers");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -175,7 +225,9 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
     const int g0 = (blockIdx.x * C5_WAVES + wave) * 32;
     const bool active = g0 < total_points;
 
-    C5_LOAD_ROWS_SPLIT(CIN, cat, g0, active, li, q)
+#define C5_LD4_CAT(p_) (NT ? ld4_nt(p_) : ld4(p_))
+    C5_LOAD_ROWS_SPLIT(CIN, cat, g0, active, li, q, C5_LD4_CAT)
+#undef C5_LD4_CAT
 
     f32x4v P[4][2];   // logits^T, P[cg][p][r] = cluster 16 cg + 4 q + r, point 16 p + li
 #pragma unroll
@@ -219,11 +271,27 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
     // The epilogue of a chunk in two parts: epi_valu = VALU + stores (un-scale, ReLU, |feat|^2, feat stores, the bf16 split of
     // the accumulators into fh / fl); assign_mfma = the chunk's 24 assignment MFMAs.
     bf16x8 fh[2], fl[2];
+    // Form 1: the bias and inverse-scale tables are adjacent (OFF_TI = OFF_B5 + 1024), so one lane base + 32 c reaches the chunk's
+    // four reads by immediate offsets (compiled: one v_add and four ds_read_b128 with offsets 0, 64, 4096, 4160 where form 0 has
+    // four adds); the tile's feat base is wave-uniform, the lane's share a constant offset.
+    static_assert(L::OFF_TI == L::OFF_B5 + 1024, "one base serves both tables");
+    typedef const __attribute__((address_space(3))) f32x4v* lds_f32x4_ptr;
+    lds_f32x4_ptr tab = (lds_f32x4_ptr)(lds + L::OFF_B5 + 4 * q);
+    // opaque: hipcc otherwise folds OFF_B5 (past the 16-bit ds offset) back into the per-chunk address, four adds again
+    if constexpr (FORM == 1) asm volatile("" : "+v"(tab));
+    const int tile_u = __builtin_amdgcn_readfirstlane(g0 >> 5);
+    float* feat_tile = feat + (size_t)tile_u * (32 * 768);
     auto epi_valu = [&](int c) {
         // ---- epilogue: out = relu(acc * (inverse row scale * inverse column scale) + bias) ----
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-            const float4 bv = ld4(lds + L::OFF_B5 + 32 * c + 16 * g + 4 * q), tv = ld4(lds + L::OFF_TI + 32 * c + 16 * g + 4 * q);
+            float4 bv, tv;
+            if constexpr (FORM == 1) {
+                const f32x4v b_ = tab[8 * c + 4 * g], t_ = tab[8 * c + 256 + 4 * g];
+                bv = make_float4(b_[0], b_[1], b_[2], b_[3]), tv = make_float4(t_[0], t_[1], t_[2], t_[3]);
+            } else {
+                bv = ld4(lds + L::OFF_B5 + 32 * c + 16 * g + 4 * q), tv = ld4(lds + L::OFF_TI + 32 * c + 16 * g + 4 * q);
+            }
             const float b4[4] = {bv.x, bv.y, bv.z, bv.w}, t4[4] = {tv.x, tv.y, tv.z, tv.w};
 #pragma unroll
             for (int p = 0; p < 2; ++p)
@@ -250,10 +318,10 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
                 w[3 * t + 1] = __builtin_amdgcn_perm(cc, b, 0x06050302u);   // b.b2 b.b3 c.b1 c.b2
                 w[3 * t + 2] = __builtin_amdgcn_perm(d, cc, 0x07060503u);   // c.b3 d.b1 d.b2 d.b3
             }
-            float* fdst = feat + ((size_t)(g0 >> 5) * 32 + c) * 768 + lane * 4;
+            float* fdst = FORM == 1 ? feat_tile + c * 768 + lane_off / 4 : feat + ((size_t)(g0 >> 5) * 32 + c) * 768 + lane * 4;
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc)
-                *reinterpret_cast<u32x4*>(fdst + pc * 256) = u32x4{w[4 * pc], w[4 * pc + 1], w[4 * pc + 2], w[4 * pc + 3]};
+                st_u32x4<NT>(fdst + pc * 256, u32x4{w[4 * pc], w[4 * pc + 1], w[4 * pc + 2], w[4 * pc + 3]});
         }
         // assignment GEMM share of this chunk: P^T (64 clusters x 32 points) += Wc^T (64 x 32 ch) feat^T (32 ch x 32 points);
         // (feat * rn) @ Wc == (feat @ Wc) * rn, so it runs while the norm is still accumulating.  B operand of point group p:
@@ -262,7 +330,8 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
         for (int p = 0; p < 2; ++p) {
             const float v[8] = {acc[0][p][0], acc[0][p][1], acc[0][p][2], acc[0][p][3],
                                 acc[1][p][0], acc[1][p][1], acc[1][p][2], acc[1][p][3]};
-            split8(v, fh[p], fl[p]);
+            if constexpr (FORM == 1) split8_pk(v, fh[p], fl[p]);
+            else split8(v, fh[p], fl[p]);
         }
     };
     auto assign_mfma = [&](int c) {
@@ -365,13 +434,13 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
                 float* arow = assign + (size_t)(g0 + 16 * p + li) * 64 + 4 * q;
 #pragma unroll
                 for (int cg = 0; cg < 4; ++cg)
-                    st4(arow + 16 * cg, make_float4(P[cg][p][0] / inv_sum[p], P[cg][p][1] / inv_sum[p], P[cg][p][2] / inv_sum[p],
-                                                    P[cg][p][3] / inv_sum[p]));
+                    st_u32x4<NT>(arow + 16 * cg, __builtin_bit_cast(u32x4, f32x4v{P[cg][p][0] / inv_sum[p], P[cg][p][1] / inv_sum[p],
+                                                                                     P[cg][p][2] / inv_sum[p], P[cg][p][3] / inv_sum[p]}));
             }
         }
         if (q == 0) {
-            rnorm[g0 + li] = rn[0];
-            rnorm[g0 + 16 + li] = rn[1];
+            st_f32<NT>(rnorm + g0 + li, rn[0]);
+            st_f32<NT>(rnorm + g0 + 16 + li, rn[1]);
         }
         // the assignments as bf16 hi + lo B fragments of the aggregate GEMM (cluster -> lane, 8 consecutive points -> fragment:
         // [tile][cluster tile t][k-step][part][lane][8], a[32 g + 16 ks + 8 (l >> 5) + e][32 t + (l & 31)]) and the tile's partial
@@ -397,17 +466,34 @@ __global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float*
 #pragma unroll
                 for (int e = 0; e < 8; ++e) s_ += v[e];
                 bf16x8 ah, al;
-                split8(v, ah, al);
-                *reinterpret_cast<u32x4*>(fdst + ((t * 2 + ks) * 2 + 0) * 256) = __builtin_bit_cast(u32x4, ah);
-                *reinterpret_cast<u32x4*>(fdst + ((t * 2 + ks) * 2 + 1) * 256) = __builtin_bit_cast(u32x4, al);
+                if constexpr (FORM == 1) split8_pk(v, ah, al);
+                else split8(v, ah, al);
+                st_u32x4<NT>(fdst + ((t * 2 + ks) * 2 + 0) * 256, __builtin_bit_cast(u32x4, ah));
+                st_u32x4<NT>(fdst + ((t * 2 + ks) * 2 + 1) * 256, __builtin_bit_cast(u32x4, al));
             }
             asum[t] = s_ + __shfl_xor(s_, 32);
         }
         if (h == 0) {
-            apart[(size_t)(g0 >> 5) * 64 + j] = asum[0];
-            apart[(size_t)(g0 >> 5) * 64 + 32 + j] = asum[1];
+            st_f32<NT>(apart + (size_t)(g0 >> 5) * 64 + j, asum[0]);
+            st_f32<NT>(apart + (size_t)(g0 >> 5) * 64 + 32 + j, asum[1]);
         }
     }
+}
+
+// The shipped form keeps the name conv5_vlad_f32_kernel: bench.py finds the kernel's counters by it.
+template <int CIN>
+__global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_kernel(const float* __restrict__ cat, const float* __restrict__ pack,
+                                                                    int total_points, float* __restrict__ feat,
+                                                                    float* __restrict__ rnorm, float* __restrict__ assign,
+                                                                    float* __restrict__ assign_frag, float* __restrict__ apart) {
+    conv5_vlad_f32_body<CIN, 1>(cat, pack, total_points, feat, rnorm, assign, assign_frag, apart);
+}
+template <int CIN>
+__global__ __launch_bounds__(C5_THREADS) void conv5_vlad_f32_form0_kernel(const float* __restrict__ cat, const float* __restrict__ pack,
+                                                                          int total_points, float* __restrict__ feat,
+                                                                          float* __restrict__ rnorm, float* __restrict__ assign,
+                                                                          float* __restrict__ assign_frag, float* __restrict__ apart) {
+    conv5_vlad_f32_body<CIN, 0>(cat, pack, total_points, feat, rnorm, assign, assign_frag, apart);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -469,7 +555,7 @@ __global__ __launch_bounds__(C5M_THREADS, 4) void conv5_max_f32_kernel(const flo
     const int g0 = (blockIdx.x * C5M_WAVES + wave) * 32;
     const bool active = g0 < total_points;
     const bool wg_one_cloud = n % (C5M_WAVES * 32) == 0;               // the workgroup's four tiles share a cloud
-    C5_LOAD_ROWS_SPLIT(CIN, cat, g0, active, li, q)
+    C5_LOAD_ROWS_SPLIT(CIN, cat, g0, active, li, q, ld4)
     // register r of acc[p] belongs to point 16 p + 4 q + r, whose inverse row scale lives in the lane that loaded that point:
     // through a wave-private LDS row, read back once
     if (q == 0) {
@@ -561,20 +647,35 @@ __global__ __launch_bounds__(C5M_THREADS, 4) void conv5_max_f32_kernel(const flo
     }
 }
 
-extern "C" int epc_conv5_assign_f32_fwd(const float* cat, int cin, const void* packed_conv5, int num_points_total,
-                                        void* feat_frag, float* rnorm, float* assign, void* assign_frag, float* apart,
-                                        void* stream) {
+// epc_conv5_assign_f32_fwd and epcnet_conv5_assign_f32_fwd_form (include/epcnet_forms.h): form 0 = the parent form, 1 = the shipped one
+static int conv5_assign_f32_fwd_impl(const float* cat, int cin, const void* packed_conv5, int num_points_total, void* feat_frag,
+                                     float* rnorm, float* assign, void* assign_frag, float* apart, int form, void* stream) {
     EPC_CHECK_ARG(cat && packed_conv5 && feat_frag && rnorm && assign_frag && apart, "null pointer");
     EPC_CHECK_ARG(cin == 256, "EPC-Net conv5 takes the 256-channel concat (models/epc-net.py:134)");
     EPC_CHECK_ARG(num_points_total >= 0 && num_points_total % 32 == 0, "point count must be a multiple of 32");
     if (num_points_total == 0) return EPC_OK;
     const size_t lds_bytes = C5fLds<256>::TOTAL * sizeof(float);
-    EPC_SET_DYN_LDS(conv5_vlad_f32_kernel<256>, lds_bytes);
+    const auto kernel = form == 0 ? conv5_vlad_f32_form0_kernel<256> : conv5_vlad_f32_kernel<256>;
+    EPC_SET_DYN_LDS(kernel, lds_bytes);
     const unsigned blocks = (unsigned)((num_points_total + C5_WAVES * 32 - 1) / (C5_WAVES * 32));
-    hipLaunchKernelGGL((conv5_vlad_f32_kernel<256>), dim3(blocks), dim3(C5_THREADS), lds_bytes, (hipStream_t)stream, cat,
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(C5_THREADS), lds_bytes, (hipStream_t)stream, cat,
                        (const float*)packed_conv5, num_points_total, (float*)feat_frag, rnorm, assign, (float*)assign_frag, apart);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
+}
+
+extern "C" int epc_conv5_assign_f32_fwd(const float* cat, int cin, const void* packed_conv5, int num_points_total,
+                                        void* feat_frag, float* rnorm, float* assign, void* assign_frag, float* apart,
+                                        void* stream) {
+    return conv5_assign_f32_fwd_impl(cat, cin, packed_conv5, num_points_total, feat_frag, rnorm, assign, assign_frag, apart, 1, stream);
+}
+
+// Test entry point: the VLAD kernel in the form the caller names.  An explicit argument: the library reads no environment.
+extern "C" int epcnet_conv5_assign_f32_fwd_form(const float* cat, int cin, const void* packed_conv5, int num_points_total,
+                                                void* feat_frag, float* rnorm, float* assign, void* assign_frag, float* apart,
+                                                int form, void* stream) {
+    EPC_CHECK_ARG(form == 0 || form == 1, "form 0 or 1");
+    return conv5_assign_f32_fwd_impl(cat, cin, packed_conv5, num_points_total, feat_frag, rnorm, assign, assign_frag, apart, form, stream);
 }
 
 extern "C" int epc_conv5_maxpool_fwd(const float* cat, int cin, const void* packed_conv5, int num_clouds, int n,

@@ -25,6 +25,14 @@ int epcnet_block_fwd_form(const float* x, const void* x16, const float* xyz, con
                           float* out, void* out16, int out_stride, int out_off, float* x_next, void* x_next16, int32_t* status,
                           int form, void* stream);
 
+/* epc_conv5_assign_f32_fwd of epcnet.h -- same arguments, same checks -- with the form of the kernel chosen by the caller: form 0 = the
+ * kernel with plain loads and stores and the epilogue's bf16 split value by value, 1 = the once-touched bytes (outputs, cat rows)
+ * moved with the non-temporal hint and the epilogue's vector work trimmed (what the entry of epcnet.h and the pipeline launch).
+ * Both forms leave bit-identical feat_frag, rnorm, assign, assign_frag and apart (tests/test_gpu_conv5_forms.py).  EPC_EINVAL for
+ * any other form. */
+int epcnet_conv5_assign_f32_fwd_form(const float* cat, int cin, const void* packed_conv5, int num_points_total, void* feat_frag,
+                                     float* rnorm, float* assign, void* assign_frag, float* apart, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
