@@ -3,8 +3,9 @@
 The header is the one definition of the C boundary: ``parse_header`` reads every declaration, ``#define EPC_*`` and the
 ``epc_status`` enum out of it, and this module sets ``restype`` / ``argtypes`` of every entry point, the ``EPC_*`` module
 attributes, ``STATUS_NAMES``, ``EXPORTS`` and the checked call form ``run`` of every entry point that takes a stream from the
-result.  Anything the reader does not understand is an exception at import, never a skipped line.  Only the three structures are mirrored by hand (tests/test_host_cpu.py checks their layout
-against the compiler).
+result.  The further headers ``include/epcnet_*.h`` are read the same way, one row of the table ``_HEADERS`` each.  Anything the reader
+does not understand, a name declared twice or a missing header is an exception at import, never a skipped line.  Only the three
+structures are mirrored by hand (tests/test_host_cpu.py checks their layout against the compiler).
 
 There is NO fallback: if the shared library has not been built (``python -c "import __graft_entry__ as g;
 g.build()"`` or ``make -C epc-net_amd/csrc``) importing this module raises, and every op raises ``EpcNetError``
@@ -28,8 +29,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "epcnet.h")
 
 _SCALARS = {"int": c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "float": c_float,
             "size_t": ctypes.c_size_t, "int32_t": c_int32, "uint32_t": ctypes.c_uint32}
-# what include/epcnet_revisits.h, include/epcnet_pairs.h and include/epcnet_trajectory.h pass by value besides: the reader of every other header goes on refusing a
-# `double` parameter
+# what the headers whose row of _HEADERS says so pass by value besides: the reader of every other header goes on refusing a `double`
+# parameter
 _REVISIT_SCALARS = dict(_SCALARS, double=ctypes.c_double)
 # the dtype a tensor must have where the header declares a typed pointee (``run``); any dtype goes at every other pointer
 _POINTEES = {"float*": torch.float32, "double*": torch.float64, "int32_t*": torch.int32, "int*": torch.int32, "long*": torch.int64}
@@ -37,10 +38,11 @@ _POINTEES = {"float*": torch.float32, "double*": torch.float64, "int32_t*": torc
 
 def parse_header(text: str, need_status: bool = True, scalars=_SCALARS):
     """``(functions, constants, status)`` of the text of include/epcnet.h (or, with ``need_status=False``, of a further header in the
-    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: include/epcnet_poses.h, include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h, include/epcnet_pairs.h, include/epcnet_trajectory.h): ``functions[name] = (return type, [parameter
-    types], [parameter names])`` in header order, the types as C type names without ``const`` and spaces around ``*`` -- a key
-    of ``scalars``, or any type with a ``*`` (``char*`` alone as a return type); ``constants``: every ``#define EPC_<NAME>
-    <integer>``; ``status``: the members of ``enum epc_status``.  Raises ValueError on whatever it does not understand."""
+    same grammar that declares no ``enum epc_status`` of its own and whose entries are named ``epcnet_*``: the rows of ``_HEADERS``):
+    ``functions[name] = (return type, [parameter types], [parameter names])`` in header order, the types as C type names without
+    ``const`` and spaces around ``*`` -- a key of ``scalars``, or any type with a ``*`` (``char*`` alone as a return type);
+    ``constants``: every ``#define EPC_<NAME> <integer>``; ``status``: the members of ``enum epc_status``.  Raises ValueError on whatever
+    it does not understand."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)         # extern "C" { and its }
     constants = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(EPC_\w+)[ \t]+(.*?)[ \t]*$", text, flags=re.M)}
@@ -80,100 +82,40 @@ if not os.path.exists(HEADER_PATH):
         "There is no second copy of the declarations." % HEADER_PATH)
 with open(HEADER_PATH) as _f:
     _functions, _constants, _status = parse_header(_f.read())
-# the second header (relations and tuples from poses): the same grammar, its entries bound and callable like the others but listed on
-# their own -- EXPORTS stays what include/epcnet.h declares
-POSES_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_poses.h")
-if not os.path.exists(POSES_HEADER_PATH):
-    raise ImportError("%s is missing: the binding of the pose entries is derived from it" % POSES_HEADER_PATH)
-with open(POSES_HEADER_PATH) as _f:
-    _pose_functions, _pose_constants, _ = parse_header(_f.read(), need_status=False)
-if set(_pose_functions) & set(_functions) or set(_pose_constants) & set(_constants):
-    raise ImportError("epcnet_poses.h declares a name epcnet.h declares")
-_constants.update(_pose_constants)
-POSE_EXPORTS = list(_pose_functions)
-# the third header (raw scans in front of the down-sampler): read, bound and listed like the second
-SCANS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_scans.h")
-if not os.path.exists(SCANS_HEADER_PATH):
-    raise ImportError("%s is missing: the binding of the scan entries is derived from it" % SCANS_HEADER_PATH)
-with open(SCANS_HEADER_PATH) as _f:
-    _scan_functions, _scan_constants, _ = parse_header(_f.read(), need_status=False)
-if set(_scan_functions) & (set(_functions) | set(_pose_functions)) or set(_scan_constants) & set(_constants):
-    raise ImportError("epcnet_scans.h declares a name epcnet.h or epcnet_poses.h declares")
-_constants.update(_scan_constants)
-SCAN_EXPORTS = list(_scan_functions)
-# the fourth header (travel-length submaps from posed scans): read, bound and listed like the third
-SUBMAPS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_submaps.h")
-if not os.path.exists(SUBMAPS_HEADER_PATH):
-    raise ImportError("%s is missing: the binding of the submap entries is derived from it" % SUBMAPS_HEADER_PATH)
-with open(SUBMAPS_HEADER_PATH) as _f:
-    _submap_functions, _submap_constants, _ = parse_header(_f.read(), need_status=False)
-if (set(_submap_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions))
-        or set(_submap_constants) & set(_constants)):
-    raise ImportError("epcnet_submaps.h declares a name an earlier header declares")
-_constants.update(_submap_constants)
-SUBMAP_EXPORTS = list(_submap_functions)
-# the fifth header (timestamped scans: odometry interpolated at the stamps, sweeps de-skewed): read, bound and listed like the fourth.
-# Its times are `long long*`, which _POINTEES does not know: ops checks the int64 dtypes itself
-STAMPS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_stamps.h")
-if not os.path.exists(STAMPS_HEADER_PATH):
-    raise ImportError("%s is missing: the binding of the stamp entries is derived from it" % STAMPS_HEADER_PATH)
-with open(STAMPS_HEADER_PATH) as _f:
-    _stamp_functions, _stamp_constants, _ = parse_header(_f.read(), need_status=False)
-if (set(_stamp_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions))
-        or set(_stamp_constants) & set(_constants)):
-    raise ImportError("epcnet_stamps.h declares a name an earlier header declares")
-_constants.update(_stamp_constants)
-STAMP_EXPORTS = list(_stamp_functions)
-# the sixth header (revisit search: the k nearest descriptors among the rows at least min_travel behind each query): read, bound and listed
-# like the fifth.  Its `along` values are `double*` (a float64 tensor, _POINTEES) and min_travel is a `double` by value
-REVISITS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_revisits.h")
-if not os.path.exists(REVISITS_HEADER_PATH):
-    raise ImportError("%s is missing: the binding of the revisit entries is derived from it" % REVISITS_HEADER_PATH)
-with open(REVISITS_HEADER_PATH) as _f:
-    _revisit_functions, _revisit_constants, _ = parse_header(_f.read(), need_status=False, scalars=_REVISIT_SCALARS)
-if (set(_revisit_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions) | set(_stamp_functions))
-        or set(_revisit_constants) & set(_constants)):
-    raise ImportError("epcnet_revisits.h declares a name an earlier header declares")
-_constants.update(_revisit_constants)
-REVISIT_EXPORTS = list(_revisit_functions)
-# the seventh header (pair registration: ICP of candidate pairs of clouds from seed poses): read, bound and listed like the sixth, with
-# the scalars that allow a `double` by value (max_dist); its two status bits join the EPC_* constants
-PAIRS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_pairs.h")
-if not os.path.exists(PAIRS_HEADER_PATH):
-    raise ImportError("%s is missing: the binding of the pair entries is derived from it" % PAIRS_HEADER_PATH)
-with open(PAIRS_HEADER_PATH) as _f:
-    _pair_functions, _pair_constants, _ = parse_header(_f.read(), need_status=False, scalars=_REVISIT_SCALARS)
-if (set(_pair_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions) | set(_stamp_functions)
-                            | set(_revisit_functions))
-        or set(_pair_constants) & set(_constants)):
-    raise ImportError("epcnet_pairs.h declares a name an earlier header declares")
-_constants.update(_pair_constants)
-PAIR_EXPORTS = list(_pair_functions)
-# the ninth header (loop closing: the relaxation of a trajectory's pose graph): read, bound and listed like the seventh, with the scalars
-# that allow a `double` by value (the odometry weights); its status bit joins the EPC_* constants
-TRAJECTORY_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_trajectory.h")
-if not os.path.exists(TRAJECTORY_HEADER_PATH):
-    raise ImportError("%s is missing: the binding of the trajectory entries is derived from it" % TRAJECTORY_HEADER_PATH)
-with open(TRAJECTORY_HEADER_PATH) as _f:
-    _trajectory_functions, _trajectory_constants, _ = parse_header(_f.read(), need_status=False, scalars=_REVISIT_SCALARS)
-if (set(_trajectory_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions)
-                                  | set(_stamp_functions) | set(_revisit_functions) | set(_pair_functions))
-        or set(_trajectory_constants) & set(_constants)):
-    raise ImportError("epcnet_trajectory.h declares a name an earlier header declares")
-_constants.update(_trajectory_constants)
-TRAJECTORY_EXPORTS = list(_trajectory_functions)
-# the eighth header (test / tuning entries that name a kernel's form): read, bound and listed like the others
-FORMS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "epcnet_forms.h")
-if not os.path.exists(FORMS_HEADER_PATH):
-    raise ImportError("%s is missing: the binding of the form entries is derived from it" % FORMS_HEADER_PATH)
-with open(FORMS_HEADER_PATH) as _f:
-    _form_functions, _form_constants, _ = parse_header(_f.read(), need_status=False)
-if (set(_form_functions) & (set(_functions) | set(_pose_functions) | set(_scan_functions) | set(_submap_functions) | set(_stamp_functions)
-                            | set(_revisit_functions) | set(_pair_functions) | set(_trajectory_functions))
-        or set(_form_constants) & set(_constants)):
-    raise ImportError("epcnet_forms.h declares a name an earlier header declares")
-_constants.update(_form_constants)
-FORM_EXPORTS = list(_form_functions)
+# The further headers, in the order they are bound: the same grammar and the same library, their entries bound and callable like the
+# others but listed on their own -- EXPORTS stays what include/epcnet.h declares.  A new header is a new row: (the stem of
+# include/epcnet_<stem>.h, the prefix of its list, whether a `double` may be passed by value, whether every entry must launch)
+_HEADERS = (
+    ("poses", "POSE", False, True),             # POSE_EXPORTS, POSES_HEADER_PATH: relations and tuples from poses
+    ("scans", "SCAN", False, False),            # SCAN_EXPORTS, SCANS_HEADER_PATH: raw scans in front of the down-sampler
+    ("submaps", "SUBMAP", False, False),        # SUBMAP_EXPORTS, SUBMAPS_HEADER_PATH: travel-length submaps from posed scans
+    # STAMP_EXPORTS, STAMPS_HEADER_PATH: timestamped scans.  Its times are `long long*`, which _POINTEES does not know: ops checks them
+    ("stamps", "STAMP", False, False),
+    ("revisits", "REVISIT", True, False),       # REVISIT_EXPORTS, REVISITS_HEADER_PATH: `along` is `double*` (float64, _POINTEES)
+    ("pairs", "PAIR", True, False),             # PAIR_EXPORTS, PAIRS_HEADER_PATH: its two status bits join the EPC_* constants
+    ("trajectory", "TRAJECTORY", True, False),  # TRAJECTORY_EXPORTS, TRAJECTORY_HEADER_PATH: loop closing; one status bit more
+    ("forms", "FORM", False, False))            # FORM_EXPORTS, FORMS_HEADER_PATH: test / tuning entries that name a kernel's form
+
+
+def _bind_header(text, header, doubles, declared, constants):
+    """The functions of the further header ``header`` from its text; its constants join ``constants``.  A function that a header of
+    ``declared`` (header -> functions) declares, or a constant that ``constants`` holds, is an ImportError that names ``header``."""
+    functions, defines, _ = parse_header(text, need_status=False, scalars=_REVISIT_SCALARS if doubles else _SCALARS)
+    if any(set(functions) & set(earlier) for earlier in declared.values()) or set(defines) & set(constants):
+        raise ImportError("%s declares a name epcnet.h or an earlier header declares" % header)
+    constants.update(defines)
+    return functions
+
+
+_declared = {"epcnet.h": _functions}            # header -> its functions, in the order bound: what argtypes and `run` are set from
+for _stem, _prefix, _doubles, _ in _HEADERS:
+    _header = "epcnet_%s.h" % _stem
+    _path = os.path.join(os.path.dirname(HEADER_PATH), _header)
+    if not os.path.exists(_path):
+        raise ImportError("%s is missing: the binding of its entries is derived from it" % _path)
+    with open(_path) as _f:
+        _declared[_header] = _bind_header(_f.read(), _header, _doubles, _declared, _constants)
+    globals().update({_stem.upper() + "_HEADER_PATH": _path, _prefix + "_EXPORTS": list(_declared[_header])})
 globals().update(_constants, **_status)     # EPC_OK, EPC_EINVAL, EPC_KNN_CAP, EPC_PRECISION_FAST, EPC_NUM_STAGES ... as module attributes
 # every symbol include/epcnet.h declares, in its order (tests check the library exports exactly these)
 EXPORTS = list(_functions)
@@ -222,12 +164,11 @@ _lib = ctypes.CDLL(LIB_PATH)
 
 # a pointer to a structure mirrored above keeps its type check; every other pointer is a void*
 _POINTERS = {"epc_cfg*": POINTER(EpcCfg), "epc_chain_fwd_args*": POINTER(ChainFwdArgs)}
-for _name, (_ret, _params, _) in (list(_functions.items()) + list(_pose_functions.items()) + list(_scan_functions.items())
-                                  + list(_submap_functions.items()) + list(_stamp_functions.items()) + list(_revisit_functions.items())
-                                  + list(_pair_functions.items()) + list(_trajectory_functions.items()) + list(_form_functions.items())):
-    _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
-    _fn.restype = c_char_p if _ret == "char*" else _REVISIT_SCALARS[_ret]
-    _fn.argtypes = [_REVISIT_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
+for _fs in _declared.values():
+    for _name, (_ret, _params, _) in _fs.items():
+        _fn = getattr(_lib, _name)  # AttributeError here = the built library is stale (rebuild it)
+        _fn.restype = c_char_p if _ret == "char*" else _REVISIT_SCALARS[_ret]
+        _fn.argtypes = [_REVISIT_SCALARS.get(_t) or _POINTERS.get(_t, c_void_p) for _t in _params]
 
 
 def lib() -> ctypes.CDLL:
@@ -316,22 +257,17 @@ class run:
     size queries, ``*_ok``, the forwards whose stream is not last -- is called on the raw handle ``lib()``."""
 
 
-LAUNCHING = [_n for _n, (_, _t, _pn) in _functions.items() if _t and (_t[-1], _pn[-1]) == ("void*", "stream")]
-for _name in LAUNCHING:
-    assert _functions[_name][0] == "int", "%s takes a stream and does not return a status" % _name
-    setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), *_functions[_name][1:])))
-for _name, (_ret, _t, _pn) in _pose_functions.items():          # every entry of include/epcnet_poses.h launches
-    assert _ret == "int" and (_t[-1], _pn[-1]) == ("void*", "stream"), "%s does not take a stream last and return a status" % _name
-    setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))
-for _name, (_ret, _t, _pn) in (list(_scan_functions.items()) + list(_submap_functions.items()) + list(_stamp_functions.items())
-                               + list(_revisit_functions.items()) + list(_pair_functions.items()) + list(_trajectory_functions.items())
-                               + list(_form_functions.items())):
-    # include/epcnet_scans.h, include/epcnet_submaps.h, include/epcnet_stamps.h, include/epcnet_revisits.h, include/epcnet_pairs.h,
-    # include/epcnet_trajectory.h and include/epcnet_forms.h: the
-    # entries that take a stream launch
-    if _t and (_t[-1], _pn[-1]) == ("void*", "stream"):
-        assert _ret == "int", "%s takes a stream and does not return a status" % _name
-        setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))
+LAUNCHING = []                                  # what include/epcnet.h alone declares with a stream
+_all_launch = {"epcnet_%s.h" % _stem for _stem, _, _, _every in _HEADERS if _every}
+for _header, _fs in _declared.items():
+    for _name, (_ret, _t, _pn) in _fs.items():
+        if _t and (_t[-1], _pn[-1]) == ("void*", "stream"):
+            assert _ret == "int", "%s takes a stream and does not return a status" % _name
+            setattr(run, _name, staticmethod(_launcher(_name, getattr(_lib, _name), _t, _pn)))
+            if _header == "epcnet.h":
+                LAUNCHING.append(_name)
+        else:
+            assert _header not in _all_launch, "%s: every entry of %s takes a stream last" % (_name, _header)
 
 
 def require_gpu() -> None:

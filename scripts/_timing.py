@@ -1,9 +1,11 @@
-"""What the front-end timing scripts share (time_downsample.py, time_ground.py, time_submap.py, time_deskew.py): the compiler's resource
-remarks per kernel, the loop of alternating arms, and the JSON line stamped with the SHA-256 of the loaded library."""
+"""What the timing scripts of the scan front end and of loop closing share (time_downsample.py, time_ground.py, time_submap.py,
+time_deskew.py; time_revisits.py, time_register.py, time_relax.py): the compiler's resource remarks per kernel, one child process per
+case, the loop of alternating arms, and the JSON line stamped with the SHA-256 of the loaded library."""
 import json
 import os
 import re
 import subprocess
+import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,6 +30,24 @@ def kernel_resources(source, name_regex):
                               "vgpr_spills": grab("VGPRs Spill"), "lds_bytes": grab("LDS Size [bytes/block]"),
                               "waves_per_simd": grab("Occupancy [waves/SIMD]")}
     return out
+
+
+def children(script, cases, passed_on, limit):
+    """The parent half of a script that measures one case per process and touches no device itself: ``script --one <case>`` with the
+    arguments ``passed_on``, one child at a time, each under ``limit`` seconds -> the last stdout line of every child, parsed as JSON
+    (and printed as it arrives).  The first child that exits non-zero or runs out of time ends the run: nothing further is started."""
+    lines = []
+    for case in cases:
+        cmd = [sys.executable, os.path.abspath(script), "--one", case] + [str(a) for a in passed_on]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)     # a child past its limit is killed
+        except subprocess.TimeoutExpired:
+            raise SystemExit("--one %s did not end within %d s; nothing further is started" % (case, limit))
+        if r.returncode != 0:
+            raise SystemExit("--one %s failed (%d); nothing further is started\n%s" % (case, r.returncode, r.stderr[-2000:]))
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        print(json.dumps(lines[-1]), flush=True)
+    return lines
 
 
 def alternate(arms, steps, regions, warmup, events=False):
@@ -61,9 +81,11 @@ def alternate(arms, steps, regions, warmup, events=False):
 
 
 def emit(line, out=None):
-    """Stamp ``line`` with the loaded library's SHA-256, print it as one JSON line and, ``out``, write it to that file too."""
-    import bench
-    line["lib_sha256"] = bench.lib_sha256()
+    """Stamp ``line`` with the loaded library's SHA-256 (a parent of ``children`` loads none: its line carries a child's stamp already),
+    print it as one JSON line and, ``out``, write it to that file too."""
+    if "lib_sha256" not in line:
+        import bench
+        line["lib_sha256"] = bench.lib_sha256()
     text = json.dumps(line)
     print(text)
     if out:

@@ -11,13 +11,14 @@ stops at the first child that fails, and writes the children's lines as one JSON
 Usage (GPU box): python scripts/time_register.py [--sizes 1024,4096] [--pairs 5,320,4096] [--steps K] [--regions R] [--warmup W]
 [--limit SECONDS] [--out FILE]"""
 import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import _timing  # noqa: E402
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "r14_register_time.json")
 
 ap = argparse.ArgumentParser()
@@ -34,32 +35,19 @@ ap.add_argument("--out", default=DEFAULT_OUT)
 args = ap.parse_args()
 
 if not args.one:
-    lines = []
-    for n in (int(s) for s in args.sizes.split(",")):
-        for P in (int(s) for s in args.pairs.split(",")):
-            cmd = [sys.executable, os.path.abspath(__file__), "--one", "%d,%d" % (n, P), "--steps", str(args.steps), "--regions",
-                   str(args.regions), "--warmup", str(args.warmup), "--seeds", str(args.seeds), "--iterations", str(args.iterations)]
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)   # a child past its limit is killed: TimeoutExpired
-            if r.returncode != 0:
-                raise SystemExit("n = %d, P = %d failed (%d); nothing further is started\n%s" % (n, P, r.returncode, r.stderr[-2000:]))
-            lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
-            print(json.dumps(lines[-1]), flush=True)
+    lines = _timing.children(__file__, ["%s,%s" % (n, P) for n in args.sizes.split(",") for P in args.pairs.split(",")],
+                             ["--steps", args.steps, "--regions", args.regions, "--warmup", args.warmup, "--seeds", args.seeds,
+                              "--iterations", args.iterations], args.limit)
     slower = [(l["n"], l["P"]) for l in lines if l["pass_over_torch"] > 1.0]
-    doc = {"workload": "P pairs among 64 views of a structured scene of n rows, %d seeds per pair a few degrees apart, %d iterations, max_dist "
-                       "1 m, min_pairs 32" % (args.seeds, args.iterations),
-           "timer": "HIP events around %d calls; median of %d regions, the arms alternating; eager, one stream; one process per (n, P)"
-                    % (args.steps, args.regions),
-           "bar": "one correspondence pass through the entry is not slower than the faster torch.cdist + argmin pass",
-           "verdict": "met at every size" if not slower else "MISSED at (n, P) = %s" % slower,
-           "sizes": lines, "lib_sha256": lines[0]["lib_sha256"] if lines else None}
-    text = json.dumps(doc)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    _timing.emit({"workload": "P pairs among 64 views of a structured scene of n rows, %d seeds per pair a few degrees apart, %d iterations, max_dist "
+                              "1 m, min_pairs 32" % (args.seeds, args.iterations),
+                  "timer": "HIP events around %d calls; median of %d regions, the arms alternating; eager, one stream; one process per (n, P)"
+                           % (args.steps, args.regions),
+                  "bar": "one correspondence pass through the entry is not slower than the faster torch.cdist + argmin pass",
+                  "verdict": "met at every size" if not slower else "MISSED at (n, P) = %s" % slower,
+                  "sizes": lines, "lib_sha256": lines[0]["lib_sha256"]}, args.out)
     raise SystemExit(0)
 
-sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -116,28 +104,14 @@ arms = {"register_pairs": lambda: RT.register_pairs(clouds, pairs, seeds, iterat
         "one_pass_entry": lambda: RT.register_pairs(clouds, pairs, None, iterations=0, **kw),
         "torch_pass_loop": torch_pass_loop,
         "torch_pass_batched": torch_pass_batched}
-for fn in arms.values():
-    for _ in range(args.warmup):
-        fn()
-torch.cuda.synchronize()
-times = {name: [] for name in arms}
-for _ in range(args.regions):
-    for name, fn in arms.items():
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        start.record()
-        for _ in range(args.steps):
-            fn()
-        end.record()
-        end.synchronize()
-        times[name].append(start.elapsed_time(end) / args.steps)
+times = {name: [1e3 * t / args.steps for t in v]                             # seconds per region -> ms per call
+         for name, v in _timing.alternate(arms, args.steps, args.regions, args.warmup, events=True).items()}
 ms = {name: statistics.median(v) for name, v in times.items()}
 ratio = ms["one_pass_entry"] / min(ms["torch_pass_loop"], ms["torch_pass_batched"])
 passes = Hs + args.iterations
-print(json.dumps({"n": n, "P": P, "seeds": Hs, "iterations": args.iterations, "passes_per_call": passes,
-                  "ms_per_call": {k: round(v, 4) for k, v in ms.items()},
-                  "regions_ms": {k: [round(t, 4) for t in v] for k, v in times.items()},
-                  "ms_per_pass_in_call": round(ms["register_pairs"] / passes, 4),
-                  "pass_over_torch": round(ratio, 3),
-                  "verdict": "not slower than the torch pass" if ratio <= 1.0 else "SLOWER than the torch pass",
-                  "lib_sha256": bench.lib_sha256()}))
+_timing.emit({"n": n, "P": P, "seeds": Hs, "iterations": args.iterations, "passes_per_call": passes,
+              "ms_per_call": {k: round(v, 4) for k, v in ms.items()},
+              "regions_ms": {k: [round(t, 4) for t in v] for k, v in times.items()},
+              "ms_per_pass_in_call": round(ms["register_pairs"] / passes, 4),
+              "pass_over_torch": round(ratio, 3),
+              "verdict": "not slower than the torch pass" if ratio <= 1.0 else "SLOWER than the torch pass"})

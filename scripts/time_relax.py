@@ -12,13 +12,14 @@ stops at the first child that fails, and writes the children's lines as one JSON
 Usage (GPU box): python scripts/time_relax.py [--sizes 4096x64,32768x1024,4096x5] [--steps K] [--regions R] [--warmup W] [--limit SECONDS]
 [--out FILE]"""
 import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import _timing  # noqa: E402
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "r15_relax_time.json")
 
 ap = argparse.ArgumentParser()
@@ -34,33 +35,20 @@ ap.add_argument("--out", default=DEFAULT_OUT)
 args = ap.parse_args()
 
 if not args.one:
-    lines = []
-    for size in args.sizes.split(","):
-        T, nl = (int(v) for v in size.split("x"))
-        cmd = [sys.executable, os.path.abspath(__file__), "--one", "%d,%d" % (T, nl), "--steps", str(args.steps), "--regions", str(args.regions),
-               "--warmup", str(args.warmup), "--iterations", str(args.iterations), "--cg", str(args.cg)]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)       # a child past its limit is killed: TimeoutExpired
-        if r.returncode != 0:
-            raise SystemExit("T = %d, L = %d failed (%d); nothing further is started\n%s" % (T, nl, r.returncode, r.stderr[-2000:]))
-        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
-        print(json.dumps(lines[-1]), flush=True)
+    lines = _timing.children(__file__, [size.replace("x", ",") for size in args.sizes.split(",")],
+                             ["--steps", args.steps, "--regions", args.regions, "--warmup", args.warmup, "--iterations", args.iterations,
+                              "--cg", args.cg], args.limit)
     slower = [(l["T"], l["L"]) for l in lines if l["entry_over_torch"] > 1.0]
-    doc = {"workload": "a wandering trajectory of T submaps, 5 m apart, with L loops between random nodes; iterations %d, cg_iterations %d, "
-                       "odometry weights (1, 100)" % (args.iterations, args.cg),
-           "timer": "HIP events around %d calls; median of %d regions, the arms alternating; one stream; one process per size"
-                    % (args.steps, args.regions),
-           "bar": "the eager call is not slower than the same iteration written with torch (cumsum, index_add_, batched matmul) on the device",
-           "verdict": "met at every size" if not slower else "MISSED at (T, L) = %s" % slower,
-           "not_measured": "no kernel trace was taken: the shares of launch latency, scans and edge work inside a CG iteration are not known",
-           "sizes": lines, "lib_sha256": lines[0]["lib_sha256"] if lines else None}
-    text = json.dumps(doc)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    _timing.emit({"workload": "a wandering trajectory of T submaps, 5 m apart, with L loops between random nodes; iterations %d, cg_iterations %d, "
+                              "odometry weights (1, 100)" % (args.iterations, args.cg),
+                  "timer": "HIP events around %d calls; median of %d regions, the arms alternating; one stream; one process per size"
+                           % (args.steps, args.regions),
+                  "bar": "the eager call is not slower than the same iteration written with torch (cumsum, index_add_, batched matmul) on the device",
+                  "verdict": "met at every size" if not slower else "MISSED at (T, L) = %s" % slower,
+                  "not_measured": "no kernel trace was taken: the shares of launch latency, scans and edge work inside a CG iteration are not known",
+                  "sizes": lines, "lib_sha256": lines[0]["lib_sha256"]}, args.out)
     raise SystemExit(0)
 
-sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -206,31 +194,17 @@ arms = {"entry": lambda: RT.relax_trajectory(odo, pairs, rel, weights, (WT, WR),
         "entry_half_cg": lambda: RT.relax_trajectory(odo, pairs, rel, weights, (WT, WR), args.iterations, half, workspace=ws),
         "torch_half_cg": lambda: torch_relax(args.iterations, half),
         "entry_graph": graphs["entry_graph"].replay}
-for fn in arms.values():
-    for _ in range(args.warmup):
-        fn()
-torch.cuda.synchronize()
-times = {name: [] for name in arms}
-for _ in range(args.regions):
-    for name, fn in arms.items():
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        start.record()
-        for _ in range(args.steps):
-            fn()
-        end.record()
-        end.synchronize()
-        times[name].append(start.elapsed_time(end) / args.steps)
+times = {name: [1e3 * t / args.steps for t in v]                             # seconds per region -> ms per call
+         for name, v in _timing.alternate(arms, args.steps, args.regions, args.warmup, events=True).items()}
 ms = {name: statistics.median(v) for name, v in times.items()}
 ratio = ms["entry"] / ms["torch"]
 per_cg = lambda full, part: (ms[full] - ms[part]) / (args.iterations * (args.cg - half)) if args.cg > half else None
 launches = 4 + args.iterations * (7 + 7 * args.cg) + 4
-print(json.dumps({"T": T, "L": nl, "iterations": args.iterations, "cg_iterations": args.cg, "launches_per_call": launches,
-                  "ms_per_call": {k: round(v, 4) for k, v in ms.items()},
-                  "regions_ms": {k: [round(t, 4) for t in v] for k, v in times.items()},
-                  "us_per_cg_iteration": {"entry": round(1e3 * per_cg("entry", "entry_half_cg"), 2),
-                                          "torch": round(1e3 * per_cg("torch", "torch_half_cg"), 2)},
-                  "us_per_launch_in_graph": round(1e3 * ms["entry_graph"] / launches, 3),
-                  "entry_over_torch": round(ratio, 3),
-                  "verdict": "not slower than the torch arm" if ratio <= 1.0 else "SLOWER than the torch arm",
-                  "lib_sha256": bench.lib_sha256()}))
+_timing.emit({"T": T, "L": nl, "iterations": args.iterations, "cg_iterations": args.cg, "launches_per_call": launches,
+              "ms_per_call": {k: round(v, 4) for k, v in ms.items()},
+              "regions_ms": {k: [round(t, 4) for t in v] for k, v in times.items()},
+              "us_per_cg_iteration": {"entry": round(1e3 * per_cg("entry", "entry_half_cg"), 2),
+                                      "torch": round(1e3 * per_cg("torch", "torch_half_cg"), 2)},
+              "us_per_launch_in_graph": round(1e3 * ms["entry_graph"] / launches, 3),
+              "entry_over_torch": round(ratio, 3),
+              "verdict": "not slower than the torch arm" if ratio <= 1.0 else "SLOWER than the torch arm"})

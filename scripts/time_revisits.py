@@ -9,13 +9,14 @@ Without --one the script touches no device itself: it starts one child process p
 the first child that fails, and writes the children's lines as one JSON document, stamped with the SHA-256 of the loaded library.
 Usage (GPU box): python scripts/time_revisits.py [--sizes 4096,32768] [--steps K] [--regions R] [--warmup W] [--limit SECONDS] [--out FILE]"""
 import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import _timing  # noqa: E402
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "r13_revisit_time.json")
 
 ap = argparse.ArgumentParser()
@@ -32,28 +33,16 @@ ap.add_argument("--out", default=DEFAULT_OUT)
 args = ap.parse_args()
 
 if not args.one:
-    lines = []
-    for T in (int(s) for s in args.sizes.split(",")):
-        cmd = [sys.executable, os.path.abspath(__file__), "--one", str(T), "--steps", str(args.steps), "--regions", str(args.regions),
-               "--warmup", str(args.warmup), "--dim", str(args.dim), "--k", str(args.k), "--min-travel", str(args.min_travel)]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)       # a child past its limit is killed: TimeoutExpired
-        if r.returncode != 0:
-            raise SystemExit("T = %d failed (%d); nothing further is started\n%s" % (T, r.returncode, r.stderr[-2000:]))
-        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
-    doc = {"workload": "one trajectory of T submaps searched against itself: dim %d, k %d, along = arange(T) * 10, min_travel %g"
-                       % (args.dim, args.k, args.min_travel),
-           "timer": "HIP events around %d calls; median of %d regions, the arms alternating; eager, one stream; one process per T"
-                    % (args.steps, args.regions),
-           "expectation": "revisit_search is not slower than knn_search(desc, desc, k) on the same rows",
-           "sizes": lines, "lib_sha256": lines[0]["lib_sha256"] if lines else None}
-    text = json.dumps(doc)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    lines = _timing.children(__file__, args.sizes.split(","), ["--steps", args.steps, "--regions", args.regions, "--warmup", args.warmup,
+                                                                "--dim", args.dim, "--k", args.k, "--min-travel", args.min_travel], args.limit)
+    _timing.emit({"workload": "one trajectory of T submaps searched against itself: dim %d, k %d, along = arange(T) * 10, min_travel %g"
+                              % (args.dim, args.k, args.min_travel),
+                  "timer": "HIP events around %d calls; median of %d regions, the arms alternating; eager, one stream; one process per T"
+                           % (args.steps, args.regions),
+                  "expectation": "revisit_search is not slower than knn_search(desc, desc, k) on the same rows",
+                  "sizes": lines, "lib_sha256": lines[0]["lib_sha256"]}, args.out)
     raise SystemExit(0)
 
-sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import bench  # noqa: E402
@@ -95,25 +84,11 @@ assert torch.equal(got[1], idx[-1:]) and torch.equal(got[2], count[-1:]), "the s
 arms = {"revisit_search": lambda: RT.revisit_search(desc, along, args.min_travel, k, workspace=ws),
         "knn_search_square": lambda: RT.knn_search(desc, desc, k),
         "index_add_one_row": add_one}
-for fn in arms.values():
-    for _ in range(args.warmup):
-        fn()
-torch.cuda.synchronize()
-times = {name: [] for name in arms}
-for _ in range(args.regions):
-    for name, fn in arms.items():
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        start.record()
-        for _ in range(args.steps):
-            fn()
-        end.record()
-        end.synchronize()
-        times[name].append(start.elapsed_time(end) / args.steps)
+times = {name: [1e3 * t / args.steps for t in v]                             # seconds per region -> ms per call
+         for name, v in _timing.alternate(arms, args.steps, args.regions, args.warmup, events=True).items()}
 ms = {name: statistics.median(v) for name, v in times.items()}
 ratio = ms["revisit_search"] / ms["knn_search_square"]
-print(json.dumps({"T": T, "ms_per_call": {n: round(v, 4) for n, v in ms.items()},
-                  "regions_ms": {n: [round(t, 4) for t in v] for n, v in times.items()},
-                  "revisit_over_square": round(ratio, 3),
-                  "verdict": "not slower than the square search" if ratio <= 1.0 else "SLOWER than the square search",
-                  "lib_sha256": bench.lib_sha256()}))
+_timing.emit({"T": T, "ms_per_call": {n: round(v, 4) for n, v in ms.items()},
+              "regions_ms": {n: [round(t, 4) for t in v] for n, v in times.items()},
+              "revisit_over_square": round(ratio, 3),
+              "verdict": "not slower than the square search" if ratio <= 1.0 else "SLOWER than the square search"})

@@ -405,3 +405,19 @@ def test_engine_clouds_option_on_both_trajectory_entries():
         plain = tuple(t.clone() for t in eng.forward_trajectory(moved, offsets, scan_pose, num_points=32, submaps=sub, ground=ground))
         got = eng.forward_trajectory(moved, offsets, scan_pose, num_points=32, submaps=sub, ground=ground, clouds=True)
         assert len(plain) == 4 and len(got) == 5 and all(_bits_equal(x, y) for x, y in zip(plain, got)) and got[4].shape == (24, 32, 3)
+
+
+def test_no_pair_with_the_callers_workspace_and_with_none():
+    """P = 0 pairs over two clouds of n = 32, with no seeds and with empty ones: the empty pairs, seeds and outputs have no address, the
+    workspace's stands in for them -- the caller's, which nothing writes, or the entry's own."""
+    RT = H.pkg("retrieval")
+    dev = torch.device("cuda")
+    clouds = _up(_moved_clouds(7, 32, count=2), np.float32)
+    pairs = torch.empty((0, 2), dtype=torch.int32, device=dev)
+    for ws in (torch.full((64,), 0xFF, dtype=torch.uint8, device=dev), None):
+        for seeds in (None, torch.empty((0, 2, 12), dtype=torch.float64, device=dev)):
+            out = RT.register_pairs(clouds, pairs, seeds, workspace=ws)
+            torch.cuda.synchronize()
+            assert [tuple(t.shape) for t in out] == [(0, 12), (0, 2), (0, 4), (0,)]
+            assert [t.dtype for t in out] == [torch.float64, torch.float64, torch.int32, torch.int32]
+            assert ws is None or bool((ws == 0xFF).all())

@@ -265,3 +265,17 @@ def test_python_entry_refuses_what_it_would_have_to_convert():
     with pytest.raises(L.EpcNetError) as e:
         M.relax_trajectory(*good, workspace=torch.empty(64, dtype=torch.uint8, device="cuda"))
     assert e.value.status == L.EPC_ENOMEM
+
+
+def test_no_loop_on_two_poses_with_the_callers_workspace_and_with_none():
+    """L = 0 loops on T = 2 poses through the Python entry: the empty pairs, rel, weights, chi2 and status have no address, the
+    workspace's stands in for them -- the caller's or the entry's own -- and the poses come back bit for bit."""
+    M, L = H.pkg("retrieval"), H.pkg("lib")
+    odo, pairs, rel, weights = R.walk_scene(2, 0, seed=4)
+    want = R.relax_reference(odo, pairs, rel, weights, 1.0, 100.0, 2, 8)
+    args = (_up(odo, np.float64), _up(np.zeros((0, 2)), np.int32), _up(np.zeros((0, 12)), np.float64), _up(np.zeros((0, 2)), np.float64))
+    for ws in (torch.full((L.lib().epcnet_trajectory_relax_workspace_bytes(2, 0),), 0xFF, dtype=torch.uint8, device="cuda"), None):
+        got = [t.cpu().numpy() for t in M.relax_trajectory(*args, iterations=2, cg_iterations=8, workspace=ws)]
+        _equal(got, want, "L = 0, workspace %s" % ("given" if ws is not None else "None"))
+        assert (_bits(got[0]) == _bits(odo)).all() and (_bits(got[1]) == 0).all() and got[4].tolist() == [2, 0]
+        assert got[2].shape == (0,) and got[3].shape == (0,)

@@ -305,3 +305,18 @@ def test_end_to_end_on_a_small_out_and_back_drive():
     assert count.tolist() == R.prefix_counts(along, along, 3 * length).tolist() and (count[S // 2:K] > 0).all()     # the return leg
     assert (idx[K:] == -1).all() and (idx < K).all()                         # a NaN slot selects nothing and is never selected
     assert (idx[7:K, 0] >= 0).all()
+
+
+def test_no_query_with_the_callers_workspace_and_with_none():
+    """Q = 0 queries against T = 8 rows of dim 8: the empty queries and outputs have no address, the workspace's stands in for them --
+    the caller's, which nothing writes, or the entry's own."""
+    RT = H.pkg("retrieval")
+    dev = torch.device("cuda")
+    desc = torch.from_numpy(R.unit_rows(5, 8, 8)).to(dev)
+    along = torch.arange(8, dtype=torch.float64, device=dev)
+    for ws in (torch.full((64,), 0xFF, dtype=torch.uint8, device=dev), None):
+        dist, idx, count = RT.revisit_search(desc, along, 1.0, 3, queries=desc[:0], q_along=along[:0], workspace=ws)
+        torch.cuda.synchronize()
+        assert (tuple(dist.shape), tuple(idx.shape), tuple(count.shape)) == ((0, 3), (0, 3), (0,))
+        assert (dist.dtype, idx.dtype, count.dtype) == (torch.float32, torch.int32, torch.int32)
+        assert ws is None or bool((ws == 0xFF).all())

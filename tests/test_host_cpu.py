@@ -112,6 +112,56 @@ def test_launching_set_is_the_headers_stream_last_functions():
     assert not [name for name, (ret, _, _) in functions.items() if ret == "size_t" and name in L.LAUNCHING]
 
 
+def test_every_further_header_has_its_row_and_is_bound_whole():
+    """lib._HEADERS against the files on disk -- a header added without a row fails here --, and what one loop makes of every row: the
+    public lists and paths, non-default restype / argtypes, and `run` holding exactly the functions whose last parameter is
+    `void* stream`."""
+    import glob
+    L = H.pkg("lib")
+    on_disk = sorted(os.path.basename(p)[len("epcnet_"):-len(".h")] for p in glob.glob(os.path.join(ROOT, "include", "epcnet_*.h")))
+    assert sorted(row[0] for row in L._HEADERS) == on_disk and list(L._declared) == ["epcnet.h"] + ["epcnet_%s.h" % row[0] for row in L._HEADERS]
+    assert [row[0] for row in L._HEADERS if row[2]] == ["revisits", "pairs", "trajectory"]          # a `double` by value
+    assert [row[0] for row in L._HEADERS if row[3]] == ["poses"]                                    # every entry launches
+    launching = []
+    for stem, prefix, doubles, every_launches in L._HEADERS:
+        path = getattr(L, stem.upper() + "_HEADER_PATH")
+        assert path == os.path.join(ROOT, "include", "epcnet_%s.h" % stem)
+        functions = L.parse_header(open(path).read(), need_status=False, scalars=L._REVISIT_SCALARS if doubles else L._SCALARS)[0]
+        assert functions == L._declared["epcnet_%s.h" % stem] and list(functions) == getattr(L, prefix + "_EXPORTS") and functions
+        for name, (ret, types, names) in functions.items():
+            fn = getattr(L.lib(), name)
+            assert fn.restype is L._REVISIT_SCALARS[ret], name             # set, and to the header's type: ctypes' default is c_int
+            assert fn.argtypes is not None and len(fn.argtypes) == len(types), name
+            if types and (types[-1], names[-1]) == ("void*", "stream"):
+                launching.append(name)
+        assert not every_launches or [n for n in functions if n in launching] == list(functions)
+    on_run = [n for n in vars(L.run) if not n.startswith("_")]
+    assert sorted(on_run) == sorted(L.LAUNCHING + launching) and len(on_run) == len(set(on_run))
+
+
+def test_a_name_declared_twice_is_an_import_error():
+    """The loop's collision check (lib._bind_header) on copies of what it accumulated: binding any row's text a second time -- every
+    function of it is declared already -- or a header that defines a constant again raises ImportError and names the header."""
+    L = H.pkg("lib")
+    for stem, _, doubles, _ in L._HEADERS:
+        text = open(getattr(L, stem.upper() + "_HEADER_PATH")).read()
+        declared, constants = dict(L._declared), dict(L._constants)
+        with pytest.raises(ImportError) as e:
+            L._bind_header(text, "epcnet_%s.h" % stem, doubles, declared, constants)
+        assert "epcnet_%s.h" % stem in str(e.value) and constants == L._constants
+        if not doubles:                                                      # ... and never by reading a `double` it should not
+            continue
+        with pytest.raises(ValueError):
+            L._bind_header(text, "epcnet_%s.h" % stem, False, {}, {})
+    fresh, constants = "int epcnet_fresh_entry(const float* x, int n, void* stream);\n", dict(L._constants)
+    assert list(L._bind_header("#define EPC_FRESH 7\n" + fresh, "epcnet_fresh.h", False, dict(L._declared), constants)) == ["epcnet_fresh_entry"]
+    assert constants["EPC_FRESH"] == 7 and "EPC_FRESH" not in L._constants
+    for clash in ("#define EPC_KNN_CAP 32\n" + fresh, fresh.replace("epcnet_fresh_entry", "epc_version"),
+                  fresh.replace("epcnet_fresh_entry", L.FORM_EXPORTS[-1])):
+        with pytest.raises(ImportError):
+            L._bind_header(clash, "epcnet_fresh.h", False, dict(L._declared), dict(L._constants))
+
+
 class _FakeDeviceTensor:
     """What lib.run asks of a tensor argument, without a device."""
 
