@@ -78,6 +78,10 @@ __device__ __forceinline__ void glds16(const float* uniform_base, unsigned lane_
 // scripts/probe/mfma_fp6_probe.hip: lane l supplies row / column l & 31 and k = 32 * (l >> 5) + j, value j in bits
 // [6j, 6j + 6) of the lane's six dwords; each lane passes its own scale byte (2^(byte - 127)), the byte of the scale
 // dword is picked by op_sel.  Six dwords per lane per 64-wide k-step, kept in LDS as 16 B + 8 B pieces.
+// v_cvt_scalef32_pk32_fp6_f16 rounds to nearest, ties to the even mantissa (the block exponent keeps |q| <= 7.5, so its
+// saturation is never reached); e2m3 subnormals (0.125 .. 0.875) count as such; sums whose partial sums are all float32
+// values come out exact.  Pinned bit for bit against a CPU emulation by tests/test_gpu_f16f6_product.py (tie rows, boundary
+// rows, a +-3 sweep over every (k, column)).
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x6 __attribute__((ext_vector_type(6)));
 typedef _Float16 f16x32 __attribute__((ext_vector_type(32)));

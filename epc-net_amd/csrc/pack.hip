@@ -157,6 +157,11 @@ __global__ void fold_pack_conv5_kernel(const float* __restrict__ W, const float*
 // chunk (byte offsets from the start of the lo area, 64*cin bytes into the chunk):
 //   k-step ks: [lane][16 B: dwords 0-3] at 1536 ks, [lane][8 B: dwords 4-5] at 1536 ks + 1024;
 //   block scales: [lane][4 B: byte ks = 127 + e] at 1536 * (cin / 64).
+// Runs AFTER fold_pack_conv5_kernel(f16 = 1) on the same stream: lo is the residual of the hi that kernel STORED, read back from
+// its fragments.  Rounding w to fp16 again here is not the same value: hipcc fuses this kernel's multiply into the conversion
+// (v_fma_mixlo_f16, one rounding of the exact product) while the fold converts the f32 product, and where that lands on an fp16
+// tie (1 weight in ~10^4) the two take different neighbours -- hi + lo was then a whole fp16 ulp off the weight
+// (tests/test_gpu_f16f6_product.py).
 __global__ void pack_conv5_lo6_kernel(const float* __restrict__ W, const float* __restrict__ gamma,
                                       const float* __restrict__ var, int cin, unsigned short* __restrict__ dstW) {
     const int o = blockIdx.x * 256 + threadIdx.x;
@@ -165,12 +170,15 @@ __global__ void pack_conv5_lo6_kernel(const float* __restrict__ W, const float* 
     const int lane = o & 63, ks = (o >> 6) % nks, c = (o >> 6) / nks;
     const int col = 32 * c + (lane & 31), k0 = 64 * ks + 32 * (lane >> 5);
     const float inv = bn_inv(gamma, var, col) * W5_SCALE;
+    // hi fragments of the chunk: k-step k >> 4, lane (column, k-octet (k >> 3) & 1), element k & 7 (fold_pack_conv5_kernel)
+    const unsigned short* hi = dstW + (size_t)c * 48 * cin + (lane & 31) * 8;
     float lo[32];
     float m = 0.f;
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
-        const float w = W[(size_t)(k0 + j) * 1024 + col] * inv;   // the same expression fold_pack_conv5_kernel rounds to hi
-        lo[j] = w - (float)(_Float16)w;
+        const int k = k0 + j;
+        const float w = W[(size_t)k * 1024 + col] * inv;   // the value fold_pack_conv5_kernel rounded to hi (256 = 2^8: the same product)
+        lo[j] = w - (float)__builtin_bit_cast(_Float16, hi[(k >> 4) * 512 + ((k >> 3) & 1) * 256 + (k & 7)]);
         m = fmaxf(m, fabsf(lo[j]));
     }
     const int e = fp6_block_exponent(m, -100, 20);
