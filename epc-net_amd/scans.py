@@ -1,6 +1,6 @@
 """The scan front end: everything between raw sensor data and the network's (B, N, 3) clouds -- the spatial sort, packing, grid
-down-sampling, ground removal, travel-length submaps, de-skewing and pose interpolation -- and the relations and training tuples drawn
-from poses.  Plain functions over device tensors: no autograd, no torch arithmetic on the hot path, no CPU fallback.  Every launch goes
+down-sampling, ground removal, travel-length submaps, de-skewing and pose interpolation --, the voxel map the corrected submaps are
+fused into, and the relations and training tuples drawn from poses.  Plain functions over device tensors: no autograd, no torch arithmetic on the hot path, no CPU fallback.  Every launch goes
 through ``L.run`` (lib.py).  ``ops`` re-exports these names: ``ops.pack_scans`` and the rest are this module's."""
 from __future__ import annotations
 
@@ -12,6 +12,7 @@ import torch
 
 from . import lib as L
 from .lib import EpcNetError
+from .loops import _workspace       # a caller's workspace is refused or taken by ONE rule
 
 # why a tensor of the wrong dtype is refused and never converted, by the dtype that was asked for
 _NEVER_CONVERTED = {
@@ -216,6 +217,55 @@ def build_submaps(points, offsets, poses, along=None, length=20.0, spacing=10.0,
                               sub_offsets, num_out, sub_pose, info, status, ws, ws.numel())
     result = (out, sub_offsets, status, sub_pose, info, num_out)
     return result + (along,) if return_along else result
+
+
+def fuse_map(points, offsets, poses, voxel=0.2, origin=None, max_voxels=None, min_count=1, workspace=None):
+    """Posed clouds -> ONE voxel map in one frame (include/epcnet_maps.h: epcnet_map_fuse; numpy restatement: tests/map_ref.py):
+    ``(map_points (max_voxels, 3) float32, count (max_voxels,) int32, num_out (4,) int32, origin (3,) float64)``, all device tensors, on
+    the current stream, no host read, capturable.  ``points`` / ``offsets``: packed ragged clouds -- the ``sub_points, sub_offsets`` of
+    ``build_submaps``, with or without ``remove_ground``; NaN rows are absent --; ``poses``: (C, 12) or (C, 3, 4) FLOAT64 device tensor,
+    row-major ``[R | t]`` cloud to world -- ``sub_pose``, or what ``close_loops`` returns; any other dtype is refused, never converted
+    (float32 UTM coordinates are 0.5 m apart).  ``origin`` (3,) float64 device tensor: the world point the map is relative to; ``None``
+    takes the first pose's translation (a device copy).
+
+    Every row is moved by its cloud's pose in float64 and falls into a cube of ``voxel`` metres; voxel j -- numbered by the first source
+    row that fell into it -- yields the mean of its rows' positions (on a lattice of ``voxel / 4096``, summed in integers: the same
+    bits on every run) as ``map_points[j]`` and their number as ``count[j]``.  A voxel of fewer than ``min_count`` rows (something that
+    passed by) and every row behind the last voxel are NaN rows, which ``grid_downsample`` and ``retrieval.register_pairs`` treat as
+    absent: the map goes to them as it is (a new submap is registered against the map like against a submap).  Nothing is compacted.
+    ``num_out``: voxels, rows kept, rows absent, rows out of range (more than 2^20 voxels from the origin); ``num_out[0] == -1`` with
+    an all-NaN map: more than ``max_voxels`` voxels, or invalid offsets.  ``max_voxels=None`` is the LOOSE bound ``min(max(rows, 1),
+    2^28)`` -- the true number is device data --; ``workspace``: a uint8 device tensor of at least ``epcnet_map_fuse_workspace_bytes``
+    bytes to reuse (what a captured graph needs), else one is allocated."""
+    who = "fuse_map"
+    C, rows, dev = _packed(who, points, offsets, "C")
+    _device_tensor(who, "poses", poses, torch.float64)
+    if tuple(poses.shape) not in ((C, 12), (C, 3, 4)):
+        raise EpcNetError(-1, "%s: poses must be (%d, 12) or (%d, 3, 4) = [R | t] per cloud, got %s" % (who, C, C, tuple(poses.shape)))
+    poses = poses.reshape(C, 12)
+    if origin is None:
+        origin = poses[0, 3::4].clone() if C else torch.zeros(3, dtype=torch.float64, device=dev)
+    else:
+        _device_tensor(who, "origin", origin, torch.float64, (3,))
+    L.require_gpu()
+    if max_voxels is None:
+        max_voxels = min(max(rows, 1), 2 ** 28)
+    max_voxels, voxel, min_count = int(max_voxels), float(voxel), int(min_count)
+    need = int(L.lib().epcnet_map_fuse_workspace_bytes(rows, C, max_voxels))
+    if need == 0:
+        raise EpcNetError(-1, "%s: need fewer than 2^31 rows, C <= 2^24 and 1 <= max_voxels <= 2^28, got %d, %d and %d" % (who, rows, C, max_voxels))
+    if not (math.isfinite(voxel) and 2.0 ** -20 <= voxel <= 2.0 ** 20 and 1 <= min_count < 2 ** 31):
+        raise EpcNetError(-1, "%s: need 2^-20 <= voxel <= 2^20 and 1 <= min_count < 2^31, got %r and %r" % (who, voxel, min_count))
+    ws, own = _workspace(who, need, workspace, dev)
+    map_points = torch.empty((max_voxels, 3), dtype=torch.float32, device=dev)
+    count = torch.empty(max_voxels, dtype=torch.int32, device=dev)
+    num_out = torch.empty(4, dtype=torch.int32, device=dev)
+    params = (ctypes.c_double * L.EPC_MAP_PARAMS)(voxel, float(min_count))       # (host memory; the six reserved doubles are 0)
+    L.run.epcnet_map_fuse(points if rows else _spare(dev), offsets, rows, C, poses if C else _spare(dev, torch.float64), origin, params,
+                          max_voxels, map_points, count, num_out, ws, ws.numel())
+    if own:
+        ws.record_stream(torch.cuda.current_stream(dev))
+    return map_points, count, num_out, origin
 
 
 def _max_gap_ns(who, max_gap):
