@@ -217,6 +217,24 @@ int epc_sort_launch(const float* xyz, int num_clouds, int n, float* xyz_sorted, 
 
 // ---- host helpers that serve every launcher of the library ------------------------------------------------
 static inline bool epc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline size_t epc_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Cuts a caller's workspace into regions.  An entry's layout function takes every region from one carver, in order (as the clauses of a
+// braced initialiser, which are evaluated left to right): on the buffer it yields the pointers, on NULL it only counts (every pointer
+// NULL), and bytes() after the last take is the entry's size query -- the query and the launcher cannot disagree.  A region occupies
+// count * sizeof(T) rounded up to `align` bytes.
+struct epc_carver {
+    char* base;
+    size_t offset = 0;
+    explicit epc_carver(void* buffer) : base(static_cast<char*>(buffer)) {}
+    template <typename T>
+    T* take(size_t count, size_t align = 1) {
+        T* const p = base ? reinterpret_cast<T*>(base + offset) : nullptr;
+        offset += epc_align_up(count * sizeof(T), align);
+        return p;
+    }
+    size_t bytes() const { return offset; }
+};
 
 // Opt a kernel in to `bytes` of dynamic LDS (more than the default 64 KB needs it).  A launcher that is not itself the entry point
 // passes the entry point's name on; EPC_SET_DYN_LDS is the form for an entry point's own body.

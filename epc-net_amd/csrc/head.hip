@@ -170,14 +170,16 @@ __global__ __launch_bounds__(1024) void fc_head_kernel(const float* __restrict__
     if (part == 0) out[(size_t)cloud * 256 + c] = poisoned ? __int_as_float(0x7fc00000) : y * (1.0f / sqrtf(fmaxf(tot, 1e-12f)));
 }
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// the workspace: U (num_clouds, kh) | Yp (slices, num_clouds, 256), each rounded up to 256 bytes; kh = the folded width, in slices of HSL
+struct vh_ws { int kh, slices; float *U, *Yp; size_t bytes; };
+static vh_ws vh_layout(void* base, int num_clouds, int groups) {
+    epc_carver c(base);
+    const int kh = 65536 / groups, slices = kh / HSL;
+    return {kh, slices, c.take<float>((size_t)num_clouds * kh, 256), c.take<float>((size_t)slices * num_clouds * 256, 256), c.bytes()};
+}
 
 extern "C" size_t epc_vlad_head_workspace_bytes(int num_clouds, int groups) {
-    if (num_clouds <= 0 || groups <= 0 || 64 % groups) return 0;
-    const size_t kh = 65536 / groups;
-    const size_t u = align_up((size_t)num_clouds * kh * sizeof(float), 256);
-    const size_t yp = align_up((kh / HSL) * (size_t)num_clouds * 256 * sizeof(float), 256);
-    return u + yp;
+    return num_clouds > 0 && groups > 0 && 64 % groups == 0 ? vh_layout(nullptr, num_clouds, groups).bytes : 0;
 }
 
 extern "C" int epc_vlad_head_fwd(const float* V, const float* colss, const void* packed_head, int groups,
@@ -191,20 +193,17 @@ extern "C" int epc_vlad_head_fwd(const float* V, const float* colss, const void*
         epc_set_error("epc_vlad_head_fwd: workspace too small");
         return EPC_ENOMEM;
     }
-    const int kh = 65536 / groups;
+    const vh_ws w = vh_layout(workspace, num_clouds, groups);
+    const int kh = w.kh, slices = w.slices;
     const float* hp = (const float*)packed_head;
     const float* Hw = hp + 65536;   // past the centres (epc_vlad_aggregate_fwd's operand)
     const float* tail = Hw + (size_t)kh * 256;
-    char* wsp = (char*)workspace;
-    float* U = (float*)wsp;
-    wsp += align_up((size_t)num_clouds * kh * sizeof(float), 256);
-    float* Yp = (float*)wsp;
     hipStream_t st = (hipStream_t)stream;
     EPC_CHECK_ARG(num_clouds <= 65535, "too many clouds per call");
     switch (groups) {
 #define EPC_VF(G)                                                                                                  \
     case G:                                                                                                        \
-        hipLaunchKernelGGL(vlad_fold_kernel<G>, dim3(1024 / G / 16, num_clouds), dim3(256), 0, st, V, colss, U);   \
+        hipLaunchKernelGGL(vlad_fold_kernel<G>, dim3(1024 / G / 16, num_clouds), dim3(256), 0, st, V, colss, w.U);   \
         break;
         EPC_VF(1) EPC_VF(2) EPC_VF(4) EPC_VF(8) EPC_VF(16)
 #undef EPC_VF
@@ -213,11 +212,10 @@ extern "C" int epc_vlad_head_fwd(const float* V, const float* colss, const void*
             return EPC_EINVAL;
     }
     EPC_CHECK_LAUNCH();
-    const int slices = kh / HSL;
-    hipLaunchKernelGGL(hidden_gemm_kernel, dim3(8, slices, (num_clouds + 63) / 64), dim3(64), 0, st, U, Hw,
-                       num_clouds, kh, Yp);
+    hipLaunchKernelGGL(hidden_gemm_kernel, dim3(8, slices, (num_clouds + 63) / 64), dim3(64), 0, st, w.U, Hw,
+                       num_clouds, kh, w.Yp);
     EPC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(head_finish_kernel, dim3(num_clouds), dim3(1024), 0, st, Yp, slices, num_clouds, tail,
+    hipLaunchKernelGGL(head_finish_kernel, dim3(num_clouds), dim3(1024), 0, st, w.Yp, slices, num_clouds, tail,
                        groups, status, out);
     EPC_CHECK_LAUNCH();
     return EPC_OK;

@@ -48,7 +48,6 @@ struct mp_ws {
     int32_t* group;
     unsigned long long mask;   // cap - 1
 };
-static inline size_t mp_round16(size_t n) { return (n + 15) & ~(size_t)15; }
 static inline unsigned long long mp_cap(long long max_voxels) {
     unsigned long long cap = 1;
     while (cap < 2ull * (unsigned long long)max_voxels + 1) cap <<= 1;
@@ -56,21 +55,13 @@ static inline unsigned long long mp_cap(long long max_voxels) {
 }
 static inline long long mp_tiles(long long num_rows) { return (num_rows + MP_TILE - 1) / MP_TILE; }
 static inline long long mp_groups(long long num_rows) { return (mp_tiles(num_rows) + MP_GROUP - 1) / MP_GROUP; }
-static size_t mp_ws_bytes(long long num_rows, long long max_voxels) {
-    return MP_HEAD * sizeof(int32_t) + mp_cap(max_voxels) * sizeof(mp_slot) + mp_round16((size_t)num_rows * 4) +
-           mp_round16((size_t)mp_tiles(num_rows) * 4) + mp_round16((size_t)mp_groups(num_rows) * 4);
-}
-static mp_ws mp_carve(void* workspace, long long num_rows, long long max_voxels) {
-    mp_ws w;
+// the regions of mp_ws in `workspace`, or (workspace NULL) only their total: the head and the table as they are, the rest rounded up to 16 bytes
+struct mp_layout_t { mp_ws ws; size_t bytes; };
+static mp_layout_t mp_layout(void* workspace, long long num_rows, long long max_voxels) {
+    epc_carver c(workspace);
     const unsigned long long cap = mp_cap(max_voxels);
-    char* p = reinterpret_cast<char*>(workspace);
-    w.head = reinterpret_cast<int32_t*>(p), p += MP_HEAD * sizeof(int32_t);
-    w.table = reinterpret_cast<mp_slot*>(p), p += cap * sizeof(mp_slot);
-    w.row_slot = reinterpret_cast<int32_t*>(p), p += mp_round16((size_t)num_rows * 4);
-    w.tile = reinterpret_cast<int32_t*>(p), p += mp_round16((size_t)mp_tiles(num_rows) * 4);
-    w.group = reinterpret_cast<int32_t*>(p);
-    w.mask = cap - 1;
-    return w;
+    return {{c.take<int32_t>(MP_HEAD), c.take<mp_slot>(cap), c.take<int32_t>((size_t)num_rows, 16), c.take<int32_t>((size_t)mp_tiles(num_rows), 16),
+             c.take<int32_t>((size_t)mp_groups(num_rows), 16), cap - 1}, c.bytes()};
 }
 
 struct mp_params {
@@ -298,7 +289,7 @@ static bool mp_supported(long long num_rows, int num_clouds, long long max_voxel
 
 extern "C" size_t epcnet_map_fuse_workspace_bytes(long long num_rows, int num_clouds, long long max_voxels) {
     if (!mp_supported(num_rows, num_clouds, max_voxels)) return 0;
-    return mp_ws_bytes(num_rows, max_voxels);
+    return mp_layout(nullptr, num_rows, max_voxels).bytes;
 }
 
 extern "C" int epcnet_map_fuse(const float* points, const int32_t* offsets, long long num_rows, int num_clouds, const double* poses,
@@ -319,7 +310,7 @@ extern "C" int epcnet_map_fuse(const float* points, const int32_t* offsets, long
     pr.step = voxel / 4096.0;
     pr.min_count = (long long)min_count;
     hipStream_t st = (hipStream_t)stream;
-    const mp_ws ws = mp_carve(workspace, num_rows, max_voxels);
+    const mp_ws ws = mp_layout(workspace, num_rows, max_voxels).ws;
     const long long tiles = mp_tiles(num_rows), groups = mp_groups(num_rows);
     if (int rc = scan_clear_words_launch(ws.head, MP_HEAD, st, __func__)) return rc;
     const unsigned long long clear_blocks = (ws.mask + MP_THREADS) / MP_THREADS;             // cap / MP_THREADS, at least 1

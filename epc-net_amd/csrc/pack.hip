@@ -7,8 +7,6 @@
 
 #define BN_EPS 1e-3f
 
-static inline size_t align64(size_t v) { return (v + 63) / 64 * 64; }
-
 struct StageLayout {
     size_t off[8];  // float offsets of stages 0..6, off[7] = total
     size_t guard;   // 64 floats after the stages: word 0 = max |packed 16-bit operand| bit pattern (fp16 range guard)
@@ -35,21 +33,21 @@ static StageLayout stage_layout(const epc_cfg* c) {
     size_t o = 0;
     const int nblocks = c->arch == EPC_ARCH_EPC_NET ? 4 : 2;
     L.off[0] = o;
-    o += align64(EPC_CONV1_PACK_FLOATS);
+    o += epc_align_up(EPC_CONV1_PACK_FLOATS, 64);
     for (int b = 1; b <= 4; ++b) {
         L.off[b] = o;
-        if (b <= nblocks) o += align64(EPC_BLOCK_PACK_FLOATS_S);
+        if (b <= nblocks) o += epc_align_up(EPC_BLOCK_PACK_FLOATS_S, 64);
     }
     L.off[5] = o;
     if (c->arch == EPC_ARCH_EPC_NET) {
-        o += align64((size_t)256 * 1024 + 1024 + 1024 * 64 + 128 + 1024);   // W5, b5, Wc, cluster_bn, inverse column scales
+        o += epc_align_up((size_t)256 * 1024 + 1024 + 1024 * 64 + 128 + 1024, 64);   // W5, b5, Wc, cluster_bn, inverse column scales
         L.off[6] = o;
         const size_t kh = 65536 / c->groups;
-        o += align64((size_t)65536 + kh * 256 + 512 + 65536 + 512);
+        o += epc_align_up((size_t)65536 + kh * 256 + 512 + 65536 + 512, 64);
     } else {
-        o += align64((size_t)128 * 1024 + 1024 + 1024);                    // W5, b5, inverse column scales
+        o += epc_align_up((size_t)128 * 1024 + 1024 + 1024, 64);                    // W5, b5, inverse column scales
         L.off[6] = o;
-        o += align64((size_t)1024 * 256 + 256);
+        o += epc_align_up((size_t)1024 * 256 + 256, 64);
     }
     L.guard = o;
     o += 64;

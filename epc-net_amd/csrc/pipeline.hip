@@ -4,8 +4,6 @@
 //                                               -> conv5+maxpool -> fc head               (EPC-Net-L)
 #include "common.h"
 
-static inline size_t al(size_t v) { return (v + 255) / 256 * 256; }
-
 static int micro_batch(const epc_cfg* c, int num_clouds) {
     int mb = c->micro_batch > 0 ? c->micro_batch : (c->arch == EPC_ARCH_EPC_NET ? 64 : 256);
     return num_clouds < mb ? num_clouds : mb;
@@ -24,7 +22,7 @@ static WsLayout ws_layout(const epc_cfg* c, int mb) {
     size_t o = 0;
     auto take = [&](size_t bytes) {
         size_t at = o;
-        o += al(bytes);
+        o += epc_align_up(bytes, 256);
         return at;
     };
     w.status = take((size_t)mb * 4);   // per-cloud EPC_STATUS_* words: offset 0 (epc_net_last_status)

@@ -31,7 +31,6 @@
 
 typedef float rg_f32x2 __attribute__((ext_vector_type(2)));
 
-static inline size_t rg_align(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline int rg_chunks(int n) { return (n + RG_CHUNK - 1) / RG_CHUNK; }
 
 // ---- launch 1: the pairs -----------------------------------------------------------------------------------------------------------------
@@ -345,16 +344,17 @@ static bool rg_shape_ok(int num_pairs, int num_seeds, int n) {
     return num_pairs >= 0 && num_pairs <= RG_MAX_PAIRS && num_seeds >= 1 && num_seeds <= RG_MAX_SEEDS && n >= 32 && n <= RG_MAX_N &&
            n % 32 == 0;
 }
-// the workspace: sums (P, H, chunks, 17) f64 | cur (P, 12) f64 | state (P, 4) i32 | run_a (P, H) i32 | run_b (P) i32
-static size_t rg_sums_bytes(int num_pairs, int num_seeds, int n) {
-    return rg_align((size_t)num_pairs * num_seeds * rg_chunks(n) * RG_SUMS * sizeof(double));
+// the workspace: sums (P, H, chunks, 17) f64 | cur (P, 12) f64 | state (P, 4) i32 | run_a (P, H) i32 | run_b (P) i32, each rounded up to 16 bytes
+struct rg_ws { double *sums, *cur; int32_t *state, *run_a, *run_b; size_t bytes; };
+static rg_ws rg_layout(void* base, int num_pairs, int num_seeds, int n) {
+    epc_carver c(base);
+    const size_t P = (size_t)num_pairs;
+    return {c.take<double>(P * num_seeds * rg_chunks(n) * RG_SUMS, 16), c.take<double>(P * 12, 16), c.take<int32_t>(P * RG_STATE, 16),
+            c.take<int32_t>(P * num_seeds, 16), c.take<int32_t>(P, 16), c.bytes()};
 }
 
 extern "C" size_t epcnet_pair_register_workspace_bytes(int num_pairs, int num_seeds, int n) {
-    if (!rg_shape_ok(num_pairs, num_seeds, n)) return 0;
-    const size_t P = (size_t)num_pairs;
-    return rg_sums_bytes(num_pairs, num_seeds, n) + rg_align(P * 12 * sizeof(double)) + rg_align(P * RG_STATE * sizeof(int32_t)) +
-           rg_align(P * num_seeds * sizeof(int32_t)) + rg_align(P * sizeof(int32_t));
+    return rg_shape_ok(num_pairs, num_seeds, n) ? rg_layout(nullptr, num_pairs, num_seeds, n).bytes : 0;
 }
 
 extern "C" int epcnet_pair_register(const float* clouds, int num_clouds, int n, const int32_t* pairs, int num_pairs, const double* seeds,
@@ -372,33 +372,23 @@ extern "C" int epcnet_pair_register(const float* clouds, int num_clouds, int n, 
     EPC_CHECK_WORKSPACE(workspace, workspace_bytes, epcnet_pair_register_workspace_bytes(num_pairs, num_seeds, n));
     const float g = (float)(max_dist * max_dist);
     const float gate2 = g < FLT_MAX ? g : FLT_MAX;
-    const size_t P = (size_t)num_pairs;
     const int chunks = rg_chunks(n);
-    char* w = (char*)workspace;
-    double* sums = (double*)w;
-    w += rg_sums_bytes(num_pairs, num_seeds, n);
-    double* cur = (double*)w;
-    w += rg_align(P * 12 * sizeof(double));
-    int32_t* state = (int32_t*)w;
-    w += rg_align(P * RG_STATE * sizeof(int32_t));
-    int32_t* run_a = (int32_t*)w;
-    w += rg_align(P * num_seeds * sizeof(int32_t));
-    int32_t* run_b = (int32_t*)w;
+    const rg_ws w = rg_layout(workspace, num_pairs, num_seeds, n);
     hipStream_t st = (hipStream_t)stream;
     const dim3 solve_grid((num_pairs + 63) / 64);
-    hipLaunchKernelGGL(rg_prep_kernel, dim3(num_pairs), dim3(256), 0, st, clouds, num_clouds, n, pairs, seeds, num_seeds, state, run_a, cur);
+    hipLaunchKernelGGL(rg_prep_kernel, dim3(num_pairs), dim3(256), 0, st, clouds, num_clouds, n, pairs, seeds, num_seeds, w.state, w.run_a, w.cur);
     // stage A: a pass per seed (under cur, the identity, where there are no seeds), the choice, and the first solve
-    hipLaunchKernelGGL(rg_corr_kernel, dim3(num_pairs, num_seeds, chunks), dim3(RG_CHUNK), 0, st, clouds, n, pairs, seeds ? seeds : cur, run_a,
-                       gate2, sums);
-    hipLaunchKernelGGL(rg_solve_kernel, solve_grid, dim3(64), 0, st, sums, num_pairs, num_seeds, chunks, seeds, run_a, min_pairs, 1,
-                       iterations > 0 ? 1 : 0, iterations > 0 ? 0 : 1, state, run_b, cur, pose, fit, info, status);
+    hipLaunchKernelGGL(rg_corr_kernel, dim3(num_pairs, num_seeds, chunks), dim3(RG_CHUNK), 0, st, clouds, n, pairs, seeds ? seeds : w.cur, w.run_a,
+                       gate2, w.sums);
+    hipLaunchKernelGGL(rg_solve_kernel, solve_grid, dim3(64), 0, st, w.sums, num_pairs, num_seeds, chunks, seeds, w.run_a, min_pairs, 1,
+                       iterations > 0 ? 1 : 0, iterations > 0 ? 0 : 1, w.state, w.run_b, w.cur, pose, fit, info, status);
     EPC_CHECK_LAUNCH();
     // stage B's further passes, then the final pass: all under cur
     for (int it = 1; it <= iterations; ++it) {
         const int last = it == iterations;
-        hipLaunchKernelGGL(rg_corr_kernel, dim3(num_pairs, 1, chunks), dim3(RG_CHUNK), 0, st, clouds, n, pairs, cur, run_b, gate2, sums);
-        hipLaunchKernelGGL(rg_solve_kernel, solve_grid, dim3(64), 0, st, sums, num_pairs, 1, chunks, seeds, run_a, min_pairs, 0, last ? 0 : 1,
-                           last, state, run_b, cur, pose, fit, info, status);
+        hipLaunchKernelGGL(rg_corr_kernel, dim3(num_pairs, 1, chunks), dim3(RG_CHUNK), 0, st, clouds, n, pairs, w.cur, w.run_b, gate2, w.sums);
+        hipLaunchKernelGGL(rg_solve_kernel, solve_grid, dim3(64), 0, st, w.sums, num_pairs, 1, chunks, seeds, w.run_a, min_pairs, 0, last ? 0 : 1,
+                           last, w.state, w.run_b, w.cur, pose, fit, info, status);
         EPC_CHECK_LAUNCH();
     }
     return EPC_OK;

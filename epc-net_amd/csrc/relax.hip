@@ -30,7 +30,6 @@ enum { RX_TE = 0, RX_ACTIVE = 1, RX_FAIL = 2, RX_USED = 3, RX_FLAGS = 4 };
 // element k of item i of a structure-of-arrays buffer of `stride` items
 #define RX_AT(buf, k, i, stride) (buf)[(size_t)(k) * (size_t)(stride) + (size_t)(i)]
 
-static inline size_t rx_align(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline int rx_blocks(int n) { return (n + RX_BLOCK - 1) / RX_BLOCK; }
 
 // ---- the arithmetic of the definition ------------------------------------------------------------------------------------------------------
@@ -746,17 +745,17 @@ struct rx_ws {
 };
 static rx_ws rx_layout(void* base, int T, int L) {
     rx_ws w;
-    char* at = (char*)base;
+    epc_carver c(base);
     const size_t t = (size_t)T, l = (size_t)L;
-    auto f64 = [&](size_t n) { double* q = (double*)at; at += rx_align(n * sizeof(double)); return q; };
-    auto i32 = [&](size_t n) { int32_t* q = (int32_t*)at; at += rx_align(n * sizeof(int32_t)); return q; };
+    auto f64 = [&](size_t n) { return c.take<double>(n, 16); };
+    auto i32 = [&](size_t n) { return c.take<int32_t>(n, 16); };
     w.R = f64(9 * t), w.c = f64(3 * t), w.Z = f64(12 * t), w.cJ = f64(27 * t), w.cb = f64(6 * t), w.cL = f64(21 * t);
     w.x = f64(6 * t), w.r = f64(6 * t), w.p = f64(6 * t), w.z = f64(6 * t), w.hp = f64(6 * t), w.eta = f64(6 * t), w.sa = f64(6 * t), w.sg = f64(6 * t);
     w.lJ = f64(27 * l), w.U = f64(6 * l);
     w.tot_a = f64(6 * RX_MAX_BLOCKS), w.tot_g = f64(6 * RX_MAX_BLOCKS);
     w.part_php = f64(RX_MAX_BLOCKS), w.part_rz = f64(2 * RX_MAX_BLOCKS), w.part_chain = f64(RX_MAX_BLOCKS), w.part_loops = f64(RX_MAX_LBLOCKS);
     w.flags = i32(RX_FLAGS), w.dead = i32(4096 + 2), w.start = i32(t), w.count = i32(t), w.blocktot = i32(RX_MAX_BLOCKS), w.entries = i32(2 * l);
-    w.bytes = (size_t)(at - (char*)base);
+    w.bytes = c.bytes();
     return w;
 }
 

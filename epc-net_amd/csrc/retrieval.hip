@@ -117,11 +117,17 @@ static int rt_chunk(int num_db, int num_q) {
     return (int)(per < num_q ? per : num_q);
 }
 
-extern "C" size_t epc_pairwise_topk_workspace_bytes(int num_db, int num_q) {
-    if (num_db <= 0 || num_q <= 0) return 0;
+// the workspace: S (ch, num_db) | dn (num_db) | qn (num_q) | flag (num_q) | dn_max (1), each rounded up to 256 bytes; ch = queries per pass
+struct rt_ws { int ch; float *S, *dn, *qn; int32_t* flag; float* dn_max; size_t bytes; };
+static rt_ws rt_layout(void* base, int num_db, int num_q) {
+    epc_carver c(base);
     const int ch = rt_chunk(num_db, num_q);
-    return rt_align((size_t)ch * num_db * 4) + rt_align((size_t)num_db * 4) + rt_align((size_t)num_q * 4) + rt_align((size_t)num_q * 4) +
-           rt_align(4);
+    return {ch, c.take<float>((size_t)ch * num_db, 256), c.take<float>(num_db, 256), c.take<float>(num_q, 256), c.take<int32_t>(num_q, 256),
+            c.take<float>(1, 256), c.bytes()};
+}
+
+extern "C" size_t epc_pairwise_topk_workspace_bytes(int num_db, int num_q) {
+    return num_db > 0 && num_q > 0 ? rt_layout(nullptr, num_db, num_q).bytes : 0;
 }
 
 extern "C" int epc_pairwise_topk_ws(const float* database, int num_db, const float* queries, int num_q, int dim, int k,
@@ -135,21 +141,12 @@ extern "C" int epc_pairwise_topk_ws(const float* database, int num_db, const flo
         epc_set_error("epc_pairwise_topk_ws: workspace too small");
         return EPC_ENOMEM;
     }
-    const int ch = rt_chunk(num_db, num_q);
-    char* w = (char*)workspace;
-    float* S = (float*)w;
-    w += rt_align((size_t)ch * num_db * 4);
-    float* dn = (float*)w;
-    w += rt_align((size_t)num_db * 4);
-    float* qn = (float*)w;
-    w += rt_align((size_t)num_q * 4);
-    int32_t* flag = (int32_t*)w;
-    w += rt_align((size_t)num_q * 4);
-    float* dn_max = (float*)w;
+    const rt_ws w = rt_layout(workspace, num_db, num_q);
+    const int ch = w.ch;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(rownorm2_kernel, dim3((num_db + 3) / 4), dim3(256), 0, st, database, num_db, dim, dn);
-    hipLaunchKernelGGL(rownorm2_kernel, dim3((num_q + 3) / 4), dim3(256), 0, st, queries, num_q, dim, qn);
-    hipLaunchKernelGGL(finite_max_kernel, dim3(1), dim3(1024), 0, st, dn, num_db, dn_max);
+    hipLaunchKernelGGL(rownorm2_kernel, dim3((num_db + 3) / 4), dim3(256), 0, st, database, num_db, dim, w.dn);
+    hipLaunchKernelGGL(rownorm2_kernel, dim3((num_q + 3) / 4), dim3(256), 0, st, queries, num_q, dim, w.qn);
+    hipLaunchKernelGGL(finite_max_kernel, dim3(1), dim3(1024), 0, st, w.dn, num_db, w.dn_max);
     EPC_CHECK_LAUNCH();
     const int in_lds = (size_t)num_db * 4 <= 149 * 1024;
     const size_t lds_bytes = (in_lds ? (((size_t)num_db + 3) & ~(size_t)3) * 4 : 0) + 4 * 64 * 4;   // the row (if it fits) + the selection's 4 x 64 words
@@ -158,10 +155,10 @@ extern "C" int epc_pairwise_topk_ws(const float* database, int num_db, const flo
         const int nq = (num_q - q0) < ch ? (num_q - q0) : ch;
         const float* Qc = queries + (size_t)q0 * dim;
         hipLaunchKernelGGL(pairdist_gemm_kernel, dim3((num_db + 127) / 128, (nq + 127) / 128), dim3(256), 0, st, Qc, database,
-                           qn + q0, dn, nq, num_db, dim, S);
-        hipLaunchKernelGGL(select_rerank_kernel, dim3(nq), dim3(64), lds_bytes, st, S, Qc, database, qn + q0, dn_max, num_db, dim, k,
-                           in_lds, idx + (size_t)q0 * k, dist + (size_t)q0 * k, flag + q0);
-        hipLaunchKernelGGL(exact_fallback_kernel, dim3(nq), dim3(64), 0, st, S, Qc, database, num_db, dim, k, flag + q0,
+                           w.qn + q0, w.dn, nq, num_db, dim, w.S);
+        hipLaunchKernelGGL(select_rerank_kernel, dim3(nq), dim3(64), lds_bytes, st, w.S, Qc, database, w.qn + q0, w.dn_max, num_db, dim, k,
+                           in_lds, idx + (size_t)q0 * k, dist + (size_t)q0 * k, w.flag + q0);
+        hipLaunchKernelGGL(exact_fallback_kernel, dim3(nq), dim3(64), 0, st, w.S, Qc, database, num_db, dim, k, w.flag + q0,
                            idx + (size_t)q0 * k, dist + (size_t)q0 * k);
         EPC_CHECK_LAUNCH();
     }
@@ -209,7 +206,7 @@ __global__ __launch_bounds__(64) void mine_select_kernel(const float* __restrict
 
 extern "C" size_t epc_mine_topk_workspace_bytes(int num_q, int max_cand) {
     if (num_q <= 0 || max_cand <= 0) return 0;
-    return rt_align((size_t)num_q * max_cand * sizeof(float));
+    return epc_align_up((size_t)num_q * max_cand * sizeof(float), 256);
 }
 
 extern "C" int epc_mine_topk(const float* table, int num_rows, int dim, const float* queries, int num_q, const int32_t* cand,

@@ -7,8 +7,6 @@
 #define RT_EXTRA 8          // candidates beyond k whose GEMM distances bracket the answer
 #define RT_MAXC 64          // k + RT_EXTRA <= one lane per candidate
 
-static inline size_t rt_align(size_t v) { return (v + 255) / 256 * 256; }
-
 // exact squared distance sum_c (q_c - d_c)^2: sequential over c, one rounding per operation.  ONE definition for every kernel under the
 // bit-for-bit contract of epc_pairwise_topk (the first form, the re-rank and the fallback of the workspace form, the mining distances,
 // the prefix search)

@@ -131,12 +131,20 @@ static bool rv_shape_ok(int num_db, int num_q, int pass_queries) {
            (pass_queries == 0 || (pass_queries >= RV_TILE && pass_queries <= RV_MAX_ROWS && pass_queries % RV_TILE == 0));
 }
 
+// the workspace: S (min(ch, num_q), num_db) | dn (num_db) | qn (num_q) | flag (num_q) | tile_pmax (tiles) | dn_max and fail (a word each,
+// one region), each region rounded up to 256 bytes; ch = queries per pass, tiles of RV_TILE queries
+struct rv_ws { int ch, tiles; float *S, *dn, *qn; int32_t *flag, *tile_pmax; float* dn_max; int32_t* fail; size_t bytes; };
+static rv_ws rv_layout(void* base, int num_db, int num_q, int pass_queries) {
+    epc_carver c(base);
+    const int ch = rv_pass(num_db, pass_queries), tiles = (num_q + RV_TILE - 1) / RV_TILE;
+    rv_ws w = {ch, tiles, c.take<float>((size_t)(ch < num_q ? ch : num_q) * num_db, 256), c.take<float>(num_db, 256), c.take<float>(num_q, 256),
+               c.take<int32_t>(num_q, 256), c.take<int32_t>(tiles, 256), c.take<float>(2, 256), nullptr, c.bytes()};
+    if (w.dn_max) w.fail = reinterpret_cast<int32_t*>(w.dn_max + 1);
+    return w;
+}
+
 extern "C" size_t epcnet_revisit_workspace_bytes(int num_db, int num_q, int pass_queries) {
-    if (!rv_shape_ok(num_db, num_q, pass_queries)) return 0;
-    const int ch = rv_pass(num_db, pass_queries);
-    const size_t rows = (size_t)(ch < num_q ? ch : num_q);
-    return rt_align(rows * num_db * 4) + rt_align((size_t)num_db * 4) + rt_align((size_t)num_q * 4) + rt_align((size_t)num_q * 4) +
-           rt_align((size_t)((num_q + RV_TILE - 1) / RV_TILE) * 4) + rt_align(8);
+    return rv_shape_ok(num_db, num_q, pass_queries) ? rv_layout(nullptr, num_db, num_q, pass_queries).bytes : 0;
 }
 
 extern "C" int epcnet_revisit_search(const float* database, const double* db_along, int num_db, const float* queries, const double* q_along,
@@ -155,27 +163,14 @@ extern "C" int epcnet_revisit_search(const float* database, const double* db_alo
         epc_set_error("epcnet_revisit_search: workspace too small");
         return EPC_ENOMEM;
     }
-    const int ch = rv_pass(num_db, pass_queries);
-    const int tiles = (num_q + RV_TILE - 1) / RV_TILE;
-    char* w = (char*)workspace;
-    float* S = (float*)w;
-    w += rt_align((size_t)(ch < num_q ? ch : num_q) * num_db * 4);
-    float* dn = (float*)w;
-    w += rt_align((size_t)num_db * 4);
-    float* qn = (float*)w;
-    w += rt_align((size_t)num_q * 4);
-    int32_t* flag = (int32_t*)w;
-    w += rt_align((size_t)num_q * 4);
-    int32_t* tile_pmax = (int32_t*)w;
-    w += rt_align((size_t)tiles * 4);
-    float* dn_max = (float*)w;
-    int32_t* fail = (int32_t*)(w + 4);
+    const rv_ws w = rv_layout(workspace, num_db, num_q, pass_queries);
+    const int ch = w.ch;
     hipStream_t st = (hipStream_t)stream;
-    if (num_db > 0) hipLaunchKernelGGL(rv_rownorm2_kernel, dim3((num_db + 3) / 4), dim3(256), 0, st, database, num_db, dim, dn);
-    hipLaunchKernelGGL(rv_rownorm2_kernel, dim3((num_q + 3) / 4), dim3(256), 0, st, queries, num_q, dim, qn);
-    hipLaunchKernelGGL(rv_check_kernel, dim3(1), dim3(1024), 0, st, db_along, dn, num_db, dn_max, fail);
-    hipLaunchKernelGGL(rv_prefix_kernel, dim3(tiles), dim3(RV_TILE), 0, st, db_along, num_db, q_along, num_q, min_travel, fail, count,
-                       tile_pmax);
+    if (num_db > 0) hipLaunchKernelGGL(rv_rownorm2_kernel, dim3((num_db + 3) / 4), dim3(256), 0, st, database, num_db, dim, w.dn);
+    hipLaunchKernelGGL(rv_rownorm2_kernel, dim3((num_q + 3) / 4), dim3(256), 0, st, queries, num_q, dim, w.qn);
+    hipLaunchKernelGGL(rv_check_kernel, dim3(1), dim3(1024), 0, st, db_along, w.dn, num_db, w.dn_max, w.fail);
+    hipLaunchKernelGGL(rv_prefix_kernel, dim3(w.tiles), dim3(RV_TILE), 0, st, db_along, num_db, q_along, num_q, min_travel, w.fail, count,
+                       w.tile_pmax);
     EPC_CHECK_LAUNCH();
     const int in_lds = (size_t)num_db * 4 <= 149 * 1024;
     const size_t lds_bytes = (in_lds ? (((size_t)num_db + 3) & ~(size_t)3) * 4 : 0) + 4 * 64 * 4;   // the row (if it fits) + the selection's 4 x 64 words
@@ -185,10 +180,10 @@ extern "C" int epcnet_revisit_search(const float* database, const double* db_alo
         const float* Qc = queries + (size_t)q0 * dim;
         if (num_db > 0)
             hipLaunchKernelGGL(rv_pairdist_kernel, dim3((num_db + 127) / 128, (nq + RV_TILE - 1) / RV_TILE), dim3(256), 0, st, Qc, database,
-                               qn + q0, dn, tile_pmax + q0 / RV_TILE, nq, num_db, dim, S);
-        hipLaunchKernelGGL(rv_select_kernel, dim3(nq), dim3(64), lds_bytes, st, S, Qc, database, qn + q0, dn_max, count + q0, num_db, dim, k,
-                           in_lds, idx + (size_t)q0 * k, dist + (size_t)q0 * k, flag + q0);
-        hipLaunchKernelGGL(rv_fallback_kernel, dim3(nq), dim3(64), 0, st, S, Qc, database, count + q0, num_db, dim, k, flag + q0,
+                               w.qn + q0, w.dn, w.tile_pmax + q0 / RV_TILE, nq, num_db, dim, w.S);
+        hipLaunchKernelGGL(rv_select_kernel, dim3(nq), dim3(64), lds_bytes, st, w.S, Qc, database, w.qn + q0, w.dn_max, count + q0, num_db, dim, k,
+                           in_lds, idx + (size_t)q0 * k, dist + (size_t)q0 * k, w.flag + q0);
+        hipLaunchKernelGGL(rv_fallback_kernel, dim3(nq), dim3(64), 0, st, w.S, Qc, database, count + q0, num_db, dim, k, w.flag + q0,
                            idx + (size_t)q0 * k, dist + (size_t)q0 * k);
         EPC_CHECK_LAUNCH();
     }

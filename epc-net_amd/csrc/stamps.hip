@@ -24,8 +24,12 @@
 #define ST_PAIRS 32            // (scan, row range) pairs listed at a time; a tile with more of them takes several batches
 #define ST_HEAD 4              // workspace words in front: [0] the whole-call failure
 
-// the workspace: head (4 int32) | j (num_scans int32)
-static size_t st_ws_bytes(int num_scans) { return (ST_HEAD * sizeof(int32_t) + (size_t)num_scans * sizeof(int32_t) + 15) & ~(size_t)15; }
+// the workspace: head (4 int32) | j (num_scans int32), rounded up to 16 bytes (the head is 16 bytes itself)
+struct st_ws { int32_t *head, *scan_j; size_t bytes; };
+static st_ws st_layout(void* base, int num_scans) {
+    epc_carver c(base);
+    return {c.take<int32_t>(ST_HEAD), c.take<int32_t>(num_scans, 16), c.bytes()};
+}
 
 // ---- the definition -------------------------------------------------------------------------------------------------------------------
 // floor(num * 2^32 / den) for 0 <= num <= den < 2^31, den > 0: a float64 estimate (off by one at most) put right in integers
@@ -259,7 +263,7 @@ static bool st_supported(int num_scans, int num_poses, long long num_rows) {
 
 extern "C" size_t epcnet_deskew_workspace_bytes(int num_scans, int num_poses, long long num_rows) {
     if (!st_supported(num_scans, num_poses, num_rows)) return 0;
-    return st_ws_bytes(num_scans);
+    return st_layout(nullptr, num_scans).bytes;
 }
 
 static int st_blocks(long long n) { return (int)((n + ST_THREADS - 1) / ST_THREADS); }
@@ -301,23 +305,22 @@ extern "C" int epcnet_scan_deskew(const float* points, const int32_t* offsets, l
     EPC_CHECK_ARG(max_gap_ns >= 1 && max_gap_ns < 2147483648ll, "need 1 <= max_gap_ns < 2^31");
     EPC_CHECK_WORKSPACE(workspace, workspace_bytes, epcnet_deskew_workspace_bytes(num_scans, num_poses, num_rows));
     hipStream_t st = (hipStream_t)stream;
-    int32_t* head = reinterpret_cast<int32_t*>(workspace);
-    int32_t* scan_j = head + ST_HEAD;
-    if (int rc = scan_clear_words_launch(head, ST_HEAD, st, __func__)) return rc;
+    const st_ws w = st_layout(workspace, num_scans);
+    if (int rc = scan_clear_words_launch(w.head, ST_HEAD, st, __func__)) return rc;
     const int most = num_scans > num_poses ? num_scans : num_poses;
     hipLaunchKernelGGL(stamps_check_kernel, dim3(st_blocks(most)), dim3(ST_THREADS), 0, st, offsets, num_rows, num_scans, pose_time,
-                       num_poses, head);
+                       num_poses, w.head);
     EPC_CHECK_LAUNCH();
     if (num_scans > 0) {
         hipLaunchKernelGGL(stamps_scan_kernel, dim3(st_blocks(num_scans)), dim3(ST_THREADS), 0, st, scan_time, pose_time, pose, num_poses,
-                           max_gap_ns, (const int32_t*)head, 0, num_scans, scan_pose, status, scan_j);
+                           max_gap_ns, (const int32_t*)w.head, 0, num_scans, scan_pose, status, w.scan_j);
         EPC_CHECK_LAUNCH();
     }
     const int tiles = (int)((num_rows + ST_TILE - 1) / ST_TILE);
     if (point_dt && num_scans > 0 && tiles > 0) {
         hipLaunchKernelGGL(stamps_row_kernel, dim3(tiles), dim3(ST_THREADS), 0, st, points, offsets, num_scans, point_dt, scan_time,
-                           pose_time, pose, num_poses, max_gap_ns, (const double*)scan_pose, (const int32_t*)head,
-                           (const int32_t*)scan_j, status, points_out);
+                           pose_time, pose, num_poses, max_gap_ns, (const double*)scan_pose, (const int32_t*)w.head,
+                           (const int32_t*)w.scan_j, status, points_out);
         EPC_CHECK_LAUNCH();
     }
     return EPC_OK;

@@ -582,6 +582,9 @@ __global__ __launch_bounds__(64 * VDF_WAVES, TAIL ? 2 : 3) void vlad_df_kernel(c
     }
 }
 
+// workgroups per cloud: VDF_WAVES tiles of 32 points each (the tail form leaves 2 x 1024 partials per workgroup)
+static int vdf_cloud_wgs(int n_points) { return ((n_points + 31) / 32 + VDF_WAVES - 1) / VDF_WAVES; }
+
 extern "C" size_t epc_vlad_df_packed_bytes(int num_clouds, int F) {
     return num_clouds > 0 && F > 0 ? (size_t)num_clouds * (F / 32) * VDF_CHUNK_U4 * sizeof(u32x4) : 0;
 }
@@ -597,8 +600,7 @@ extern "C" int epc_vlad_df(const float* a, const float* dz, const float* dvlad, 
                   "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(vlad_df_pack_kernel, dim3(F / 32, num_clouds), dim3(256), 0, st, dvlad, Wc, F, (u32x4*)packed);
-    const int tiles = (n_points + 31) / 32;
-    const int wgs = (tiles + VDF_WAVES - 1) / VDF_WAVES * num_clouds;   // (three workgroups per CU: every tile whole)
+    const int wgs = vdf_cloud_wgs(n_points) * num_clouds;   // (three workgroups per CU: every tile whole)
     const dim3 grid(wgs);
     if (pieces == 2) hipLaunchKernelGGL((vlad_df_kernel<2, false>), grid, dim3(64 * VDF_WAVES), 0, st, a, dz, (const u32x4*)packed, n_points, F, df, VdfTail{}, wgs, 1);
     else hipLaunchKernelGGL((vlad_df_kernel<1, false>), grid, dim3(64 * VDF_WAVES), 0, st, a, dz, (const u32x4*)packed, n_points, F, df, VdfTail{}, wgs, 1);
@@ -608,8 +610,7 @@ extern "C" int epc_vlad_df(const float* a, const float* dz, const float* dvlad, 
 
 extern "C" size_t epc_vlad_df_tail_partial_floats(int num_clouds, int n_points) {
     if (num_clouds <= 0 || n_points <= 0) return 0;
-    const size_t tiles = (n_points + 31) / 32;
-    return (size_t)num_clouds * ((tiles + VDF_WAVES - 1) / VDF_WAVES) * 2 * 1024;
+    return (size_t)num_clouds * vdf_cloud_wgs(n_points) * 2 * 1024;
 }
 
 extern "C" int epc_vlad_df_tail(const float* a, const float* dz, const float* dvlad, const float* Wc, int num_clouds, int n_points,
@@ -630,8 +631,7 @@ extern "C" int epc_vlad_df_tail(const float* a, const float* dz, const float* dv
                   "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(vlad_df_pack_kernel, dim3(F / 32, num_clouds), dim3(256), 0, st, dvlad, Wc, F, (u32x4*)packed);
-    const int tiles = (n_points + 31) / 32;
-    const int wgs = (tiles + VDF_WAVES - 1) / VDF_WAVES * num_clouds;
+    const int wgs = vdf_cloud_wgs(n_points) * num_clouds;
     int whole, parts;
     tail_split(wgs, 2 * epc_device_cu_count(), F / (32 * VDF_NT), whole, parts);   // (two workgroups per CU: launch bounds of the tail form)
     const dim3 grid(whole + (wgs - whole) * parts);

@@ -512,10 +512,15 @@ __global__ __launch_bounds__(256) void h16_expand_kernel(const unsigned* __restr
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------
 
-extern "C" size_t epc_h16_conv5_fwd_scratch_bytes(int rows) {
-    if (rows <= 0) return 0;
-    return (size_t)256 * 1024 * 2 + (size_t)((rows + 127) / 128) * 3 * 1024 * sizeof(float);
+// conv5's scratch: W5 packed (256 x 1024 bf16) | the moments' partials, 3 x 1024 per 128-row workgroup (wgs of them)
+struct h16_conv5_ws { int wgs; u32x4* pack; float* stats; size_t bytes; };
+static h16_conv5_ws h16_conv5_layout(void* base, int rows) {
+    epc_carver c(base);
+    const int wgs = (rows + 127) / 128;
+    return {wgs, c.take<u32x4>(256 * 1024 * 2 / sizeof(u32x4)), c.take<float>((size_t)wgs * 3 * 1024), c.bytes()};
 }
+
+extern "C" size_t epc_h16_conv5_fwd_scratch_bytes(int rows) { return rows > 0 ? h16_conv5_layout(nullptr, rows).bytes : 0; }
 
 extern "C" int epc_h16_conv5_fwd(const void* cat, int cat_is_bf16, const float* W5, const float* b5, int rows, void* z5, float* mean,
                                  float* var, void* scratch, size_t scratch_bytes, void* stream) {
@@ -524,14 +529,13 @@ extern "C" int epc_h16_conv5_fwd(const void* cat, int cat_is_bf16, const float* 
     EPC_CHECK_ARG(scratch_bytes >= epc_h16_conv5_fwd_scratch_bytes(rows), "scratch too small (epc_h16_conv5_fwd_scratch_bytes)");
     EPC_CHECK_ARG(epc_aligned16(cat) && epc_aligned16(z5) && epc_aligned16(scratch) && epc_aligned16(b5), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    h16_pack<1>(W5, 1024, 1, 0, 1, 256, 1024, 0, 4, scratch, st);
-    float* stats = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (size_t)256 * 1024 * 2);
-    const int wgs = (rows + 127) / 128;
+    const h16_conv5_ws w = h16_conv5_layout(scratch, rows);
+    h16_pack<1>(W5, 1024, 1, 0, 1, 256, 1024, 0, 4, w.pack, st);
     if (cat_is_bf16)
-        hipLaunchKernelGGL(h16_conv5_fwd_kernel<false>, dim3(wgs), dim3(256), 0, st, cat, rows, (const u32x4*)scratch, b5, (unsigned*)z5, stats);
+        hipLaunchKernelGGL(h16_conv5_fwd_kernel<false>, dim3(w.wgs), dim3(256), 0, st, cat, rows, (const u32x4*)w.pack, b5, (unsigned*)z5, w.stats);
     else
-        hipLaunchKernelGGL(h16_conv5_fwd_kernel<true>, dim3(wgs), dim3(256), 0, st, cat, rows, (const u32x4*)scratch, b5, (unsigned*)z5, stats);
-    epc_moments_finalize_launch(stats, wgs, 1024, rows, 128, b5, mean, var, stream);
+        hipLaunchKernelGGL(h16_conv5_fwd_kernel<true>, dim3(w.wgs), dim3(256), 0, st, cat, rows, (const u32x4*)w.pack, b5, (unsigned*)z5, w.stats);
+    epc_moments_finalize_launch(w.stats, w.wgs, 1024, rows, 128, b5, mean, var, stream);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
 }
@@ -573,9 +577,16 @@ extern "C" int epc_h16_colgemm(const void* z5, const float* mean5, const float* 
                                 stream);
 }
 
+// the tail's scratch: dvlad Wc^T packed (16 stages per cloud) | (sum du, sum du zhat) partials, 2 x 1024 per 128-row workgroup (`tiles` per cloud)
+struct h16_df_ws { int tiles; u32x4* pack; float* partials; size_t bytes; };
+static h16_df_ws h16_df_layout(void* base, int num_clouds, int n_points) {
+    epc_carver c(base);
+    const int tiles = (n_points + 127) / 128;
+    return {tiles, c.take<u32x4>((size_t)num_clouds * 16 * DF_STAGE_U4), c.take<float>((size_t)num_clouds * tiles * 2 * 1024), c.bytes()};
+}
+
 extern "C" size_t epc_h16_df_tail_scratch_bytes(int num_clouds, int n_points) {
-    if (num_clouds <= 0 || n_points <= 0) return 0;
-    return (size_t)num_clouds * 16 * DF_STAGE_U4 * sizeof(u32x4) + (size_t)num_clouds * ((n_points + 127) / 128) * 2 * 1024 * sizeof(float);
+    return num_clouds > 0 && n_points > 0 ? h16_df_layout(nullptr, num_clouds, n_points).bytes : 0;
 }
 
 // du (rows, 1024) bf16 and dbeta_dgamma (2, 1024) = (sum du, sum du zhat): see h16_df_tail_kernel
@@ -591,12 +602,11 @@ extern "C" int epc_h16_df_tail(const float* a, const float* dz, const float* dvl
                       epc_aligned16(scratch) && epc_aligned16(dbeta_dgamma),
                   "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(h16_df_pack_kernel, dim3(16, num_clouds), dim3(256), 0, st, dvlad, Wc, (u32x4*)scratch);
-    float* partials = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (size_t)num_clouds * 16 * DF_STAGE_U4 * sizeof(u32x4));
-    const dim3 grid((n_points + 127) / 128, num_clouds);
-    const H16Tail tail{(const unsigned*)z5, rn, trow, H16Bn{mean5, var5, gamma5, beta5, eps}, partials};
-    hipLaunchKernelGGL(h16_df_tail_kernel, grid, dim3(256), 0, st, a, dz, (const u32x4*)scratch, n_points, (unsigned*)du, tail);
-    epc_partial_sum_wide_launch(partials, (int)(grid.x * grid.y), 2 * 1024, dbeta_dgamma, stream);
+    const h16_df_ws w = h16_df_layout(scratch, num_clouds, n_points);
+    hipLaunchKernelGGL(h16_df_pack_kernel, dim3(16, num_clouds), dim3(256), 0, st, dvlad, Wc, w.pack);
+    const H16Tail tail{(const unsigned*)z5, rn, trow, H16Bn{mean5, var5, gamma5, beta5, eps}, w.partials};
+    hipLaunchKernelGGL(h16_df_tail_kernel, dim3(w.tiles, num_clouds), dim3(256), 0, st, a, dz, (const u32x4*)w.pack, n_points, (unsigned*)du, tail);
+    epc_partial_sum_wide_launch(w.partials, w.tiles * num_clouds, 2 * 1024, dbeta_dgamma, stream);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
 }
@@ -614,12 +624,7 @@ extern "C" int epc_h16_bn_bwd_apply(const void* du, const void* z5, const float*
     return EPC_OK;
 }
 
-static int h16_dw5_splits(int rows) {
-    const int cus = epc_device_cu_count();
-    int s = max(1, cus / 4);                              // 4 column tiles per slice: one workgroup (eight waves) per CU
-    while (s > 1 && (rows + s - 1) / s < 64) s >>= 1;     // (short inputs: at least 64 rows per slice)
-    return s;
-}
+static int h16_dw5_splits(int rows) { return hx_dw5_splits(rows, 64); }
 
 extern "C" size_t epc_h16_conv5_dw_scratch_bytes(int rows) {
     return rows > 0 ? (size_t)h16_dw5_splits(rows) * 256 * 1024 * sizeof(float) : 0;

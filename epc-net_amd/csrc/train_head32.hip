@@ -336,10 +336,15 @@ __global__ __launch_bounds__(512, 1) void h32_dw5_kernel(const float* __restrict
 }
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------
-extern "C" size_t epc_h32_conv5_fwd_scratch_bytes(int rows) {
-    if (rows <= 0) return 0;
-    return (size_t)256 * 1024 * 4 + 1024 * sizeof(float) + (size_t)((rows + 127) / 128) * 3 * 1024 * sizeof(float);   // (>= the 256-row tiles' partials)
+// conv5's scratch: W5 packed (256 x 1024, two bf16 pieces) | inverse column scales (1024) | the moments' partials, 3 x 1024 per tile, with
+// room for 128-row tiles (>= the 256-row tiles' partials)
+struct h32_conv5_ws { u32x4* pack; float *inv_col, *stats; size_t bytes; };
+static h32_conv5_ws h32_conv5_layout(void* base, int rows) {
+    epc_carver c(base);
+    return {c.take<u32x4>(256 * 1024 * 4 / sizeof(u32x4)), c.take<float>(1024), c.take<float>((size_t)((rows + 127) / 128) * 3 * 1024), c.bytes()};
 }
+
+extern "C" size_t epc_h32_conv5_fwd_scratch_bytes(int rows) { return rows > 0 ? h32_conv5_layout(nullptr, rows).bytes : 0; }
 
 extern "C" int epc_h32_conv5_fwd(const float* cat, const float* W5, const float* b5, int rows, float* z5, float* mean, float* var,
                                  void* scratch, size_t scratch_bytes, void* stream) {
@@ -348,16 +353,14 @@ extern "C" int epc_h32_conv5_fwd(const float* cat, const float* W5, const float*
     EPC_CHECK_ARG(scratch_bytes >= epc_h32_conv5_fwd_scratch_bytes(rows), "scratch too small (epc_h32_conv5_fwd_scratch_bytes)");
     EPC_CHECK_ARG(epc_aligned16(cat) && epc_aligned16(z5) && epc_aligned16(scratch), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    u32x4* pack = (u32x4*)scratch;
-    float* inv_col = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (size_t)256 * 1024 * 4);
-    float* stats = inv_col + 1024;
-    hipLaunchKernelGGL(h32_pack_conv5_kernel, dim3(16, 2, 4), dim3(256), 0, st, W5, pack, inv_col);
+    const h32_conv5_ws w = h32_conv5_layout(scratch, rows);
+    hipLaunchKernelGGL(h32_pack_conv5_kernel, dim3(16, 2, 4), dim3(256), 0, st, W5, w.pack, w.inv_col);
     const int tile_rows = 32 * C32_WAVES, tiles = (rows + tile_rows - 1) / tile_rows;
     int whole, parts;
     tail_split(tiles, epc_device_cu_count(), 16, whole, parts);   // (one workgroup per CU)
-    hipLaunchKernelGGL(h32_conv5_fwd_kernel, dim3(whole + (tiles - whole) * parts), dim3(64 * C32_WAVES), 0, st, cat, rows, (const u32x4*)pack,
-                       inv_col, b5, z5, stats, whole, parts);
-    epc_moments_finalize_launch(stats, tiles, 1024, rows, tile_rows, b5, mean, var, stream);
+    hipLaunchKernelGGL(h32_conv5_fwd_kernel, dim3(whole + (tiles - whole) * parts), dim3(64 * C32_WAVES), 0, st, cat, rows, (const u32x4*)w.pack,
+                       w.inv_col, b5, z5, w.stats, whole, parts);
+    epc_moments_finalize_launch(w.stats, tiles, 1024, rows, tile_rows, b5, mean, var, stream);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
 }
@@ -398,12 +401,7 @@ extern "C" int epc_h32_conv5_dx_bn(const float* du, const float* z5, const float
     return hx_conv5_dx_bn<H32Arith>(du, z5, mean5, var5, gamma5, eps, dbeta, dgamma, W5, rows, dz5, dcat, scratch, scratch_bytes, stream);
 }
 
-static int h32_dw5_splits(int rows) {
-    const int cus = epc_device_cu_count();
-    int s = max(1, cus / 4);                              // 4 column tiles per slice: one workgroup (eight waves) per CU
-    while (s > 1 && (rows + s - 1) / s < 32) s >>= 1;     // (short inputs: at least 32 rows per slice)
-    return s;
-}
+static int h32_dw5_splits(int rows) { return hx_dw5_splits(rows, 32); }
 
 extern "C" size_t epc_h32_conv5_dw_scratch_bytes(int rows) {
     return rows > 0 ? (size_t)h32_dw5_splits(rows) * 256 * 1024 * sizeof(float) : 0;

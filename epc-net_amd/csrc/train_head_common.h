@@ -583,12 +583,20 @@ static inline int h16_splits(int num_clouds, int n_points, int tiles) {
         }                                                                                                \
     } while (0)
 
+// The assignment's scratch: the packed operand (nb of them: one, or one per cloud) | the moments' partials, 3 x 64 per tile, with room for
+// either tiling of the rows -- `tiles` of 128 rows per cloud, or (the shared-operand launch may take them) `tiles96` of 96 over all rows
+struct hx_assign_ws { int nb; size_t tiles, tiles96; void* pack; float* stats; size_t bytes; };
+template <typename A>
+static hx_assign_ws hx_assign_layout(void* base, int num_clouds, int n_points, int per_cloud_operand) {
+    epc_carver c(base);
+    const int nb = per_cloud_operand ? num_clouds : 1;
+    const size_t tiles = (size_t)num_clouds * ((n_points + 127) / 128), tiles96 = ((size_t)num_clouds * n_points + 95) / 96;
+    return {nb, tiles, tiles96, c.take<char>((size_t)nb * 1024 * 64 * A::ASSIGN_PACK_BYTES),
+            c.take<float>((tiles > tiles96 ? tiles : tiles96) * 3 * 64), c.bytes()};
+}
 template <typename A>
 static size_t hx_assign_scratch_bytes(int num_clouds, int n_points, int per_cloud_operand) {
-    if (num_clouds <= 0 || n_points <= 0) return 0;
-    const size_t pack = (size_t)(per_cloud_operand ? num_clouds : 1) * 1024 * 64 * A::ASSIGN_PACK_BYTES;
-    const size_t tiles = (size_t)num_clouds * ((n_points + 127) / 128), tiles96 = ((size_t)num_clouds * n_points + 95) / 96;
-    return pack + (tiles > tiles96 ? tiles : tiles96) * 3 * 64 * sizeof(float);   // (the shared-operand launch may tile the rows by 96)
+    return num_clouds > 0 && n_points > 0 ? hx_assign_layout<A>(nullptr, num_clouds, n_points, per_cloud_operand).bytes : 0;
 }
 
 // za = rn (relu(bn(z5)) B): B = Wc (1024, 64) shared (per_cloud_operand = 0: the forward's logits; rn and the batch moments of za are
@@ -607,25 +615,24 @@ static int hx_assign(const typename A::T* z5, const float* mean5, const float* v
                  "scratch too small (%s_assign_scratch_bytes)");
     HX_CHECK_ARG("assign", epc_aligned16(z5) && epc_aligned16(scratch) && epc_aligned16(out), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const int nb = per_cloud_operand ? num_clouds : 1;
-    h16_pack<A::P>(B, 64, 1, (long)1024 * 64, nb, 1024, 64, 1, A::KSC_ASSIGN, scratch, st);
-    float* stats = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + (size_t)nb * 1024 * 64 * A::ASSIGN_PACK_BYTES);
+    const hx_assign_ws w = hx_assign_layout<A>(scratch, num_clouds, n_points, per_cloud_operand);
+    h16_pack<A::P>(B, 64, 1, (long)1024 * 64, w.nb, 1024, 64, 1, A::KSC_ASSIGN, w.pack, st);
     const dim3 grid((n_points + 127) / 128, num_clouds);
     const H16Bn bn{mean5, var5, gamma5, beta5, eps};
     const long rows = (long)num_clouds * n_points;
     if (!per_cloud_operand && rows < (1L << 31) && rows_tile_waves((int)rows, A::ASSIGN_SLOTS * epc_device_cu_count()) == 3) {
         // one operand for every row: the tiles need not respect the clouds -- 96-row workgroups where they spread evenly over the CUs' slots
         // (18 x 4096 rows: 768 of them, three per CU; 576 of 128 rows leave a quarter of the CUs a third more)
-        const int wgs = (int)((rows + 95) / 96);
+        const int wgs = (int)w.tiles96;
         hipLaunchKernelGGL((hx_rowgemm_kernel<2, true, T, A::P, A::KSC_ASSIGN, false, 3>), dim3(wgs, 1), dim3(192), 0, st, z5, (int)rows,
-                           (const u32x4*)scratch, 0L, bn, out, rn_out, mean_out ? stats : nullptr, HxBnb<T>{});
-        if (mean_out) epc_moments_finalize_launch(stats, wgs, 64, (int)rows, 96, nullptr, mean_out, var_out, stream);
+                           (const u32x4*)w.pack, 0L, bn, out, rn_out, mean_out ? w.stats : nullptr, HxBnb<T>{});
+        if (mean_out) epc_moments_finalize_launch(w.stats, wgs, 64, (int)rows, 96, nullptr, mean_out, var_out, stream);
         HX_CHECK_LAUNCH("assign");
         return EPC_OK;
     }
-    hipLaunchKernelGGL((hx_rowgemm_kernel<2, true, T, A::P, A::KSC_ASSIGN>), grid, dim3(256), 0, st, z5, n_points, (const u32x4*)scratch,
-                       per_cloud_operand ? (long)(1024 * 64 * 2 * A::P / 16) : 0L, bn, out, rn_out, mean_out ? stats : nullptr, HxBnb<T>{});
-    if (mean_out) epc_moments_finalize_launch(stats, (int)(grid.x * grid.y), 64, num_clouds * n_points, 128, nullptr, mean_out, var_out, stream, n_points);
+    hipLaunchKernelGGL((hx_rowgemm_kernel<2, true, T, A::P, A::KSC_ASSIGN>), grid, dim3(256), 0, st, z5, n_points, (const u32x4*)w.pack,
+                       per_cloud_operand ? (long)(1024 * 64 * 2 * A::P / 16) : 0L, bn, out, rn_out, mean_out ? w.stats : nullptr, HxBnb<T>{});
+    if (mean_out) epc_moments_finalize_launch(w.stats, (int)w.tiles, 64, num_clouds * n_points, 128, nullptr, mean_out, var_out, stream, n_points);
     HX_CHECK_LAUNCH("assign");
     return EPC_OK;
 }
@@ -660,6 +667,14 @@ static int hx_colgemm(const typename A::T* z5, const float* mean5, const float* 
         hipLaunchKernelGGL(h16_partial_reduce_kernel, dim3((unsigned)(per / 4 / 256), 1), dim3(256), 0, st, (const float*)scratch, num_clouds * S, per, out);
     HX_CHECK_LAUNCH("colgemm");
     return EPC_OK;
+}
+
+// Row slices of dW5's product, a (256, 1024) f32 partial each: 4 column tiles per slice, one workgroup (eight waves) per CU; short inputs
+// keep at least `min_rows` rows per slice
+static inline int hx_dw5_splits(int rows, int min_rows) {
+    int s = max(1, epc_device_cu_count() / 4);
+    while (s > 1 && (rows + s - 1) / s < min_rows) s >>= 1;
+    return s;
 }
 
 template <typename A>

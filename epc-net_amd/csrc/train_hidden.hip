@@ -281,8 +281,9 @@ __global__ __launch_bounds__(256, 1) void hp_dw_kernel(const float* __restrict__
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------
 extern "C" int epc_hidden_proj_ok(int M, int K, int N) { return M >= 64 && M <= 32 * HP_MT && M % 4 == 0 && N == 256 && K >= 256 && K % 256 == 0; }
 
+static int hp_splits(int K) { return K / 256; }   // K-slices of the forward: an (M, 256) partial each
 extern "C" size_t epc_hidden_proj_scratch_bytes(int M, int K) {
-    return M > 0 && K > 0 ? (size_t)(K / 256) * M * 256 * sizeof(float) : 0;
+    return M > 0 && K > 0 ? (size_t)hp_splits(K) * M * 256 * sizeof(float) : 0;
 }
 
 #define HP_LAUNCH(kern, grid, lds, ...)                                                                   \
@@ -308,7 +309,7 @@ extern "C" int epc_hidden_proj_fwd(const float* X, const float* W, int M, int K,
     EPC_CHECK_ARG(scratch_bytes >= epc_hidden_proj_scratch_bytes(M, K), "scratch too small (epc_hidden_proj_scratch_bytes)");
     EPC_CHECK_ARG(epc_aligned16(X) && epc_aligned16(W) && epc_aligned16(Y) && epc_aligned16(scratch), "tensors must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const int MT = (M + 31) / 32, S = K / 256;
+    const int MT = (M + 31) / 32, S = hp_splits(K);
     const size_t stage = (size_t)32 * MT * HP_PITCH * sizeof(float), meet = (size_t)4 * HP_MT * 16 * 2 * 64 * sizeof(float);
     const size_t lds = stage > meet ? stage : meet;
     HP_LAUNCH(hp_fwd_kernel, dim3(4, S), lds, X, W, M, K, (float*)scratch);

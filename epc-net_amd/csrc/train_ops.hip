@@ -1216,10 +1216,15 @@ __global__ __launch_bounds__(256) void colreduce_finish_kernel(const float* __re
     }
 }
 
-extern "C" size_t epc_colreduce_workspace_bytes(int rows, int C) {
-    const size_t nb = (rows + CR_ROWS - 1) / CR_ROWS;
-    return CR_COUNTERS * sizeof(unsigned int) + 3 * nb * (size_t)C * sizeof(float);   // (linear_stats64: sum, sum of squares, pivot)
+// the column-reduction workspace: CR_COUNTERS unused words | the partials, 3 (linear_stats64: sum, sum of squares, pivot) x nb panels of
+// CR_ROWS rows x C
+struct cr_ws { int nb; unsigned int* counters; float* part; size_t bytes; };
+static cr_ws cr_layout(void* base, int rows, int C) {
+    epc_carver c(base);
+    const int nb = (rows + CR_ROWS - 1) / CR_ROWS;
+    return {nb, c.take<unsigned int>(CR_COUNTERS), c.take<float>(3 * (size_t)nb * (size_t)C), c.bytes()};
 }
+extern "C" size_t epc_colreduce_workspace_bytes(int rows, int C) { return cr_layout(nullptr, rows, C).bytes; }
 
 static int colreduce_check(const char* who, int rows, int C, const void* workspace, size_t workspace_bytes) {
     EPC_CHECK_ARG(rows > 0 && C > 0 && C % 4 == 0 && C <= 64 * CR_COUNTERS, "C must be a multiple of 4, at most 4096");
@@ -1257,8 +1262,7 @@ static int linear_stats64_impl(const float* x, BnParams xbn, const float* W, con
     EPC_CHECK_ARG(x && W && z && mean && var, "null pointer");
     EPC_CHECK_ARG(((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(z)) & 15) == 0, "x and z must be 16-byte aligned");
     if (int rc = colreduce_check("epc_linear_stats64: workspace too small", rows, 64, workspace, workspace_bytes)) return rc;
-    unsigned int* counters = (unsigned int*)workspace;
-    float* part = (float*)(counters + CR_COUNTERS);
+    float* const part = cr_layout(workspace, rows, 64).part;
     const int wgs = (rows + LS_ROWS_PER_WG - 1) / LS_ROWS_PER_WG;   // <= the 256-row panels the workspace is sized for
     hipLaunchKernelGGL(linear_stats64_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, x, xbn, W, bias, rows, z, part);
     launch_moments_finalize(part, wgs, 64, rows, LS_ROWS_PER_WG, bias, mean, var, (hipStream_t)stream);
@@ -1271,12 +1275,10 @@ extern "C" int epc_col_moments(const float* x, int rows, int C, float* mean, flo
                                size_t workspace_bytes, void* stream) {
     EPC_CHECK_ARG(x && mean && var, "null pointer");
     if (int rc = colreduce_check("epc_col_moments: workspace too small", rows, C, workspace, workspace_bytes)) return rc;
-    const int nb = (rows + CR_ROWS - 1) / CR_ROWS;
-    unsigned int* counters = (unsigned int*)workspace;
-    float* part = (float*)(counters + CR_COUNTERS);
-    hipLaunchKernelGGL(colreduce_kernel<1>, dim3((C + 63) / 64, nb), dim3(256), 0, (hipStream_t)stream, x, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, 0.f, 0, rows, C, 1.0f / rows, part);
-    hipLaunchKernelGGL(colreduce_finish_kernel<1>, dim3((C + CF_COLS - 1) / CF_COLS), dim3(256), 0, (hipStream_t)stream, part, x, nb, C,
+    const cr_ws w = cr_layout(workspace, rows, C);
+    hipLaunchKernelGGL(colreduce_kernel<1>, dim3((C + 63) / 64, w.nb), dim3(256), 0, (hipStream_t)stream, x, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, 0.f, 0, rows, C, 1.0f / rows, w.part);
+    hipLaunchKernelGGL(colreduce_finish_kernel<1>, dim3((C + CF_COLS - 1) / CF_COLS), dim3(256), 0, (hipStream_t)stream, w.part, x, w.nb, C,
                        1.0f / rows, mean, var);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
@@ -1287,12 +1289,10 @@ extern "C" int epc_col_sum(const float* x, int rows, int C, float* out, void* wo
                            void* stream) {
     EPC_CHECK_ARG(x && out, "null pointer");
     if (int rc = colreduce_check("epc_col_sum: workspace too small", rows, C, workspace, workspace_bytes)) return rc;
-    const int nb = (rows + CR_ROWS - 1) / CR_ROWS;
-    unsigned int* counters = (unsigned int*)workspace;
-    float* part = (float*)(counters + CR_COUNTERS);
-    hipLaunchKernelGGL(colreduce_kernel<0>, dim3((C + 63) / 64, nb), dim3(256), 0, (hipStream_t)stream, x, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, 0.f, 0, rows, C, 1.0f, part);
-    hipLaunchKernelGGL(colreduce_finish_kernel<0>, dim3((C + CF_COLS - 1) / CF_COLS), dim3(256), 0, (hipStream_t)stream, part, x, nb, C, 1.0f,
+    const cr_ws w = cr_layout(workspace, rows, C);
+    hipLaunchKernelGGL(colreduce_kernel<0>, dim3((C + 63) / 64, w.nb), dim3(256), 0, (hipStream_t)stream, x, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, 0.f, 0, rows, C, 1.0f, w.part);
+    hipLaunchKernelGGL(colreduce_finish_kernel<0>, dim3((C + CF_COLS - 1) / CF_COLS), dim3(256), 0, (hipStream_t)stream, w.part, x, w.nb, C, 1.0f,
                        out, (float*)nullptr);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
@@ -1602,9 +1602,8 @@ int epc_partial_sum_wide_launch(const float* partials, int P, int E, float* out,
     return EPC_OK;
 }
 
-extern "C" size_t epc_bn_relu_rownorm_bwd_partial_floats(int rows) {
-    return rows > 0 ? (size_t)((rows + BRB_ROWS - 1) / BRB_ROWS) * 2 * BRN_C : 0;
-}
+static int brb_wgs(int rows) { return (rows + BRB_ROWS - 1) / BRB_ROWS; }   // workgroups = (2, BRN_C) partials
+extern "C" size_t epc_bn_relu_rownorm_bwd_partial_floats(int rows) { return rows > 0 ? (size_t)brb_wgs(rows) * 2 * BRN_C : 0; }
 
 extern "C" int epc_bn_relu_rownorm_bwd(const float* df, const float* z, const float* rn, const float* mean, const float* var,
                                        const float* gamma, const float* beta, float eps, int rows, int C, float* dz,
@@ -1614,7 +1613,7 @@ extern "C" int epc_bn_relu_rownorm_bwd(const float* df, const float* z, const fl
     EPC_CHECK_ARG(rows > 0 && C == BRN_C, "implemented for the 1024 channels of conv5");
     EPC_CHECK_ARG(partial_floats >= epc_bn_relu_rownorm_bwd_partial_floats(rows), "partials buffer too small");
     hipStream_t st = (hipStream_t)stream;
-    const int wgs = (rows + BRB_ROWS - 1) / BRB_ROWS;
+    const int wgs = brb_wgs(rows);
     hipLaunchKernelGGL(bn_relu_rownorm_bwd_sums_kernel, dim3(wgs), dim3(256), 0, st, df, z, rn, mean, var, gamma, beta, eps, rows,
                        rowdot, partials);
     hipLaunchKernelGGL(partial_sum_wide_kernel, dim3(2 * BRN_C / 4 / 16), dim3(1024), 0, st, partials, wgs, 2 * BRN_C,
@@ -1677,13 +1676,11 @@ extern "C" int epc_bn_apply_bwd(const float* dy, const float* z, const float* me
     EPC_CHECK_ARG(dy && z && mean && var && gamma && beta && dz && dgamma && dbeta, "null pointer");
     if (int rc = colreduce_check("epc_bn_apply_bwd: workspace too small", rows, C, workspace, workspace_bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int nb = (rows + CR_ROWS - 1) / CR_ROWS;
-    unsigned int* counters = (unsigned int*)workspace;
-    float* part = (float*)(counters + CR_COUNTERS);
-    const dim3 grid(nb, (C + 63) / 64);
+    const cr_ws w = cr_layout(workspace, rows, C);
+    const dim3 grid(w.nb, (C + 63) / 64);
     hipLaunchKernelGGL(colreduce_kernel<2>, dim3(grid.y, grid.x), dim3(256), 0, st, z, dy, mean, var, gamma, beta, eps, relu, rows, C, 1.0f,
-                       part);
-    hipLaunchKernelGGL(colreduce_finish_kernel<2>, dim3((C + CF_COLS - 1) / CF_COLS), dim3(256), 0, st, part, z, nb, C, 1.0f, dbeta, dgamma);
+                       w.part);
+    hipLaunchKernelGGL(colreduce_finish_kernel<2>, dim3((C + CF_COLS - 1) / CF_COLS), dim3(256), 0, st, w.part, z, w.nb, C, 1.0f, dbeta, dgamma);
     hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(grid.y, grid.x), dim3(256), 0, st, dy, z, mean, var, gamma, beta, dbeta, dgamma, eps,
                        1.0f / rows, relu, rows, C, dz);
     EPC_CHECK_LAUNCH();
@@ -1740,7 +1737,7 @@ extern "C" int epc_bn_apply_bwd_given(const float* dy, const float* z, const flo
     EPC_CHECK_ARG(rows > 0 && C > 0 && C % 4 == 0, "C must be a multiple of 4");
     const int nb = (rows + CR_ROWS - 1) / CR_ROWS;
     if (C == BRN_C)
-        hipLaunchKernelGGL(bn_apply_bwd_given_wide_kernel, dim3((rows + BRB_ROWS - 1) / BRB_ROWS), dim3(256), 0, (hipStream_t)stream, dy,
+        hipLaunchKernelGGL(bn_apply_bwd_given_wide_kernel, dim3(brb_wgs(rows)), dim3(256), 0, (hipStream_t)stream, dy,
                            z, mean, var, gamma, dbeta, dgamma, eps, 1.0f / rows, rows, dz);
     else
         hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3((C + 63) / 64, nb), dim3(256), 0, (hipStream_t)stream, dy, z, mean, var, gamma, beta,
@@ -2008,9 +2005,8 @@ __global__ __launch_bounds__(256) void partial_sum_kernel(const float* __restric
     }
 }
 
-extern "C" size_t epc_linear_bn_bwd64_partial_floats(int rows) {
-    return rows > 0 ? (size_t)((rows + LB_ROWS_PER_WG - 1) / LB_ROWS_PER_WG) * 4096 : 0;
-}
+static int lb_wgs(int rows) { return (rows + LB_ROWS_PER_WG - 1) / LB_ROWS_PER_WG; }   // workgroups = (64, 64) partials of dW
+extern "C" size_t epc_linear_bn_bwd64_partial_floats(int rows) { return rows > 0 ? (size_t)lb_wgs(rows) * 4096 : 0; }
 
 static int linear_bn_bwd64_impl(const float* dy, const float* z, const float* x, BnParams xbn, const float* W, const float* mean,
                                 const float* var, const float* gamma, const float* beta, float eps, int relu, int rows,
@@ -2021,13 +2017,11 @@ static int linear_bn_bwd64_impl(const float* dy, const float* z, const float* x,
     if (int rc = colreduce_check("epc_linear_bn_bwd64: workspace too small", rows, 64, workspace, workspace_bytes)) return rc;
     EPC_CHECK_ARG(dw_partial_floats >= epc_linear_bn_bwd64_partial_floats(rows), "dW partial buffer too small (epc_linear_bn_bwd64_partial_floats)");
     hipStream_t st = (hipStream_t)stream;
-    const int nb = (rows + CR_ROWS - 1) / CR_ROWS;
-    unsigned int* counters = (unsigned int*)workspace;
-    float* part = (float*)(counters + CR_COUNTERS);
-    hipLaunchKernelGGL(colreduce_kernel<2>, dim3(1, nb), dim3(256), 0, st, z, dy, mean, var, gamma, beta, eps, relu, rows, 64, 1.0f,
-                       part);
-    hipLaunchKernelGGL(colreduce_finish_kernel<2>, dim3(64 / CF_COLS), dim3(256), 0, st, part, z, nb, 64, 1.0f, dbeta, dgamma);
-    const int wgs = (rows + LB_ROWS_PER_WG - 1) / LB_ROWS_PER_WG;
+    const cr_ws w = cr_layout(workspace, rows, 64);
+    hipLaunchKernelGGL(colreduce_kernel<2>, dim3(1, w.nb), dim3(256), 0, st, z, dy, mean, var, gamma, beta, eps, relu, rows, 64, 1.0f,
+                       w.part);
+    hipLaunchKernelGGL(colreduce_finish_kernel<2>, dim3(64 / CF_COLS), dim3(256), 0, st, w.part, z, w.nb, 64, 1.0f, dbeta, dgamma);
+    const int wgs = lb_wgs(rows);
     hipLaunchKernelGGL(linear_bn_bwd64_kernel, dim3(wgs), dim3(256), 0, st, dy, z, x, W, mean, var, gamma, beta, dbeta, dgamma, eps,
                        1.0f / rows, relu, rows, dx, dw_partials, xbn, dx_addend);
     hipLaunchKernelGGL(partial_sum_kernel, dim3(4096 / 4 / 16), dim3(256), 0, st, dw_partials, wgs, 4096, dW);
@@ -2126,16 +2120,15 @@ extern "C" int epc_linear_smallk_fwd(const float* x, const float* W, const float
     return EPC_OK;
 }
 
-extern "C" size_t epc_linear_smallk_dw_partial_floats(int rows, int cin) {
-    return rows > 0 ? (size_t)((rows + SK_ROWS_PER_WG - 1) / SK_ROWS_PER_WG) * cin * 64 : 0;
-}
+static int sk_wgs(int rows) { return (rows + SK_ROWS_PER_WG - 1) / SK_ROWS_PER_WG; }   // workgroups = (cin, 64) partials of dW
+extern "C" size_t epc_linear_smallk_dw_partial_floats(int rows, int cin) { return rows > 0 ? (size_t)sk_wgs(rows) * cin * 64 : 0; }
 
 extern "C" int epc_linear_smallk_dw(const float* x, const float* dy, int rows, int cin, int cout, float* dW, float* partials,
                                     size_t partial_floats, void* stream) {
     EPC_CHECK_ARG(x && dy && dW && partials, "null pointer");
     EPC_CHECK_ARG(rows > 0 && cin >= 1 && cin <= 4 && cout == 64, "rows > 0, 1 <= cin <= 4, cout == 64");
     EPC_CHECK_ARG(partial_floats >= epc_linear_smallk_dw_partial_floats(rows, cin), "partial buffer too small");
-    const int wgs = (rows + SK_ROWS_PER_WG - 1) / SK_ROWS_PER_WG;
+    const int wgs = sk_wgs(rows);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(linear_smallk_dw_kernel, dim3(wgs), dim3(256), 0, st, x, dy, rows, cin, partials);
     const int E = cin * 64;
@@ -2776,17 +2769,16 @@ extern "C" int epc_assign_softmax_bwd(const float* da, const float* dsum, const 
     const int rows = (int)rows_l;
     if (int rc = colreduce_check("epc_assign_softmax_bwd: workspace too small", rows, 64, workspace, workspace_bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int nb = (rows + CR_ROWS - 1) / CR_ROWS;
-    float* part = (float*)((unsigned int*)workspace + CR_COUNTERS);
-    hipLaunchKernelGGL(assign_softmax_bwd_kernel, dim3(nb), dim3(256), 0, st, da, dsum, a, z, mean, var, eps, n_points, rows, dz,
-                       part, rowdot);
-    hipLaunchKernelGGL(colreduce_finish_kernel<2>, dim3(64 / CF_COLS), dim3(256), 0, st, part, z, nb, 64, 1.0f, dbeta, dgamma);
+    const cr_ws w = cr_layout(workspace, rows, 64);
+    hipLaunchKernelGGL(assign_softmax_bwd_kernel, dim3(w.nb), dim3(256), 0, st, da, dsum, a, z, mean, var, eps, n_points, rows, dz,
+                       w.part, rowdot);
+    hipLaunchKernelGGL(colreduce_finish_kernel<2>, dim3(64 / CF_COLS), dim3(256), 0, st, w.part, z, w.nb, 64, 1.0f, dbeta, dgamma);
     // dz holds dpre: every element is read and then overwritten by the thread that owns it
     if (rowdot)
-        hipLaunchKernelGGL(assign_dz_rowdot_kernel, dim3(nb), dim3(256), 0, st, z, mean, var, gamma, dbeta, dgamma, eps, 1.0f / rows,
+        hipLaunchKernelGGL(assign_dz_rowdot_kernel, dim3(w.nb), dim3(256), 0, st, z, mean, var, gamma, dbeta, dgamma, eps, 1.0f / rows,
                            rows, dz, rowdot);
     else
-        hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(1, nb), dim3(256), 0, st, (const float*)dz, z, mean, var, gamma, beta, dbeta,
+        hipLaunchKernelGGL(bn_apply_bwd_kernel, dim3(1, w.nb), dim3(256), 0, st, (const float*)dz, z, mean, var, gamma, beta, dbeta,
                            dgamma, eps, 1.0f / rows, 0, rows, 64, dz);
     EPC_CHECK_LAUNCH();
     return EPC_OK;

@@ -23,6 +23,25 @@ def pkg(name=""):
     return importlib.import_module("epc-net_amd" + ("." + name if name else ""))
 
 
+GUARD = 4096    # bytes of poison on either side of every Guarded tensor
+
+
+class Guarded:
+    """A tensor of `shape` / `dtype` in the middle of a buffer of bytes 0xFF: `t` is the tensor to pass, `intact()` says whether the
+    GUARD bytes in front of it and behind it still hold the poison, `untouched()` whether the tensor itself does too."""
+
+    def __init__(self, shape, dtype, dev):
+        self.nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        self.buf = torch.full((2 * GUARD + self.nbytes,), 0xFF, dtype=torch.uint8, device=dev)
+        self.t = self.buf[GUARD:GUARD + self.nbytes].view(dtype).reshape(shape)
+
+    def intact(self):
+        return bool((self.buf[:GUARD] == 0xFF).all()) and bool((self.buf[GUARD + self.nbytes:] == 0xFF).all())
+
+    def untouched(self):
+        return bool((self.buf == 0xFF).all())
+
+
 def make_store(arch, weights, device, params=None):
     """Variable store holding `weights` (oracle names, relative to OUTER) under the reference's full names."""
     V = pkg("variables")

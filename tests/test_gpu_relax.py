@@ -10,23 +10,9 @@ import torch
 
 import helpers as H
 import relax_ref as R
+from helpers import Guarded
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4096    # bytes of poison on either side of every output
-
-
-class Guarded:
-    """An output of `shape` / `dtype` in the middle of a buffer of bytes 0xFF: `t` is the tensor to pass, `intact()` says whether the
-    GUARD bytes in front of it and behind it still hold the poison."""
-
-    def __init__(self, shape, dtype, dev):
-        self.nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        self.buf = torch.full((2 * GUARD + self.nbytes,), 0xFF, dtype=torch.uint8, device=dev)
-        self.t = self.buf[GUARD:GUARD + self.nbytes].view(dtype).reshape(shape)
-
-    def intact(self):
-        return bool((self.buf[:GUARD] == 0xFF).all()) and bool((self.buf[GUARD + self.nbytes:] == 0xFF).all())
 
 
 def _up(a, dtype):

@@ -16,7 +16,7 @@ import torch
 import helpers as H
 import stamps_ref as R
 import submap_ref as SR
-from helpers import O
+from helpers import GUARD, Guarded, O
 
 pytestmark = pytest.mark.gpu
 
@@ -24,20 +24,6 @@ T = 1024        # ST_TILE of csrc/stamps.hip: the rows of one tile of the row ke
 PAIRS = 32      # ST_PAIRS: the (scan, row range) pairs a tile lists at a time
 GAP = 500_000_000
 MS = 1_000_000
-GUARD = 4096    # bytes of poison on either side of every output
-
-
-class Guarded:
-    """An output of `shape` / `dtype` in the middle of a buffer of bytes 0xFF: `t` is the tensor to pass, `intact()` says whether the
-    GUARD bytes in front of it and behind it still hold the poison."""
-
-    def __init__(self, shape, dtype, dev):
-        self.nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        self.buf = torch.full((2 * GUARD + self.nbytes,), 0xFF, dtype=torch.uint8, device=dev)
-        self.t = self.buf[GUARD:GUARD + self.nbytes].view(dtype).reshape(shape)
-
-    def intact(self):
-        return bool((self.buf[:GUARD] == 0xFF).all()) and bool((self.buf[GUARD + self.nbytes:] == 0xFF).all())
 
 
 def _poison(t):
