@@ -408,6 +408,11 @@ __global__ __launch_bounds__(KNN_THREADS, BATCH == 4 ? 8 : 1) void knn_topk_cull
 //     candidate with d' < kth is always pushed (kth <= thr_q) and never evicted (a list's 20th value cannot fall below kth, the
 //     20th of a superset).  Hence the union of the four lists always contains the 20 smallest.  Tiles and batches are culled
 //     against thr_q (non-strict, for pass 2), insertion is attempted when d' < thr_q.
+//     thr_q is carried in a register and recomputed by whatever changes a list (the insertion block ends with the exchange; the
+//     warm-up recomputes it once): what a vote or a batch reads is always the current value, so the proof stands as written.
+//   * warm-up.  A lane's first 20 candidates (the first five batches of the wave's own super-tile) are sorted into the slots
+//     directly, without votes: the lists then hold every candidate seen so far -- a superset of what the rule above would have
+//     pushed, which only ever adds values >= kth to a list that keeps its 20 smallest -- and those five batches are all flagged.
 //   * kth = the 20th smallest of the union: after the scan the lanes of a pair push each other's list through their own
 //     network (both then hold the pair's 20 smallest), then the pairs do the same -- 40 pushes at most, cut short wave-wide as
 //     soon as no lane's list would change (lists are ascending).
@@ -434,6 +439,53 @@ __device__ __forceinline__ float quad_max(float v) {
         : "v"(v));
     return r;
 }
+// topk_insert_dist and the threshold exchange behind it (quad_max of the fifth values) as ONE block: the first exchange sits two
+// instructions after the write of slot 4, the second two after the first, so the network's own instructions are the DPP wait
+// states and no s_nop is issued -- 22 instructions where the separate calls took 22 + three s_nop.
+__device__ __forceinline__ void topk_insert_dist_thr(float (&top)[20], float v, float& thr) {
+    asm volatile(   // volatile as in quad_max: a lane's partners have to be active
+        "v_med3_f32 %[k19], %[k18], %[k19], %[v]\n\t"
+        "v_med3_f32 %[k18], %[k17], %[k18], %[v]\n\t"
+        "v_med3_f32 %[k17], %[k16], %[k17], %[v]\n\t"
+        "v_med3_f32 %[k16], %[k15], %[k16], %[v]\n\t"
+        "v_med3_f32 %[k15], %[k14], %[k15], %[v]\n\t"
+        "v_med3_f32 %[k14], %[k13], %[k14], %[v]\n\t"
+        "v_med3_f32 %[k13], %[k12], %[k13], %[v]\n\t"
+        "v_med3_f32 %[k12], %[k11], %[k12], %[v]\n\t"
+        "v_med3_f32 %[k11], %[k10], %[k11], %[v]\n\t"
+        "v_med3_f32 %[k10], %[k9], %[k10], %[v]\n\t"
+        "v_med3_f32 %[k9], %[k8], %[k9], %[v]\n\t"
+        "v_med3_f32 %[k8], %[k7], %[k8], %[v]\n\t"
+        "v_med3_f32 %[k7], %[k6], %[k7], %[v]\n\t"
+        "v_med3_f32 %[k6], %[k5], %[k6], %[v]\n\t"
+        "v_med3_f32 %[k5], %[k4], %[k5], %[v]\n\t"
+        "v_med3_f32 %[k4], %[k3], %[k4], %[v]\n\t"
+        "v_med3_f32 %[k3], %[k2], %[k3], %[v]\n\t"
+        "v_med3_f32 %[k2], %[k1], %[k2], %[v]\n\t"
+        "v_max_f32_dpp %[t], %[k4], %[k4] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_med3_f32 %[k1], %[k0], %[k1], %[v]\n\t"
+        "v_min_f32 %[k0], %[k0], %[v]\n\t"
+        "v_max_f32_dpp %[t], %[t], %[t] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        : [t] "=&v"(thr), [k0] "+v"(top[0]), [k1] "+v"(top[1]), [k2] "+v"(top[2]), [k3] "+v"(top[3]), [k4] "+v"(top[4]), [k5] "+v"(top[5]), [k6] "+v"(top[6]), [k7] "+v"(top[7]), [k8] "+v"(top[8]), [k9] "+v"(top[9]), [k10] "+v"(top[10]), [k11] "+v"(top[11]), [k12] "+v"(top[12]), [k13] "+v"(top[13]), [k14] "+v"(top[14]), [k15] "+v"(top[15]), [k16] "+v"(top[16]), [k17] "+v"(top[17]), [k18] "+v"(top[18]), [k19] "+v"(top[19])
+        : [v] "v"(v));
+}
+
+// Warm-up: the list holds `len` values ascending in top[0 .. len) and nothing that matters above them; v goes in without the
+// full network -- len + 1 instructions.  (len is a constant after unrolling; single instructions as in the pair merge: fminf /
+// fmaxf would add a canonicalising v_max each.)
+__device__ __forceinline__ void topk_fill(float (&top)[20], int len, float v) {
+    if (len == 0) {
+        top[0] = v;
+        return;
+    }
+#pragma unroll
+    for (int s = 19; s >= 1; --s) {
+        if (s == len) asm("v_max_f32 %0, %1, %2" : "=v"(top[s]) : "v"(top[s - 1]), "v"(v));
+        if (s < len) asm("v_med3_f32 %0, %1, %2, %3" : "=v"(top[s]) : "v"(top[s - 1]), "v"(top[s]), "v"(v));
+    }
+    asm("v_min_f32 %0, %1, %2" : "=v"(top[0]) : "v"(top[0]), "v"(v));
+}
+
 template <int STEP>
 __device__ __forceinline__ float dpp_quad_swap(float v) {   // the value of lane ^ 1 (STEP 0) / lane ^ 2 (STEP 1)
     float r;
@@ -585,10 +637,15 @@ __global__ __launch_bounds__(KNN_THREADS, 8) void knn_topk_quad_kernel(const flo
     // or below it.  (The smallest of their 20th values is a bound too, and a loose one: a list sees a quarter of the candidates, its
     // 20th value is about the query's 80th; with it alone a wave scanned 57 tiles instead of 17.)
     auto thr_q = [&]() { return quad_max(top[4]); };
+    // The threshold is CARRIED in a register: the lists change only in topk_insert_dist_thr and in the warm-up, and both leave
+    // thr = thr_q() of the lists as they then stand -- every vote and every batch reads the current value, never a stale one.
+    float thr = valid ? INFINITY : -INFINITY;   // = thr_q() of the initial lists (the lanes of a quad share `valid`)
+    int cwarm = -4, cskip = -1;   // warm-up (below): tiles cwarm, cwarm + 1 and the first batch of tile cskip are in the lists already
     auto scan1 = [&](int c) {
         const float4* tp = cand + c * KNN_CT + sub;
 #pragma unroll
         for (int ub = 0; ub < 2; ++ub) {
+            if (ub == 0 && c == cskip) continue;
             float4 q[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) q[u] = tp[16 * ub + 4 * u];
@@ -597,7 +654,6 @@ __global__ __launch_bounds__(KNN_THREADS, 8) void knn_topk_quad_kernel(const flo
             for (int u = 0; u < 4; ++u) d[u] = pos_sq_dist(q[u]);
             float dmin;
             asm("v_min3_f32 %0, %1, %2, %3\n\tv_min_f32 %0, %0, %4" : "=&v"(dmin) : "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]));
-            float thr = thr_q();
             if (wave_any(dmin <= thr)) {
                 const int bit = c * 2 + ub;
                 const unsigned long long bv = 1ull << (bit & 63);
@@ -605,10 +661,7 @@ __global__ __launch_bounds__(KNN_THREADS, 8) void knn_topk_quad_kernel(const flo
                 for (int w = 0; w < HMW; ++w) hm[w] |= (bit >> 6) == w ? bv : 0ull;
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    if (wave_any(d[u] < thr)) {
-                        topk_insert_dist(top, d[u]);
-                        thr = thr_q();
-                    }
+                    if (wave_any(d[u] < thr)) topk_insert_dist_thr(top, d[u], thr);
                 }
             }
         }
@@ -620,20 +673,42 @@ __global__ __launch_bounds__(KNN_THREADS, 8) void knn_topk_quad_kernel(const flo
     const int T0 = t0 >> 2;
     const int kmax = 2 * max(T0, nst - 1 - T0);   // visiting order k -> super-tile: T0, T0-1, T0+1, T0-2, T0+2, ...
     auto super_of = [&](int k) { return T0 + ((k & 1) ? -((k + 1) >> 1) : (k >> 1)); };
+    // Warm-up without the network.  The walk starts with the wave's own super-tile, all of it (thresholds are +inf), so a lane's
+    // first 20 candidates are those of that super-tile's first five batches: they go into the slots directly, each by a network
+    // cut to the values already there (1 + 2 + ... + 20 = 210 instructions, no vote, no exchange; twenty passes of the full network
+    // with their votes and exchanges took ~540).  The lists then hold ALL of those candidates where the network path held those it
+    // had pushed -- a superset, so the proof in the header stands -- and all five batches are flagged for pass 2.  A super-tile of
+    // fewer than three tiles (the cloud's last one, or n <= 64) goes the ordinary way.
+    if (4 * T0 + 2 < ntiles) {
+        cwarm = 4 * T0, cskip = cwarm + 2;
+#pragma unroll
+        for (int f = 0; f < 5; ++f) {
+            const float4* tp = cand + (cwarm + (f >> 1)) * KNN_CT + 16 * (f & 1) + sub;
+            float4 q[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q[u] = tp[4 * u];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) topk_fill(top, 4 * f + u, pos_sq_dist(q[u]));   // (padding: d' = +inf, a slot stays +inf)
+        }
+#pragma unroll
+        for (int s = 0; s < KSEL; ++s) top[s] = valid ? top[s] : -INFINITY;   // lanes past the cloud's end keep their list of -inf
+        thr = thr_q();
+    }
+    // (the ballots: a super-tile or tile out of range gets a NaN bound, which no threshold satisfies -- +inf would pass while a
+    // list is not full (+inf <= +inf), and `in && lb <= thr` goes through an integer predicate, a v_cndmask and a second compare)
     for (int kk = 0; kk <= kmax; kk += 4) {
         const int S = super_of(kk + sub);
         const bool in_s = S >= 0 && S < nst;
-        const float lbs = in_s ? lower_bound(sbb, S) : INFINITY;   // (a list that is not full yet has threshold +inf: test `in` too)
-        const float thr_s = thr_q();
-        const unsigned long long ms = __builtin_amdgcn_ballot_w64(in_s && lbs <= thr_s);
+        const float lbs = in_s ? lower_bound(sbb, S) : __builtin_nanf("");
+        const unsigned long long ms = __builtin_amdgcn_ballot_w64(lbs <= thr);
 #pragma unroll 1
         for (int s = 0; s < 4; ++s) {
             if (!(ms & (0x1111111111111111ull << s))) continue;
             const int c0 = 4 * super_of(kk + s);
             const bool in = c0 + sub < ntiles;
-            const float lb = in ? lower_bound(bb, c0 + sub) : INFINITY;
-            const float thr = thr_q();
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(in && lb <= thr);
+            const float lb = in ? lower_bound(bb, c0 + sub) : __builtin_nanf("");
+            unsigned long long m = __builtin_amdgcn_ballot_w64(lb <= thr);
+            if (c0 == cwarm) m &= ~0x3333333333333333ull;   // its first two tiles went in with the warm-up
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (m & (0x1111111111111111ull << r)) scan1(c0 + r);
@@ -688,11 +763,13 @@ __global__ __launch_bounds__(KNN_THREADS, 8) void knn_topk_quad_kernel(const flo
     auto pass2 = [&](auto wide) {
         constexpr int ESZ = decltype(wide)::value ? 4 : 2;
         const unsigned int row = (unsigned int)(valid ? i : 0) * ucap * ESZ;
+        const unsigned int lcap = valid ? ucap : 0u;   // (a lane past the cloud's end stores nothing)
         const int words = (2 * ntiles + 63) >> 6;
         for (int w = 0; w < words; ++w) {
             unsigned long long flagged = hm[0];
 #pragma unroll
             for (int v = 1; v < HMW; ++v) flagged = w == v ? hm[v] : flagged;
+            if (w == (2 * cwarm) >> 6) flagged |= 0x1full << ((2 * cwarm) & 63);   // the warm-up's five batches: bits from a multiple of 8
             while (flagged) {
                 const int bit = __builtin_ctzll(flagged);
                 flagged &= flagged - 1ull;
@@ -701,22 +778,23 @@ __global__ __launch_bounds__(KNN_THREADS, 8) void knn_topk_quad_kernel(const flo
                 float4 q[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) q[u] = tp[16 * ub + 4 * u];
+                // the four ballots are taken where the compares are: a ballot of a flag computed in another block goes through an
+                // integer predicate (a v_cndmask and a second compare per u)
                 float d[4];
-                bool hit = false;
+                unsigned long long hmask[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     d[u] = pos_sq_dist(q[u]);
-                    hit |= d[u] <= dk;
+                    hmask[u] = __builtin_amdgcn_ballot_w64(d[u] <= dk);
                 }
-                if (wave_any(hit)) {
+                if ((hmask[0] | hmask[1] | hmask[2] | hmask[3]) != 0ull) {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
-                        const bool h = d[u] <= dk;
-                        const unsigned long long m = __builtin_amdgcn_ballot_w64(h);
+                        const unsigned long long m = hmask[u];
                         if (m == 0ull) continue;
                         const unsigned int qb = (unsigned int)(m >> qshift) & 15u;
                         const unsigned int pos = count + __builtin_popcount(qb & below);
-                        if (h && valid && pos < ucap) {
+                        if (d[u] <= dk && pos < lcap) {
                             char* slot = lists + (row + pos * ESZ);
                             const int j = c * KNN_CT + 16 * ub + 4 * u + sub;
                             if (ESZ == 4)
