@@ -18,18 +18,7 @@
 //                          slot.  Behind them tiles over the voxels: NaN rows and zero counts for j >= V, or everywhere after an overflow
 //                          or a failed call.
 // No float atomics, no inline assembly.
-#include "scan_common.h"
-#include "../../include/epcnet_maps.h"
-
-#define MP_THREADS 256
-#define MP_TILE 256            // rows per insert / count / emit tile, one per thread (tests/test_gpu_map.py names it MP_TILE)
-#define MP_GROUP 256           // tiles per group: MP_TILE * MP_GROUP = 65536 rows is the scan's first level
-#define MP_HEAD 16             // workspace words in front
-#define MP_BAD 0               //   [0] the whole-call failure
-#define MP_CLAIMED 1           //   [1] slots claimed
-#define MP_KEPT 2              //   [2] rows kept, [3] rows absent, [4] rows out of range
-#define MP_EMPTY 0xffffffffffffffffull      // no key: a key has 63 bits
-#define MP_NO_LEADER 0x7fffffff
+#include "map_common.h"
 
 // one slot of the table: 40 bytes
 struct mp_slot {
@@ -48,13 +37,6 @@ struct mp_ws {
     int32_t* group;
     unsigned long long mask;   // cap - 1
 };
-static inline unsigned long long mp_cap(long long max_voxels) {
-    unsigned long long cap = 1;
-    while (cap < 2ull * (unsigned long long)max_voxels + 1) cap <<= 1;
-    return cap;
-}
-static inline long long mp_tiles(long long num_rows) { return (num_rows + MP_TILE - 1) / MP_TILE; }
-static inline long long mp_groups(long long num_rows) { return (mp_tiles(num_rows) + MP_GROUP - 1) / MP_GROUP; }
 // the regions of mp_ws in `workspace`, or (workspace NULL) only their total: the head and the table as they are, the rest rounded up to 16 bytes
 struct mp_layout_t { mp_ws ws; size_t bytes; };
 static mp_layout_t mp_layout(void* workspace, long long num_rows, long long max_voxels) {
@@ -68,8 +50,6 @@ struct mp_params {
     double voxel, step;        // step = fl(voxel / 4096)
     long long min_count;
 };
-
-__device__ __forceinline__ int mp_load(const int32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 
 // ---- launch 2: the table, and the whole-call failure -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(MP_THREADS) void map_clear_kernel(const int32_t* __restrict__ offsets, long long num_rows, int num_clouds,
@@ -89,33 +69,6 @@ __global__ __launch_bounds__(MP_THREADS) void map_clear_kernel(const int32_t* __
 }
 
 // ---- launch 3: the rows ----------------------------------------------------------------------------------------------------------------
-// A row's kind: 0 kept (then w holds the lattice coordinates), 1 absent, 2 out of range.  m: the pose's twelve entries, d = fl(t - origin).
-__device__ __forceinline__ int mp_row(const double* __restrict__ m, const double* __restrict__ d, double voxel, float xf, float yf, float zf,
-                                      long long* w) {
-#pragma clang fp contract(off)
-    const double x = (double)xf, y = (double)yf, z = (double)zf;
-    const double q0 = ((m[0] * x + m[1] * y) + m[2] * z) + d[0];
-    const double q1 = ((m[4] * x + m[5] * y) + m[6] * z) + d[1];
-    const double q2 = ((m[8] * x + m[9] * y) + m[10] * z) + d[2];
-    const double s0 = (q0 / voxel) * 4096.0, s1 = (q1 / voxel) * 4096.0, s2 = (q2 / voxel) * 4096.0;
-    if (!(__builtin_isfinite(s0) && __builtin_isfinite(s1) && __builtin_isfinite(s2))) return 1;
-    const double f0 = __builtin_floor(s0), f1 = __builtin_floor(s1), f2 = __builtin_floor(s2);
-    const double lim = 4294967296.0;
-    if (!(f0 >= -lim && f0 < lim && f1 >= -lim && f1 < lim && f2 >= -lim && f2 < lim)) return 2;
-    w[0] = (long long)f0, w[1] = (long long)f1, w[2] = (long long)f2;
-    return 0;
-}
-
-// the hash of a key: the finaliser of splitmix64 (the output does not depend on it)
-__device__ __forceinline__ unsigned long long mp_hash(unsigned long long k) {
-    k ^= k >> 30;
-    k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27;
-    k *= 0x94d049bb133111ebull;
-    k ^= k >> 31;
-    return k;
-}
-
 __global__ __launch_bounds__(MP_THREADS) void map_insert_kernel(const float* __restrict__ points, const int32_t* __restrict__ offsets,
                                                                 long long num_rows, int num_clouds, const double* __restrict__ poses,
                                                                 const double* __restrict__ origin, mp_params pr, long long max_voxels,

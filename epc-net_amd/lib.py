@@ -95,6 +95,7 @@ _HEADERS = (
     ("pairs", "PAIR", True, False),             # PAIR_EXPORTS, PAIRS_HEADER_PATH: its two status bits join the EPC_* constants
     ("trajectory", "TRAJECTORY", True, False),  # TRAJECTORY_EXPORTS, TRAJECTORY_HEADER_PATH: loop closing; one status bit more
     ("maps", "MAP", False, False),              # MAP_EXPORTS, MAPS_HEADER_PATH: corrected submaps fused into one voxel map
+    ("surfels", "SURFEL", False, False),        # SURFEL_EXPORTS, SURFELS_HEADER_PATH: the map with a surfel per voxel
     ("forms", "FORM", False, False))            # FORM_EXPORTS, FORMS_HEADER_PATH: test / tuning entries that name a kernel's form
 
 

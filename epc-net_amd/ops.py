@@ -11,7 +11,7 @@ import torch
 from . import lib as L
 from .lib import EpcNetError
 # the scan front end lives in scans.py; its names stay reachable here (ops.pack_scans, ops.PoseTuples, ...)
-from .scans import (PoseTuples, _device_poses, build_submaps, deskew_scans, fuse_map, grid_downsample, interpolate_poses, morton_sort,  # noqa: F401
+from .scans import (PoseTuples, _device_poses, build_submaps, deskew_scans, fuse_map, fuse_surfels, grid_downsample, interpolate_poses, morton_sort,  # noqa: F401
                     pack_scans, pose_radius_lists, remove_ground, travel_along)
 
 BN_EPS = 1e-3

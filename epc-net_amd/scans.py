@@ -219,6 +219,30 @@ def build_submaps(points, offsets, poses, along=None, length=20.0, spacing=10.0,
     return result + (along,) if return_along else result
 
 
+def _map_arguments(who, points, offsets, poses, voxel, origin, max_voxels, min_count, size_query):
+    """The checks and defaults that fuse_map and fuse_surfels share -> ``(C, rows, dev, poses (C, 12), origin, max_voxels, voxel,
+    min_count, need)``; ``size_query``: a name of the library's workspace query (looked up after the GPU is required)."""
+    C, rows, dev = _packed(who, points, offsets, "C")
+    _device_tensor(who, "poses", poses, torch.float64)
+    if tuple(poses.shape) not in ((C, 12), (C, 3, 4)):
+        raise EpcNetError(-1, "%s: poses must be (%d, 12) or (%d, 3, 4) = [R | t] per cloud, got %s" % (who, C, C, tuple(poses.shape)))
+    poses = poses.reshape(C, 12)
+    if origin is None:
+        origin = poses[0, 3::4].clone() if C else torch.zeros(3, dtype=torch.float64, device=dev)
+    else:
+        _device_tensor(who, "origin", origin, torch.float64, (3,))
+    L.require_gpu()
+    if max_voxels is None:
+        max_voxels = min(max(rows, 1), 2 ** 28)
+    max_voxels, voxel, min_count = int(max_voxels), float(voxel), int(min_count)
+    need = int(getattr(L.lib(), size_query)(rows, C, max_voxels))
+    if need == 0:
+        raise EpcNetError(-1, "%s: need fewer than 2^31 rows, C <= 2^24 and 1 <= max_voxels <= 2^28, got %d, %d and %d" % (who, rows, C, max_voxels))
+    if not (math.isfinite(voxel) and 2.0 ** -20 <= voxel <= 2.0 ** 20 and 1 <= min_count < 2 ** 31):
+        raise EpcNetError(-1, "%s: need 2^-20 <= voxel <= 2^20 and 1 <= min_count < 2^31, got %r and %r" % (who, voxel, min_count))
+    return C, rows, dev, poses, origin, max_voxels, voxel, min_count, need
+
+
 def fuse_map(points, offsets, poses, voxel=0.2, origin=None, max_voxels=None, min_count=1, workspace=None):
     """Posed clouds -> ONE voxel map in one frame (include/epcnet_maps.h: epcnet_map_fuse; numpy restatement: tests/map_ref.py):
     ``(map_points (max_voxels, 3) float32, count (max_voxels,) int32, num_out (4,) int32, origin (3,) float64)``, all device tensors, on
@@ -238,24 +262,8 @@ def fuse_map(points, offsets, poses, voxel=0.2, origin=None, max_voxels=None, mi
     2^28)`` -- the true number is device data --; ``workspace``: a uint8 device tensor of at least ``epcnet_map_fuse_workspace_bytes``
     bytes to reuse (what a captured graph needs), else one is allocated."""
     who = "fuse_map"
-    C, rows, dev = _packed(who, points, offsets, "C")
-    _device_tensor(who, "poses", poses, torch.float64)
-    if tuple(poses.shape) not in ((C, 12), (C, 3, 4)):
-        raise EpcNetError(-1, "%s: poses must be (%d, 12) or (%d, 3, 4) = [R | t] per cloud, got %s" % (who, C, C, tuple(poses.shape)))
-    poses = poses.reshape(C, 12)
-    if origin is None:
-        origin = poses[0, 3::4].clone() if C else torch.zeros(3, dtype=torch.float64, device=dev)
-    else:
-        _device_tensor(who, "origin", origin, torch.float64, (3,))
-    L.require_gpu()
-    if max_voxels is None:
-        max_voxels = min(max(rows, 1), 2 ** 28)
-    max_voxels, voxel, min_count = int(max_voxels), float(voxel), int(min_count)
-    need = int(L.lib().epcnet_map_fuse_workspace_bytes(rows, C, max_voxels))
-    if need == 0:
-        raise EpcNetError(-1, "%s: need fewer than 2^31 rows, C <= 2^24 and 1 <= max_voxels <= 2^28, got %d, %d and %d" % (who, rows, C, max_voxels))
-    if not (math.isfinite(voxel) and 2.0 ** -20 <= voxel <= 2.0 ** 20 and 1 <= min_count < 2 ** 31):
-        raise EpcNetError(-1, "%s: need 2^-20 <= voxel <= 2^20 and 1 <= min_count < 2^31, got %r and %r" % (who, voxel, min_count))
+    C, rows, dev, poses, origin, max_voxels, voxel, min_count, need = _map_arguments(
+        who, points, offsets, poses, voxel, origin, max_voxels, min_count, "epcnet_map_fuse_workspace_bytes")
     ws, own = _workspace(who, need, workspace, dev)
     map_points = torch.empty((max_voxels, 3), dtype=torch.float32, device=dev)
     count = torch.empty(max_voxels, dtype=torch.int32, device=dev)
@@ -266,6 +274,37 @@ def fuse_map(points, offsets, poses, voxel=0.2, origin=None, max_voxels=None, mi
     if own:
         ws.record_stream(torch.cuda.current_stream(dev))
     return map_points, count, num_out, origin
+
+
+def fuse_surfels(points, offsets, poses, voxel=0.2, origin=None, max_voxels=None, min_count=1, ring=1, min_support=8, workspace=None):
+    """``fuse_map`` with a SURFEL per voxel (include/epcnet_surfels.h: epcnet_map_surfels; numpy restatement: tests/surfel_ref.py):
+    ``(map_points, count, centroid (max_voxels, 3) float32, normal (max_voxels, 3) float32, eigen (max_voxels, 3) float32, support
+    (max_voxels,) int32, num_out, origin)``, all device tensors, on the current stream, no host read, capturable.  The arguments, their
+    checks and defaults, ``map_points``, ``count``, ``num_out`` and ``origin`` are ``fuse_map``'s, bit for bit.
+
+    A voxel's own two or three rows carry no covariance: the statistics of voxel j are pooled over the ``(2 ring + 1)^3`` cells around
+    it (``ring`` in 0..2), from those that hold at least ``min_count`` rows, as integer moments on a lattice of ``voxel / 256`` -- the
+    same bits on every run.  ``support[j]`` is the number of rows pooled.  Where ``count[j] >= min_count`` and ``support[j] >=
+    min_support`` (at least 3), ``centroid[j]`` is their mean in metres relative to ``origin``, ``eigen[j]`` the eigenvalues of their
+    covariance in m^2, ascending (flat: the first is small against the others), and ``normal[j]`` the unit eigenvector of the smallest,
+    in the map's axes, its largest component positive (NOT oriented towards a viewpoint); elsewhere the three are NaN rows.
+    ``workspace``: a uint8 device tensor of at least ``epcnet_map_surfels_workspace_bytes`` bytes to reuse, else one is allocated."""
+    who = "fuse_surfels"
+    C, rows, dev, poses, origin, max_voxels, voxel, min_count, need = _map_arguments(
+        who, points, offsets, poses, voxel, origin, max_voxels, min_count, "epcnet_map_surfels_workspace_bytes")
+    if ring != int(ring) or not 0 <= int(ring) <= L.EPC_SURFEL_MAX_RING or min_support != int(min_support) or not 3 <= int(min_support) < 2 ** 31:
+        raise EpcNetError(-1, "%s: need an integer ring in [0, %d] and 3 <= min_support < 2^31, got %r and %r"
+                          % (who, L.EPC_SURFEL_MAX_RING, ring, min_support))
+    ws, own = _workspace(who, need, workspace, dev)
+    map_points, centroid, normal, eigen = (torch.empty((max_voxels, 3), dtype=torch.float32, device=dev) for _ in range(4))
+    count, support = (torch.empty(max_voxels, dtype=torch.int32, device=dev) for _ in range(2))
+    num_out = torch.empty(4, dtype=torch.int32, device=dev)
+    params = (ctypes.c_double * L.EPC_SURFEL_PARAMS)(voxel, float(min_count), float(int(ring)), float(int(min_support)))   # (host memory)
+    L.run.epcnet_map_surfels(points if rows else _spare(dev), offsets, rows, C, poses if C else _spare(dev, torch.float64), origin, params,
+                             max_voxels, map_points, count, centroid, normal, eigen, support, num_out, ws, ws.numel())
+    if own:
+        ws.record_stream(torch.cuda.current_stream(dev))
+    return map_points, count, centroid, normal, eigen, support, num_out, origin
 
 
 def _max_gap_ns(who, max_gap):
