@@ -96,6 +96,7 @@ _HEADERS = (
     ("trajectory", "TRAJECTORY", True, False),  # TRAJECTORY_EXPORTS, TRAJECTORY_HEADER_PATH: loop closing; one status bit more
     ("maps", "MAP", False, False),              # MAP_EXPORTS, MAPS_HEADER_PATH: corrected submaps fused into one voxel map
     ("surfels", "SURFEL", False, False),        # SURFEL_EXPORTS, SURFELS_HEADER_PATH: the map with a surfel per voxel
+    ("localize", "LOCALIZE", False, False),     # LOCALIZE_EXPORTS, LOCALIZE_HEADER_PATH: scans localised against the surfel map
     ("forms", "FORM", False, False))            # FORM_EXPORTS, FORMS_HEADER_PATH: test / tuning entries that name a kernel's form
 
 

@@ -13,6 +13,8 @@ from .lib import EpcNetError
 # the scan front end lives in scans.py; its names stay reachable here (ops.pack_scans, ops.PoseTuples, ...)
 from .scans import (PoseTuples, _device_poses, build_submaps, deskew_scans, fuse_map, fuse_surfels, grid_downsample, interpolate_poses, morton_sort,  # noqa: F401
                     pack_scans, pose_radius_lists, remove_ground, travel_along)
+# ... and so do localize.py's: the scans localised against the surfel map (ops.index_surfels, ops.localize_scans, ops.map_seeds)
+from .localize import index_surfels, localize_scans, map_seeds  # noqa: F401
 
 BN_EPS = 1e-3
 
