@@ -1,6 +1,7 @@
 // What the two voxel-map files share (map.hip: epcnet_map_fuse; surfel.hip: epcnet_map_surfels): the definition's row -> lattice step, the
 // key of a cell, the hash of the open-addressing table, the tile / group geometry of the leaders' scan and the words of the workspace's
-// head.  Each file keeps its own slot, claim loop and scan kernels: they follow its slot's layout.
+// head.  map.hip and the surfel files keep their own slot, claim loop and scan kernels: they follow the slot's layout (surfel.hip and
+// growmap.hip share theirs through surfel_common.h).
 #ifndef EPC_MAP_COMMON_H
 #define EPC_MAP_COMMON_H
 #include "scan_common.h"

@@ -15,6 +15,8 @@ from .scans import (PoseTuples, _device_poses, build_submaps, deskew_scans, fuse
                     pack_scans, pose_radius_lists, remove_ground, travel_along)
 # ... and so do localize.py's: the scans localised against the surfel map (ops.index_surfels, ops.localize_scans, ops.map_seeds)
 from .localize import index_surfels, localize_scans, map_seeds  # noqa: F401
+# ... and growmap.py's: the surfel map that grows across calls (ops.SurfelMap)
+from .growmap import SurfelMap  # noqa: F401
 
 BN_EPS = 1e-3
 

@@ -156,8 +156,8 @@ int epcnet_surfel_index(const float* anchor, const float* centroid, const float*
  * returns EPC_OK with nothing launched.  EPC_ENOMEM for index_bytes < epcnet_surfel_index_bytes(M) or a workspace shorter than
  * epcnet_scan_localize_workspace_bytes(Q, H, n), which launches nothing and returns 0 for arguments the entry refuses.
  *
- * Not covered: robust kernels beyond the gate; point-to-plane with scan-side normals, symmetric or GICP metrics; NDT; a map that grows
- * across calls; candidate rings other than 1; global localisation without a seed. */
+ * Not covered: robust kernels beyond the gate; point-to-plane with scan-side normals, symmetric or GICP metrics; NDT; an index patched in
+ * place when the map grows (epcnet_growmap.h: it is built again); candidate rings other than 1; global localisation without a seed. */
 size_t epcnet_scan_localize_workspace_bytes(int Q, int H, int n);
 int epcnet_scan_localize(const float* scans, int Q, int n, const double* seeds, int H, const void* index, size_t index_bytes,
                          const float* centroid, const float* normal, long long M, const double* params, double* pose, double* fit,

@@ -93,8 +93,8 @@ extern "C" {
  * reserved doubles are 0; EPC_ENOMEM for a workspace shorter than epcnet_map_surfels_workspace_bytes(num_rows, num_clouds,
  * max_voxels), which launches nothing and returns 0 for unsupported arguments.
  *
- * Not covered: normals oriented towards a viewpoint; point-to-plane registration against the surfels (the follow-up this enables); a
- * map that grows across calls. */
+ * Not covered: normals oriented towards a viewpoint.  Point-to-plane registration against the surfels is epcnet_localize.h; the same map
+ * kept across calls and grown by the rows added is epcnet_growmap.h. */
 #define EPC_SURFEL_PARAMS 8
 #define EPC_SURFEL_MAX_RING 2
 #define EPC_SURFEL_SWEEPS 5
