@@ -30,9 +30,24 @@
 //                           sf_pool_solve, at its slot's number: nothing else of the outputs is written.  After an overflow: the fill, a
 //                           loop of this grid over max_voxels, in one call only
 // Overflow is `claimed > max_voxels`, as in surfel.hip; claimed lives in the head and never falls, so it is sticky by itself.
+//
+// epcnet_surfel_map_move (include/epcnet_remap.h; numpy restatement in tests/remap_ref.py) takes rows out of the map and puts them back
+// at other poses on the same state: the sums are integers, so a row leaves by the negation of what it added.  Its launches are add's
+// with ONE other tile kernel in the place of the insert:
+//   growmap_move_kernel     a tile's rows under both poses (sf_tile_row twice).  A row kept under both at the same lattice position
+//                           leaves here.  The old cell is looked up, never claimed: a slot without a number was claimed in this call
+//                           (numbers are written behind this launch), so "a voxel that existed before this call" is `found and
+//                           numbered` in whatever order the rows run -- a row that fails it is unmatched and does nothing more.  The
+//                           new cell is claimed as the insert claims it.  Both slots take the epoch into `touched`; row_slot is two
+//                           words per row, [2 r] the slot left and [2 r + 1] the slot entered, each with its GM_WON; two rounds of
+//                           the sixteen-lane adds, the first negated.  The head's three row counters move by the tile's signed sums
+// The mark kernel walks every word of a row (ws.per_row: 1 for add, 2 for move), the leaders are read from a row's LAST word (the slot
+// it entered), and the dirty list holds per_row times as many entries; the scan, the numbers and the emit are the same launches.  A
+// voxel that lost its last row keeps slot and number: the emit writes count 0 and NaN for it (sf_write_mean divides by no zero count).
 // Integer atomics only, no inline assembly, no scratch.
 #include "surfel_common.h"
 #include "../../include/epcnet_growmap.h"
+#include "../../include/epcnet_remap.h"
 
 #define GM_MAGIC 0x3170616d776f7267ull      // "growmap1": a state that init wrote
 #define GM_WON (1 << 30)                    // in a row_slot word >= 0: this row was its slot's first of the call
@@ -40,6 +55,8 @@
 #define GM_DIRTY 5                          //   [5] entries of the dirty list
 #define GM_VBASE 6                          //   [6] V before this call
 #define GM_FILL 7                           //   [7] this call fills the outputs after an overflow
+#define GM_UNMATCHED 8                      //   [8] a move's rows whose old cell was no voxel before the call (an add leaves it 0)
+// a move keeps in [MP_KEPT] its rows put in, and in [MP_KEPT + 1], [MP_KEPT + 2] nothing: the head's counters take the signed sums
 
 struct gm_head {
     unsigned long long magic;
@@ -71,7 +88,8 @@ static gm_state_layout_t gm_state_layout(void* state, long long max_voxels) {
 }
 
 // the workspace: head (16 int32, padded to 128 bytes) | row_slot (num_rows int32) | tile counts | group totals | the dirty list
-// (num_rows (2 ring + 1)^3 int32: every winner appends at most that many), each rounded up to 16 bytes
+// (num_rows (2 ring + 1)^3 int32: every winner appends at most that many), each rounded up to 16 bytes.  A move has per_row = 2 words of
+// row_slot per row -- the slot left, the slot entered -- and so twice the dirty list
 struct gm_ws {
     int32_t* head;
     int32_t* row_slot;
@@ -79,13 +97,14 @@ struct gm_ws {
     int32_t* group;
     int32_t* dirty;
     long long dirty_cap;
+    int per_row;
 };
 struct gm_layout_t { gm_ws ws; size_t bytes; };
-static gm_layout_t gm_layout(void* workspace, long long num_rows, int ring) {
+static gm_layout_t gm_layout(void* workspace, long long num_rows, int ring, int per_row = 1) {
     epc_carver c(workspace);
-    const long long side = 2 * ring + 1, cap = num_rows * side * side * side;
-    return {{c.take<int32_t>(MP_HEAD, 128), c.take<int32_t>((size_t)num_rows, 16), c.take<int32_t>((size_t)mp_tiles(num_rows), 16),
-             c.take<int32_t>((size_t)mp_groups(num_rows), 16), c.take<int32_t>((size_t)cap, 16), cap}, c.bytes()};
+    const long long side = 2 * ring + 1, cap = per_row * num_rows * side * side * side;
+    return {{c.take<int32_t>(MP_HEAD, 128), c.take<int32_t>((size_t)(per_row * num_rows), 16), c.take<int32_t>((size_t)mp_tiles(num_rows), 16),
+             c.take<int32_t>((size_t)mp_groups(num_rows), 16), c.take<int32_t>((size_t)cap, 16), cap, per_row}, c.bytes()};
 }
 
 // ---- init: the table, the head, the outputs of no row --------------------------------------------------------------------------------------
@@ -165,18 +184,86 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_insert_kernel(const float*
     }
 }
 
+// ---- a move's launch 3: the rows out of their old cells and into their new ones (include/epcnet_remap.h, steps 1 to 4) -----------------------
+// new_poses == nullptr: remove -- no row has a new kind
+__global__ __launch_bounds__(MP_THREADS) void growmap_move_kernel(const float* __restrict__ points, const int32_t* __restrict__ offsets,
+                                                                  long long num_rows, int num_clouds, const double* __restrict__ old_poses,
+                                                                  const double* __restrict__ new_poses, sf_params pr, long long max_voxels,
+                                                                  gm_state st, gm_ws ws) {
+    __shared__ sf_tile_lds out, in;                    // the rows taken out, the rows put in
+    __shared__ int moved[5];                           // the tile's signed sums of the three kinds; rows put in; rows unmatched
+    if (ws.head[MP_BAD]) return;                       // (uniform: the launch before this one decided it)
+    const int tid = threadIdx.x;
+    const long long r0 = (long long)blockIdx.x * MP_TILE, r = r0 + tid;
+    const uint32_t epoch = st.head->epoch;
+    if (tid < 5) moved[tid] = 0;                       // (sf_tile_row's barriers stand between this and the first add)
+    long long wo[3], wn[3];
+    const int ko = sf_tile_row(points, offsets, num_rows, num_clouds, old_poses, st.head->origin, pr.voxel, out, r0, wo);
+    const int kn = new_poses ? sf_tile_row(points, offsets, num_rows, num_clouds, new_poses, st.head->origin, pr.voxel, in, r0, wn) : 4;
+    int so = -1, sn = -1;
+    bool won_o = false, won_n = false;
+    const bool unmoved = ko == 0 && kn == 0 && wo[0] == wn[0] && wo[1] == wn[1] && wo[2] == wn[2];
+    if (ko != 4 && !unmoved) {
+        bool matched = true;
+        if (ko == 0) {                                 // found AND numbered: a slot claimed in this call has no number yet
+            const long long at = sf_find(st.table, st.mask, mp_key(wo[0] >> 12, wo[1] >> 12, wo[2] >> 12));
+            matched = at >= 0 && mp_load(&st.table[at].number) != 0;
+            if (matched) so = (int)at;
+        }
+        if (!matched) {
+            atomicAdd(&moved[4], 1);
+        } else {
+            atomicAdd(&moved[ko], -1);
+            if (kn < 3) atomicAdd(&moved[kn], 1);
+            if (kn == 0) {
+                atomicAdd(&moved[3], 1);
+                sn = sf_claim(st.table, st.mask, mp_key(wn[0] >> 12, wn[1] >> 12, wn[2] >> 12), &st.head->claimed, max_voxels);   // -3: gave up
+            }
+            if (so >= 0) {
+                out.pos[tid][0] = (unsigned short)(wo[0] & 4095), out.pos[tid][1] = (unsigned short)(wo[1] & 4095);
+                out.pos[tid][2] = (unsigned short)(wo[2] & 4095);
+                uint32_t* tp = &st.table[so].touched;
+                if (__atomic_load_n(tp, __ATOMIC_RELAXED) != epoch) won_o = atomicExch(tp, epoch) != epoch;
+            }
+            if (sn >= 0) {
+                in.pos[tid][0] = (unsigned short)(wn[0] & 4095), in.pos[tid][1] = (unsigned short)(wn[1] & 4095);
+                in.pos[tid][2] = (unsigned short)(wn[2] & 4095);
+                sf_slot* t = st.table + sn;
+                if (mp_load(&t->number) == 0) {        // claimed in this call: it has a leader to find
+                    int32_t* lead = &t->leader;
+                    if (mp_load(lead) > (int)r) atomicMin(lead, (int)r);
+                }
+                if (__atomic_load_n(&t->touched, __ATOMIC_RELAXED) != epoch) won_n = atomicExch(&t->touched, epoch) != epoch;
+            }
+        }
+    }
+    if (r < num_rows) {
+        ws.row_slot[2 * r] = won_o ? so | GM_WON : so;
+        ws.row_slot[2 * r + 1] = won_n ? sn | GM_WON : sn;
+    }
+    out.slot[tid] = so, in.slot[tid] = sn;
+    __syncthreads();
+    sf_add_rows<true>(st.table, out);
+    sf_add_rows(st.table, in);
+    __syncthreads();
+    if (tid < 3 && moved[tid]) atomicAdd(&st.head->kept[tid], moved[tid]);
+    if (tid == 3 && moved[3]) atomicAdd(&ws.head[MP_KEPT], moved[3]);
+    if (tid == 4 && moved[4]) atomicAdd(&ws.head[GM_UNMATCHED], moved[4]);
+}
+
 // the call changes no voxel: it was refused, or more voxels than max_voxels were claimed (row_slot and the table may not be followed)
 __device__ __forceinline__ bool gm_no_map(const gm_state& st, const gm_ws& ws, long long max_voxels) {
     return ws.head[MP_BAD] != 0 || (long long)st.head->claimed > max_voxels;
 }
 
-// row r leads a voxel that is new in this call: its slot has no number and names it the leader (a numbered slot's leader is stale)
-__device__ __forceinline__ int gm_is_leader(const gm_state& st, const gm_ws& ws, long long r, long long num_rows, int* slot, bool* won) {
-    *slot = -1, *won = false;
+// row r leads a voxel that is new in this call: the slot it entered -- the last of its row_slot words -- has no number and names it the
+// leader (a numbered slot's leader is stale)
+__device__ __forceinline__ int gm_is_leader(const gm_state& st, const gm_ws& ws, long long r, long long num_rows, int* slot) {
+    *slot = -1;
     if (r >= num_rows) return 0;
-    const int s = ws.row_slot[r];
+    const int s = ws.row_slot[r * ws.per_row + (ws.per_row - 1)];
     if (s < 0) return 0;
-    *slot = s & (GM_WON - 1), *won = (s & GM_WON) != 0;
+    *slot = s & (GM_WON - 1);
     const sf_slot* t = st.table + *slot;
     return mp_load(&t->number) == 0 && t->leader == (int)r ? 1 : 0;
 }
@@ -186,27 +273,31 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_mark_kernel(long long num_
     __shared__ int part[MP_THREADS / 64];
     if (gm_no_map(st, ws, max_voxels)) return;
     int slot, total;
-    bool won;
-    block_scan<MP_THREADS / 64, int>(gm_is_leader(st, ws, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot, &won), part, total);
+    const long long r = (long long)blockIdx.x * MP_TILE + threadIdx.x;
+    block_scan<MP_THREADS / 64, int>(gm_is_leader(st, ws, r, num_rows, &slot), part, total);
     if (threadIdx.x == 0) ws.tile[blockIdx.x] = total;
-    if (!won) return;
+    if (r >= num_rows) return;
     const uint32_t epoch = st.head->epoch;
-    long long g0, g1, g2;
-    sf_cell(st.table[slot].key, g0, g1, g2);
-    for (int o2 = -ring; o2 <= ring; ++o2) {
-        if (!sf_in_range(g2 + o2)) continue;
-        for (int o1 = -ring; o1 <= ring; ++o1) {
-            if (!sf_in_range(g1 + o1)) continue;
-            for (int o0 = -ring; o0 <= ring; ++o0) {
-                if (!sf_in_range(g0 + o0)) continue;
-                const long long at = sf_find(st.table, st.mask, mp_key(g0 + o0, g1 + o1, g2 + o2));
-                if (at < 0) continue;
-                uint32_t* dp = &st.table[at].dirty;
-                // (one atomic add per flipped slot.  Lanes of a wave that flip in the same step sharing ONE add -- a ballot -- measured
-                // the same: 0.327 against 0.329 ms per add of 80 000 rows into an empty map, 0.811 against 0.818 ms into 1.43 M voxels)
-                if (__atomic_load_n(dp, __ATOMIC_RELAXED) != epoch && atomicExch(dp, epoch) != epoch) {
-                    const int k = atomicAdd(&ws.head[GM_DIRTY], 1);
-                    if ((long long)k < ws.dirty_cap) ws.dirty[k] = (int)at;    // (k < cap always: the bound only keeps a wrong count inside)
+    for (int word = 0; word < ws.per_row; ++word) {    // an add's one slot; a move's slot left and slot entered
+        const int s = ws.row_slot[r * ws.per_row + word];
+        if (s < 0 || !(s & GM_WON)) continue;
+        long long g0, g1, g2;
+        sf_cell(st.table[s & (GM_WON - 1)].key, g0, g1, g2);
+        for (int o2 = -ring; o2 <= ring; ++o2) {
+            if (!sf_in_range(g2 + o2)) continue;
+            for (int o1 = -ring; o1 <= ring; ++o1) {
+                if (!sf_in_range(g1 + o1)) continue;
+                for (int o0 = -ring; o0 <= ring; ++o0) {
+                    if (!sf_in_range(g0 + o0)) continue;
+                    const long long at = sf_find(st.table, st.mask, mp_key(g0 + o0, g1 + o1, g2 + o2));
+                    if (at < 0) continue;
+                    uint32_t* dp = &st.table[at].dirty;
+                    // (one atomic add per flipped slot.  Lanes of a wave that flip in the same step sharing ONE add -- a ballot -- measured
+                    // the same: 0.327 against 0.329 ms per add of 80 000 rows into an empty map, 0.811 against 0.818 ms into 1.43 M voxels)
+                    if (__atomic_load_n(dp, __ATOMIC_RELAXED) != epoch && atomicExch(dp, epoch) != epoch) {
+                        const int k = atomicAdd(&ws.head[GM_DIRTY], 1);
+                        if ((long long)k < ws.dirty_cap) ws.dirty[k] = (int)at;    // (k < cap always: the bound only keeps a wrong count inside)
+                    }
                 }
             }
         }
@@ -244,15 +335,14 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_top_kernel(long long group
     num_call[0] = over ? -1 : fresh;
     num_call[1] = ws.head[MP_KEPT];
     num_call[2] = over ? 0 : (long long)dirty < ws.dirty_cap ? dirty : (int)ws.dirty_cap;
-    num_call[3] = 0;
+    num_call[3] = ws.head[GM_UNMATCHED];               // (an add: the cleared word)
 }
 
 __global__ __launch_bounds__(MP_THREADS) void growmap_number_kernel(long long num_rows, long long max_voxels, gm_state st, gm_ws ws) {
     __shared__ int part[MP_THREADS / 64];
     if (gm_no_map(st, ws, max_voxels)) return;
     int slot, total;
-    bool won;
-    const int lead = gm_is_leader(st, ws, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot, &won);
+    const int lead = gm_is_leader(st, ws, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot);
     const int place = block_scan<MP_THREADS / 64, int>(lead, part, total);
     if (!lead) return;
     const long long j = (long long)ws.head[GM_VBASE] + ws.group[blockIdx.x / MP_GROUP] + ws.tile[blockIdx.x] + place;
@@ -298,13 +388,32 @@ extern "C" size_t epcnet_surfel_map_add_workspace_bytes(long long num_rows, int 
     return gm_layout(nullptr, num_rows, ring).bytes;
 }
 
-#define GM_CHECK_STATE(state, state_bytes, max_voxels)                                                                         \
+// the refusals of an entry `who` (init checks under its own name; add and move share gm_call, which is told the entry's)
+#define GM_CHECK_ARG(who, cond, msg)                                                                                           \
     do {                                                                                                                       \
-        EPC_CHECK_ARG(epc_aligned16(state), "state must be 16-byte aligned");                                                  \
-        if ((state_bytes) < epcnet_surfel_map_state_bytes(max_voxels)) {                                                       \
-            epc_set_error("%s: state of %zu bytes, %zu needed", __func__, (size_t)(state_bytes),                               \
-                          epcnet_surfel_map_state_bytes(max_voxels));                                                          \
+        if (!(cond)) {                                                                                                         \
+            epc_set_error("%s: %s", who, msg);                                                                                 \
+            return EPC_EINVAL;                                                                                                 \
+        }                                                                                                                      \
+    } while (0)
+#define GM_CHECK_BYTES(who, what, bytes, need)                                                                                 \
+    do {                                                                                                                       \
+        if ((bytes) < (need)) {                                                                                                \
+            epc_set_error("%s: %s of %zu bytes, %zu needed", who, what, (size_t)(bytes), (size_t)(need));                      \
             return EPC_ENOMEM;                                                                                                 \
+        }                                                                                                                      \
+    } while (0)
+#define GM_CHECK_STATE(who, state, state_bytes, max_voxels)                                                                    \
+    do {                                                                                                                       \
+        GM_CHECK_ARG(who, epc_aligned16(state), "state must be 16-byte aligned");                                              \
+        GM_CHECK_BYTES(who, "state", state_bytes, epcnet_surfel_map_state_bytes(max_voxels));                                  \
+    } while (0)
+#define GM_CHECK_LAUNCH(who)                                                                                                   \
+    do {                                                                                                                       \
+        hipError_t e__ = hipGetLastError();                                                                                    \
+        if (e__ != hipSuccess) {                                                                                               \
+            epc_set_error("%s: launch failed: %s", who, hipGetErrorString(e__));                                               \
+            return EPC_EHIP;                                                                                                   \
         }                                                                                                                      \
     } while (0)
 
@@ -315,7 +424,7 @@ extern "C" int epcnet_surfel_map_init(const double* origin, const double* params
     EPC_CHECK_ARG(max_voxels >= 1 && max_voxels <= (1ll << 28), "need 1 <= max_voxels <= 2^28");
     const char* const refusal = sf_params_refusal(params);
     EPC_CHECK_ARG(!refusal, refusal);
-    GM_CHECK_STATE(state, state_bytes, max_voxels);
+    GM_CHECK_STATE(__func__, state, state_bytes, max_voxels);
     const gm_state st = gm_state_layout(state, max_voxels).st;
     const unsigned long long blocks = ((st.mask + 1) * 16 + MP_THREADS - 1) / MP_THREADS;
     hipLaunchKernelGGL(growmap_init_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(MP_THREADS), 0, (hipStream_t)stream, origin,
@@ -324,49 +433,80 @@ extern "C" int epcnet_surfel_map_init(const double* origin, const double* params
     return EPC_OK;
 }
 
+
+
+extern "C" size_t epcnet_surfel_map_move_workspace_bytes(long long num_rows, int num_clouds, int ring) {
+    if (!sf_rows_supported(num_rows, num_clouds) || ring < 0 || ring > EPC_SURFEL_MAX_RING) return 0;
+    return gm_layout(nullptr, num_rows, ring, 2).bytes;
+}
+
+// add and move: the same refusals and the same launches around ONE tile kernel of their own -- the insert, or the move (then row_slot
+// has two words per row and new_poses may be NULL: remove)
+static int gm_call(const char* who, bool move, const float* points, const int32_t* offsets, long long num_rows, int num_clouds,
+                   const double* poses, const double* new_poses, const double* params, long long max_voxels, void* state, size_t state_bytes,
+                   float* map_points, int32_t* count, float* centroid, float* normal, float* eigen, int32_t* support, int32_t* num_out,
+                   int32_t* num_call, void* workspace, size_t workspace_bytes, void* stream) {
+    GM_CHECK_ARG(who, points && offsets && poses && params && state && map_points && count && centroid && normal && eigen && support &&
+                          num_out && num_call && workspace,
+                 "null pointer");
+    GM_CHECK_ARG(who, num_rows >= 0 && num_rows < 2147483648ll, "need 0 <= num_rows < 2^31");
+    GM_CHECK_ARG(who, num_clouds >= 0 && num_clouds <= (1 << 24), "need 0 <= num_clouds <= 2^24");
+    GM_CHECK_ARG(who, max_voxels >= 1 && max_voxels <= (1ll << 28), "need 1 <= max_voxels <= 2^28");
+    const char* const refusal = sf_params_refusal(params);
+    GM_CHECK_ARG(who, !refusal, refusal);
+    GM_CHECK_STATE(who, state, state_bytes, max_voxels);
+    const sf_params pr = sf_params_of(params);
+    GM_CHECK_ARG(who, epc_aligned16(workspace), "workspace must be 16-byte aligned");
+    const gm_layout_t layout = gm_layout(workspace, num_rows, pr.ring, move ? 2 : 1);
+    GM_CHECK_BYTES(who, "workspace", workspace_bytes, layout.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const gm_state st = gm_state_layout(state, max_voxels).st;
+    const gm_ws ws = layout.ws;
+    const long long tiles = mp_tiles(num_rows), groups = mp_groups(num_rows);
+    if (int rc = scan_clear_words_launch(ws.head, MP_HEAD, s, who)) return rc;
+    const long long checks = num_clouds > 0 ? ((long long)num_clouds + MP_THREADS - 1) / MP_THREADS : 1;
+    hipLaunchKernelGGL(growmap_check_kernel, dim3((unsigned)checks), dim3(MP_THREADS), 0, s, offsets, num_rows, num_clouds, gm_bits_of(params),
+                       max_voxels, st, ws);
+    GM_CHECK_LAUNCH(who);
+    if (tiles > 0) {
+        if (move)
+            hipLaunchKernelGGL(growmap_move_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, points, offsets, num_rows, num_clouds, poses,
+                               new_poses, pr, max_voxels, st, ws);
+        else
+            hipLaunchKernelGGL(growmap_insert_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, points, offsets, num_rows, num_clouds, poses,
+                               pr, max_voxels, st, ws);
+        GM_CHECK_LAUNCH(who);
+        hipLaunchKernelGGL(growmap_mark_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, num_rows, pr.ring, max_voxels, st, ws);
+        GM_CHECK_LAUNCH(who);
+        hipLaunchKernelGGL(growmap_group_kernel, dim3((unsigned)groups), dim3(MP_GROUP), 0, s, tiles, max_voxels, st, ws);
+        GM_CHECK_LAUNCH(who);
+    }
+    hipLaunchKernelGGL(growmap_top_kernel, dim3(1), dim3(MP_THREADS), 0, s, groups, max_voxels, st, ws, num_out, num_call);
+    GM_CHECK_LAUNCH(who);
+    if (tiles > 0) {
+        hipLaunchKernelGGL(growmap_number_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, num_rows, max_voxels, st, ws);
+        GM_CHECK_LAUNCH(who);
+        // a call's dirty voxels: at most (2 ring + 1)^3 per slot that a row left or entered, and never more than the map holds
+        const long long bound = ws.dirty_cap < max_voxels ? ws.dirty_cap : max_voxels;
+        hipLaunchKernelGGL(growmap_emit_kernel, dim3((unsigned)((bound + MP_THREADS - 1) / MP_THREADS)), dim3(MP_THREADS), 0, s, max_voxels, pr,
+                           st, ws, map_points, count, centroid, normal, eigen, support);
+        GM_CHECK_LAUNCH(who);
+    }
+    return EPC_OK;
+}
+
 extern "C" int epcnet_surfel_map_add(const float* points, const int32_t* offsets, long long num_rows, int num_clouds, const double* poses,
                                      const double* params, long long max_voxels, void* state, size_t state_bytes, float* map_points,
                                      int32_t* count, float* centroid, float* normal, float* eigen, int32_t* support, int32_t* num_out,
                                      int32_t* num_call, void* workspace, size_t workspace_bytes, void* stream) {
-    EPC_CHECK_ARG(points && offsets && poses && params && state && map_points && count && centroid && normal && eigen && support &&
-                      num_out && num_call && workspace,
-                  "null pointer");
-    EPC_CHECK_ARG(num_rows >= 0 && num_rows < 2147483648ll, "need 0 <= num_rows < 2^31");
-    EPC_CHECK_ARG(num_clouds >= 0 && num_clouds <= (1 << 24), "need 0 <= num_clouds <= 2^24");
-    EPC_CHECK_ARG(max_voxels >= 1 && max_voxels <= (1ll << 28), "need 1 <= max_voxels <= 2^28");
-    const char* const refusal = sf_params_refusal(params);
-    EPC_CHECK_ARG(!refusal, refusal);
-    GM_CHECK_STATE(state, state_bytes, max_voxels);
-    const sf_params pr = sf_params_of(params);
-    EPC_CHECK_WORKSPACE(workspace, workspace_bytes, epcnet_surfel_map_add_workspace_bytes(num_rows, num_clouds, pr.ring));
-    hipStream_t s = (hipStream_t)stream;
-    const gm_state st = gm_state_layout(state, max_voxels).st;
-    const gm_ws ws = gm_layout(workspace, num_rows, pr.ring).ws;
-    const long long tiles = mp_tiles(num_rows), groups = mp_groups(num_rows);
-    if (int rc = scan_clear_words_launch(ws.head, MP_HEAD, s, __func__)) return rc;
-    const long long checks = num_clouds > 0 ? ((long long)num_clouds + MP_THREADS - 1) / MP_THREADS : 1;
-    hipLaunchKernelGGL(growmap_check_kernel, dim3((unsigned)checks), dim3(MP_THREADS), 0, s, offsets, num_rows, num_clouds, gm_bits_of(params),
-                       max_voxels, st, ws);
-    EPC_CHECK_LAUNCH();
-    if (tiles > 0) {
-        hipLaunchKernelGGL(growmap_insert_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, points, offsets, num_rows, num_clouds, poses, pr,
-                           max_voxels, st, ws);
-        EPC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(growmap_mark_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, num_rows, pr.ring, max_voxels, st, ws);
-        EPC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(growmap_group_kernel, dim3((unsigned)groups), dim3(MP_GROUP), 0, s, tiles, max_voxels, st, ws);
-        EPC_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(growmap_top_kernel, dim3(1), dim3(MP_THREADS), 0, s, groups, max_voxels, st, ws, num_out, num_call);
-    EPC_CHECK_LAUNCH();
-    if (tiles > 0) {
-        hipLaunchKernelGGL(growmap_number_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, num_rows, max_voxels, st, ws);
-        EPC_CHECK_LAUNCH();
-        // a call's dirty voxels: at most (2 ring + 1)^3 per row, and never more than the map holds
-        const long long bound = ws.dirty_cap < max_voxels ? ws.dirty_cap : max_voxels;
-        hipLaunchKernelGGL(growmap_emit_kernel, dim3((unsigned)((bound + MP_THREADS - 1) / MP_THREADS)), dim3(MP_THREADS), 0, s, max_voxels, pr,
-                           st, ws, map_points, count, centroid, normal, eigen, support);
-        EPC_CHECK_LAUNCH();
-    }
-    return EPC_OK;
+    return gm_call(__func__, false, points, offsets, num_rows, num_clouds, poses, nullptr, params, max_voxels, state, state_bytes, map_points,
+                   count, centroid, normal, eigen, support, num_out, num_call, workspace, workspace_bytes, stream);
+}
+
+extern "C" int epcnet_surfel_map_move(const float* points, const int32_t* offsets, long long num_rows, int num_clouds, const double* old_poses,
+                                      const double* new_poses, const double* params, long long max_voxels, void* state, size_t state_bytes,
+                                      float* map_points, int32_t* count, float* centroid, float* normal, float* eigen, int32_t* support,
+                                      int32_t* num_out, int32_t* num_call, void* workspace, size_t workspace_bytes, void* stream) {
+    return gm_call(__func__, true, points, offsets, num_rows, num_clouds, old_poses, new_poses, params, max_voxels, state, state_bytes, map_points,
+                   count, centroid, normal, eigen, support, num_out, num_call, workspace, workspace_bytes, stream);
 }

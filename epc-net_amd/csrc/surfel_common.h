@@ -133,7 +133,8 @@ __device__ __forceinline__ int sf_claim(sf_slot* __restrict__ table, unsigned lo
 
 // The tile's adds, behind a barrier that follows the last write of lds.slot / lds.pos: sixteen lanes per row, one per word of its slot
 // (1 the count, 2..4 the 12-bit sums, 5..7 A, 8..13 B; the key's lane and the last two idle): a wave-instruction adds to four slots of 104
-// contiguous bytes each.
+// contiguous bytes each.  NEGATE: the rows are taken OUT (growmap.hip's move) -- the two's-complement negation is added, unsigned wrap-around.
+template <bool NEGATE = false>
 __device__ __forceinline__ void sf_add_rows(sf_slot* __restrict__ table, const sf_tile_lds& lds) {
     const int tid = threadIdx.x, word = tid & 15;
     for (int it = 0; it < MP_TILE / 16; ++it) {
@@ -146,7 +147,7 @@ __device__ __forceinline__ void sf_add_rows(sf_slot* __restrict__ table, const s
                                                                                          : (word == 3 ? p1 : word == 4 ? p2 : word == 6 ? u1 : u2))
                                                   : (word < 11 ? u0 : word < 13 ? u1 : u2);
             const unsigned long long y = word < 8 ? 1ull : (word == 8 ? u0 : word == 9 || word == 11 ? u1 : u2);
-            atomicAdd(reinterpret_cast<unsigned long long*>(table + sl) + word, x * y);
+            atomicAdd(reinterpret_cast<unsigned long long*>(table + sl) + word, NEGATE ? 0ull - x * y : x * y);
         }
     }
 }
@@ -220,7 +221,7 @@ __device__ __forceinline__ void sf_rotate(double& app, double& aqq, double& apq,
 
 __device__ __forceinline__ double sf_pick(int k, double x0, double x1, double x2) { return k == 0 ? x0 : k == 1 ? x1 : x2; }
 
-// map_points and count of voxel j from its slot
+// map_points and count of voxel j from its slot (a voxel that a move emptied: count 0, NaN, nothing divided by)
 __device__ __forceinline__ void sf_write_mean(const sf_slot* __restrict__ t, const sf_params& pr, long long j, float* __restrict__ map_points,
                                               int32_t* __restrict__ count) {
 #pragma clang fp contract(off)
@@ -228,8 +229,8 @@ __device__ __forceinline__ void sf_write_mean(const sf_slot* __restrict__ t, con
     const long long cnt = (long long)t->cnt;
     long long g0, g1, g2;
     sf_cell(t->key, g0, g1, g2);
-    const long long m0 = (long long)(t->sum[0] / (unsigned long long)cnt), m1 = (long long)(t->sum[1] / (unsigned long long)cnt),
-                    m2 = (long long)(t->sum[2] / (unsigned long long)cnt);
+    const unsigned long long by = cnt != 0 ? (unsigned long long)cnt : 1ull;
+    const long long m0 = (long long)(t->sum[0] / by), m1 = (long long)(t->sum[1] / by), m2 = (long long)(t->sum[2] / by);
     const bool keep = cnt >= pr.min_count;
     map_points[(size_t)j * 3] = keep ? (float)((double)(g0 * 4096 + m0) * pr.step) : nan;
     map_points[(size_t)j * 3 + 1] = keep ? (float)((double)(g1 * 4096 + m1) * pr.step) : nan;

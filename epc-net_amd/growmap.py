@@ -1,6 +1,7 @@
 """The surfel map that grows across calls (include/epcnet_growmap.h), none of it with a counterpart in the reference: ``SurfelMap`` owns
 the persistent state and the seven output tensors of ``fuse_surfels`` on the device, and ``add`` puts further posed clouds into them at a
-cost that follows the rows added, not the size of the map.  Contiguous tensors of the exact dtype or a refusal, nothing read back, every
+cost that follows the rows added, not the size of the map; ``remove`` and ``repose`` (include/epcnet_remap.h) take clouds out or move
+them to corrected poses at a cost that follows the rows moved.  Contiguous tensors of the exact dtype or a refusal, nothing read back, every
 call asynchronous and capturable in a graph.  ``ops`` re-exports ``SurfelMap``."""
 from __future__ import annotations
 
@@ -38,8 +39,10 @@ class SurfelMap:
         pose, fit, hessian, info, st = ops.localize_scans(cloud, index, m.centroid, normal_of(m), seeds)
         m.add(scan_points, scan_offsets, pose)                                  # the localised scan goes in
 
-    (``normal_of``: the caller's planarity filter, see ``index_surfels``.)  Not covered: the index patched in place, removing rows,
-    re-posing rows after a later loop closure, moving the origin, ray-casting."""
+    (``normal_of``: the caller's planarity filter, see ``index_surfels``.)  After a loop closure, ``repose`` moves the submaps it
+    corrected and ``remove`` takes clouds out (include/epcnet_remap.h; restatement: tests/remap_ref.py): voxels left without a row keep
+    their number as empty voxels, ``count`` 0.  Not covered: the index patched in place, compaction of empty voxels (``reset()`` and
+    ``add``), moving the origin, ray-casting."""
 
     def __init__(self, max_voxels, voxel=0.2, origin=None, min_count=1, ring=1, min_support=8, device=None):
         who = "SurfelMap"
@@ -106,3 +109,52 @@ class SurfelMap:
         if own:
             ws.record_stream(torch.cuda.current_stream(dev))
         return num_call
+
+    def _move(self, who, points, offsets, old_poses, new_poses, workspace):
+        if self.origin is None:
+            raise L.EpcNetError(-1, "%s: the map has no origin yet (origin=None and no add): it holds no row to move" % who)
+        if new_poses is not None:
+            for name, p in (("old_poses", old_poses), ("new_poses", new_poses)):
+                _device_tensor(who, name, p, torch.float64)
+            if tuple(new_poses.shape) != tuple(old_poses.shape):
+                raise L.EpcNetError(-1, "%s: old_poses and new_poses must have one shape, got %s and %s"
+                                    % (who, tuple(old_poses.shape), tuple(new_poses.shape)))
+            if new_poses.device != old_poses.device:
+                raise L.EpcNetError(-1, "%s: old_poses live on %s, new_poses on %s" % (who, old_poses.device, new_poses.device))
+        C, rows, dev, old_poses, _, _, _, _, _ = _map_arguments(who, points, offsets, old_poses, self.voxel, self.origin, self.max_voxels,
+                                                                self.min_count, "epcnet_map_surfels_workspace_bytes")
+        if dev != self.device:
+            raise L.EpcNetError(-1, "%s: points live on %s, the map on %s" % (who, dev, self.device))
+        need = int(L.lib().epcnet_surfel_map_move_workspace_bytes(rows, C, self.ring))
+        ws, own = _workspace(who, need, workspace, dev)
+        num_call = torch.empty(4, dtype=torch.int32, device=dev)
+        spare = _spare(dev, torch.float64)
+        L.run.epcnet_surfel_map_move(points if rows else _spare(dev), offsets, rows, C, old_poses if C else spare,
+                                     None if new_poses is None else new_poses.reshape(C, 12) if C else spare, self._params, self.max_voxels,
+                                     self.state, self.state.numel(), *self._arrays(), num_call, ws, ws.numel())
+        if own:
+            ws.record_stream(torch.cuda.current_stream(dev))
+        return num_call
+
+    def remove(self, points, offsets, poses, workspace: Optional[torch.Tensor] = None):
+        """Clouds that were added at ``poses`` OUT of the map (epcnet_surfel_map_move of include/epcnet_remap.h with no new poses) ->
+        ``num_call`` (4,) int32 device tensor: -1 (refused on the device, or an overflowed map) or 0, 0, voxels solved again, rows
+        unmatched.  ``points``, ``offsets``, ``poses``: exactly what ``add`` was given, under its checks (FLOAT64 poses or a refusal).  Every
+        row leaves the voxel that pose puts it in -- the sums are integers, so what stays is bit for bit the map of the remaining rows --;
+        a voxel left with no row keeps its number as an EMPTY voxel: ``count`` 0 and NaN rows, still counted in ``num_out[0]`` and in
+        ``max_voxels`` (compaction is ``reset()`` and ``add``).  A row whose cell was no voxel before the call was never added: it is
+        skipped and counted as unmatched.  Refused on a map that has no origin yet.  Same stream, capture and ``workspace`` rules as
+        ``add``, sized by ``epcnet_surfel_map_move_workspace_bytes(rows, C, ring)``."""
+        return self._move("SurfelMap.remove", points, offsets, poses, None, workspace)
+
+    def repose(self, points, offsets, old_poses, new_poses, workspace: Optional[torch.Tensor] = None):
+        """Clouds that are in the map at ``old_poses`` moved to ``new_poses`` (epcnet_surfel_map_move) -- what a loop closure asks
+        for: ``retrieval.close_loops`` returns corrected submap poses, and the submaps go where they belong at a cost that follows THEIR
+        rows, not the map's -> ``num_call`` (4,) int32 device tensor: voxels new in this call (-1: refused on the device, or an
+        overflowed map), rows put in, voxels solved again, rows unmatched.  Both pose tensors: FLOAT64, of one shape, (C, 12) or
+        (C, 3, 4).  A row is taken out of the cell its old pose gives and put into the cell its new pose gives; a row whose lattice
+        position does not change touches nothing (pass every submap with the poses before and after: the ones the closure left alone
+        cost two transforms per row).  Afterwards every voxel that holds rows equals, bit for bit and matched by cell, what
+        ``fuse_surfels`` returns for all rows at their current poses; empty voxels as ``remove`` leaves them.  Only the voxels within
+        ``ring`` of a cell that lost or received a row are written.  Refused on a map that has no origin yet."""
+        return self._move("SurfelMap.repose", points, offsets, old_poses, new_poses, workspace)

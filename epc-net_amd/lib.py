@@ -98,7 +98,8 @@ _HEADERS = (
     ("surfels", "SURFEL", False, False),        # SURFEL_EXPORTS, SURFELS_HEADER_PATH: the map with a surfel per voxel
     ("localize", "LOCALIZE", False, False),     # LOCALIZE_EXPORTS, LOCALIZE_HEADER_PATH: scans localised against the surfel map
     ("forms", "FORM", False, False),            # FORM_EXPORTS, FORMS_HEADER_PATH: test / tuning entries that name a kernel's form
-    ("growmap", "GROWMAP", False, False))       # GROWMAP_EXPORTS, GROWMAP_HEADER_PATH: the surfel map that grows across calls
+    ("growmap", "GROWMAP", False, False),       # GROWMAP_EXPORTS, GROWMAP_HEADER_PATH: the surfel map that grows across calls
+    ("remap", "REMAP", False, False))           # REMAP_EXPORTS, REMAP_HEADER_PATH: rows taken out of that map, or re-posed in it
 
 
 def _bind_header(text, header, doubles, declared, constants):

@@ -76,7 +76,8 @@ extern "C" {
  * ring).
  *
  * Not covered: the localisation index of epcnet_localize.h patched in place (it is rebuilt from the arrays: a quarter of a millisecond
- * at 1.4 M voxels); removing rows; re-posing rows after a later loop closure; moving the origin; ray-casting (free space). */
+ * at 1.4 M voxels); moving the origin; ray-casting (free space).  Removing rows and re-posing rows after a later loop closure are
+ * epcnet_remap.h's epcnet_surfel_map_move, on this state: a voxel it leaves without a row keeps slot and number, with count 0. */
 #define EPC_GROWMAP_HEAD_BYTES 256
 size_t epcnet_surfel_map_state_bytes(long long max_voxels);
 int epcnet_surfel_map_init(const double* origin, const double* params, long long max_voxels, void* state, size_t state_bytes,
