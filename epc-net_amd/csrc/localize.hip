@@ -14,30 +14,27 @@
 // The localisation: scans, seeds and the index are device data, every grid is sized from Q, H and n alone, nothing is read back.
 //   lz_prep_kernel     one workgroup per scan: the rows that are not absent, which seeds are finite (or the identity where there are
 //                      none), whether the index records this M and voxel; writes the scan's state and the run flags of stage A
-//   lz_corr_kernel     the hot path, one per pass.  Grid (scan, seed, chunk of LZ_CHUNK rows), one row per lane.  The 27 lookups are
+//   lz_corr_kernel     the hot path, one per pass.  Grid (scan, seed, chunk of PS_CHUNK rows), one row per lane.  The 27 lookups are
 //                      latency-bound (the table is far larger than L2): the nine first-slot reads of a plane of cells are issued
 //                      before the first is consumed, the walk past a foreign key is the rare case.  Then residual, Jacobian, the
 //                      chunk's 29 subtree sums: a lane-xor butterfly (xor 1, 2, .. 32 = adjacent pairing), then the four waves
-//   lz_solve_kernel    one wave per scan: a lane per sum finishes the tree over the chunks, lane 0 goes on alone; after stage A chooses the seed; solves (Cholesky,
-//                      retraction) for the next pass's pose; after the final pass writes the five outputs
+//   lz_solve_kernel    one wave per scan: a lane per sum finishes the tree over the chunks, lane 0 goes on alone; after stage A
+//                      chooses the seed; solves (Cholesky, retraction) for the next pass's pose; after the final pass writes the five
+//                      outputs
 // The localisation has no atomics and reads no workspace word that an earlier kernel of the same call has not written.  No inline
 // assembly, no scratch.
+// What the localisation shares with register.hip -- the limits, the workspace, the seeds' half of the prep kernel, the correspondence
+// kernel's source row and chunk sums, the tree over the chunks, the host's launch sequence -- and the Cholesky, its substitutions and
+// the rotation of a quaternion are pose_common.h's (ps_*).
 #include "map_common.h"
-#include "../../include/epcnet_pairs.h"
+#include "pose_common.h"
 #include "../../include/epcnet_localize.h"
 
-#include <float.h>
 #include <math.h>
 
 #define LZ_THREADS 256
-#define LZ_CHUNK 256           // rows per workgroup of the correspondence kernel: one per thread
-#define LZ_MAX_N 4096          // the leaves of the summation tree
-#define LZ_MAX_CHUNKS (LZ_MAX_N / LZ_CHUNK)
 #define LZ_SUMS 29
-#define LZ_MAX_SCANS (1 << 20)
-#define LZ_MAX_SEEDS 64
 #define LZ_MAX_M (1ll << 28)
-#define LZ_STATE 4             // int32 per scan: status (0 = still running), best seed, rows, 0
 #define LZ_HEAD 32             // int32 in front of the table (128 bytes)
 #define LZ_ABSENT 0            //   [0] surfels not present   [1] out of range   [2] indexed   [3] duplicates
 #define LZ_RANGE 1
@@ -210,39 +207,14 @@ __global__ __launch_bounds__(LZ_THREADS) void lz_prep_kernel(const float* __rest
                                                              int num_seeds, const int32_t* __restrict__ head, long long M, double voxel,
                                                              int32_t* __restrict__ state, int32_t* __restrict__ run_a,
                                                              double* __restrict__ cur) {
-    __shared__ int part[LZ_THREADS / 64];
-    __shared__ int any_seed;
     const int q = blockIdx.x, tid = threadIdx.x;
     const unsigned long long bits = (unsigned long long)__double_as_longlong(voxel);
     const bool index_ok = head[LZ_HEAD_M] == (int32_t)M && head[LZ_HEAD_M + 1] == (int32_t)(bits & 0xffffffffull) &&
                           head[LZ_HEAD_M + 2] == (int32_t)(bits >> 32);                       // (uniform)
-    if (tid == 0) any_seed = 0;
-    __syncthreads();
     const float* __restrict__ src = scans + (size_t)q * n * 3;
-    int rows = 0;
-    for (int i = tid; i < n; i += LZ_THREADS) rows += epc_finite3(src[3 * i], src[3 * i + 1], src[3 * i + 2]) ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) rows += __shfl_xor(rows, off);
-    if ((tid & 63) == 0) part[tid >> 6] = rows;
-    if (tid < num_seeds) {
-        bool ok = index_ok;
-        if (seeds) {
-            const double* __restrict__ m = seeds + ((size_t)q * num_seeds + tid) * 12;
-#pragma unroll
-            for (int c = 0; c < 12; ++c) ok = ok && __builtin_isfinite(m[c]);
-        }
-        run_a[(size_t)q * num_seeds + tid] = ok ? 1 : 0;
-        if (ok) any_seed = 1;                          // every writer writes the same value
-    }
-    if (!seeds && tid < 12) cur[(size_t)q * 12 + tid] = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
-    __syncthreads();
-    if (tid == 0) {
-        int32_t* st = state + (size_t)q * LZ_STATE;
-        st[0] = any_seed ? 0 : EPC_STATUS_NO_PAIR;
-        st[1] = -1;
-        st[2] = (part[0] + part[1]) + (part[2] + part[3]);
-        st[3] = 0;
-    }
+    int rows[1] = {0};
+    for (int i = tid; i < n; i += LZ_THREADS) rows[0] += epc_finite3(src[3 * i], src[3 * i + 1], src[3 * i + 2]) ? 1 : 0;
+    ps_prep_item(q, index_ok, rows, seeds, num_seeds, state, run_a, cur);
 }
 
 // ---- the correspondence pass -------------------------------------------------------------------------------------------------------------
@@ -287,27 +259,22 @@ __device__ __forceinline__ void lz_candidate(const uint4* __restrict__ words, un
 
 // poses (Q, num_seeds, 12); run (Q, num_seeds): 0 = this pass is not wanted, nothing is written; sums (Q, num_seeds, chunks, 29).
 // Grid (Q, num_seeds, chunks).  (A run flag is only set where the index records this M: mask is the table's.)
-__global__ __launch_bounds__(LZ_CHUNK) void lz_corr_kernel(const float* __restrict__ scans, int n, const double* __restrict__ poses,
+__global__ __launch_bounds__(PS_CHUNK) void lz_corr_kernel(const float* __restrict__ scans, int n, const double* __restrict__ poses,
                                                            const int32_t* __restrict__ run, const lz_slot* __restrict__ table,
                                                            unsigned long long mask, double voxel, float gate2,
                                                            double* __restrict__ sums) {
-    __shared__ double part[LZ_CHUNK / 64][LZ_SUMS];
+    __shared__ double part[PS_CHUNK / 64][LZ_SUMS];
     const int q = blockIdx.x, h = blockIdx.y, chunk = blockIdx.z, tid = threadIdx.x;
     const size_t qh = (size_t)q * gridDim.y + h;
     if (!run[qh]) return;
-    const float* __restrict__ src = scans + (size_t)q * n * 3;
-    const int i = chunk * LZ_CHUNK + tid;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    bool present = false;
-    if (i < n) {
-        sx = src[3 * i], sy = src[3 * i + 1], sz = src[3 * i + 2];
-        present = epc_finite3(sx, sy, sz);
-    }
+    float sx, sy, sz;
+    bool present;
+    ps_corr_row(scans + (size_t)q * n * 3, n, chunk, sx, sy, sz, present);
     const double* __restrict__ m = poses + qh * 12;
     const double r0 = lz_rotate_row(m, sx, sy, sz), r1 = lz_rotate_row(m + 4, sx, sy, sz), r2 = lz_rotate_row(m + 8, sx, sy, sz);
     const float p0 = lz_place(r0, m[3]), p1 = lz_place(r1, m[7]), p2 = lz_place(r2, m[11]);
     float best = INFINITY, c0 = 0.f, c1 = 0.f, c2 = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f;
-    if (chunk * LZ_CHUNK + (tid & ~63) < n) {          // wave-uniform: a wave wholly behind the scan has nothing to look up
+    if (chunk * PS_CHUNK + (tid & ~63) < n) {          // wave-uniform: a wave wholly behind the scan has nothing to look up
         long long k[3] = {0, 0, 0};
         bool any = false;
         if (present) {
@@ -365,93 +332,24 @@ __global__ __launch_bounds__(LZ_CHUNK) void lz_corr_kernel(const float* __restri
         for (int r = 0; r < 6; ++r) v[22 + r] = J[r] * e;
         v[28] = e * e;
     }
-#pragma unroll
-    for (int s = 0; s < LZ_SUMS; ++s) {
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) v[s] += __shfl_xor(v[s], off);
-    }
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int s = 0; s < LZ_SUMS; ++s) part[tid >> 6][s] = v[s];
-    }
-    __syncthreads();
-    if (tid < LZ_SUMS) sums[(qh * gridDim.z + chunk) * LZ_SUMS + tid] = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+    ps_chunk_sums(v, part, sums + (qh * gridDim.z + chunk) * LZ_SUMS);
 }
 
 // ---- the solve -----------------------------------------------------------------------------------------------------------------------------
-// sum s of one pass: the tree over the chunks, an absent chunk the leaf +0.0
-__device__ __forceinline__ double lz_finish_sum(const double* __restrict__ chunk_sums, int chunks, int s) {
-    double v[LZ_MAX_CHUNKS];
-#pragma unroll
-    for (int c = 0; c < LZ_MAX_CHUNKS; ++c) v[c] = c < chunks ? chunk_sums[c * LZ_SUMS + s] : 0.0;
-#pragma unroll
-    for (int w = LZ_MAX_CHUNKS; w > 1; w >>= 1) {
-#pragma unroll
-        for (int c = 0; c < w / 2; ++c) v[c] = v[2 * c] + v[2 * c + 1];
-    }
-    return v[0];
-}
-
-__device__ __forceinline__ double lz_d3(double a0, double a1, double a2, double b0, double b1, double b2) {
-#pragma clang fp contract(off)
-    return (a0 * b0 + a1 * b1) + a2 * b2;
-}
-
 // one Gauss-Newton step from the 29 sums on `pose`; false on a failed pivot or a non-finite word in the new pose
 __device__ __forceinline__ bool lz_step(const double (&S)[LZ_SUMS], double (&pose)[12]) {
 #pragma clang fp contract(off)
-    double Lc[21];                                     // the lower factor, packed by rows: Lc[i (i + 1) / 2 + j]
-    bool ok = true;
-    // H[i][j], i >= j, is sum number 1 + (j (13 - j)) / 2 + (i - j): the upper triangle by rows
+    double Lc[21], r[6], d[6], C[9];
+    bool ok = ps_chol6(&S[1], Lc);                     // H's upper triangle by rows is sums 1 .. 21
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double s = S[1 + j * (13 - j) / 2];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s = s - Lc[j * (j + 1) / 2 + k] * Lc[j * (j + 1) / 2 + k];
-        ok = ok && s > 0.0;
-        const double piv = __dsqrt_rn(s);
-        Lc[j * (j + 1) / 2 + j] = piv;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double t = S[1 + j * (13 - j) / 2 + (i - j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) t = t - Lc[i * (i + 1) / 2 + k] * Lc[j * (j + 1) / 2 + k];
-            Lc[i * (i + 1) / 2 + j] = t / piv;
-        }
-    }
-    double y[6], d[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double s = -S[22 + i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s = s - Lc[i * (i + 1) / 2 + k] * y[k];
-        y[i] = s / Lc[i * (i + 1) / 2 + i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) s = s - Lc[k * (k + 1) / 2 + i] * d[k];
-        d[i] = s / Lc[i * (i + 1) / 2 + i];
-    }
-    const double w = 1.0, x = 0.5 * d[0], yy = 0.5 * d[1], z = 0.5 * d[2];
-    const double nn = ((w * w + x * x) + yy * yy) + z * z;
-    const double u = 2.0 / nn;
-    double C[9];
-    C[0] = 1.0 - u * (yy * yy + z * z);
-    C[1] = u * (x * yy - w * z);
-    C[2] = u * (x * z + w * yy);
-    C[3] = u * (x * yy + w * z);
-    C[4] = 1.0 - u * (x * x + z * z);
-    C[5] = u * (yy * z - w * x);
-    C[6] = u * (x * z - w * yy);
-    C[7] = u * (yy * z + w * x);
-    C[8] = 1.0 - u * (x * x + yy * yy);
+    for (int i = 0; i < 6; ++i) r[i] = -S[22 + i];
+    ps_chol6_solve(Lc, r, d);
+    ps_rotation<3>(1.0, 0.5 * d[0], 0.5 * d[1], 0.5 * d[2], C);
     double next[12];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
-        for (int j = 0; j < 3; ++j) next[4 * i + j] = lz_d3(C[3 * i], C[3 * i + 1], C[3 * i + 2], pose[j], pose[4 + j], pose[8 + j]);
+        for (int j = 0; j < 3; ++j) next[4 * i + j] = ps_d3(C[3 * i], C[3 * i + 1], C[3 * i + 2], pose[j], pose[4 + j], pose[8 + j]);
         next[4 * i + 3] = pose[4 * i + 3] + d[3 + i];
     }
 #pragma unroll
@@ -474,10 +372,10 @@ __global__ __launch_bounds__(64) void lz_solve_kernel(const double* __restrict__
                                                       double* __restrict__ fit_out, double* __restrict__ hessian_out,
                                                       int32_t* __restrict__ info_out, int32_t* __restrict__ status_out) {
     __shared__ double S_s[LZ_SUMS];
-    __shared__ double count_s[LZ_MAX_SEEDS], cost_s[LZ_MAX_SEEDS];
+    __shared__ double count_s[PS_MAX_SEEDS], cost_s[PS_MAX_SEEDS];
     __shared__ int best_s;
     const int q = blockIdx.x, lane = threadIdx.x;
-    int32_t* st = state + (size_t)q * LZ_STATE;
+    int32_t* st = state + (size_t)q * PS_STATE;
     int status = st[0], best = st[1];                  // (uniform over the wave)
     const int rows = st[2];
     __syncthreads();                                   // (lane 0 writes st behind everybody's read)
@@ -487,7 +385,7 @@ __global__ __launch_bounds__(64) void lz_solve_kernel(const double* __restrict__
             const bool ran = lane < pass_seeds && run_a[(size_t)q * pass_seeds + lane] != 0;
             if (ran) {
                 const double* cs = sums + ((size_t)q * pass_seeds + lane) * chunks * LZ_SUMS;
-                count_s[lane] = lz_finish_sum(cs, chunks, 0), cost_s[lane] = lz_finish_sum(cs, chunks, 28);
+                count_s[lane] = ps_finish_sum<LZ_SUMS>(cs, chunks, 0), cost_s[lane] = ps_finish_sum<LZ_SUMS>(cs, chunks, 28);
             }
             __syncthreads();
             if (lane == 0) {
@@ -503,7 +401,7 @@ __global__ __launch_bounds__(64) void lz_solve_kernel(const double* __restrict__
             __syncthreads();
             h = best = best_s;
         }
-        if (lane < LZ_SUMS) S_s[lane] = lz_finish_sum(sums + ((size_t)q * pass_seeds + h) * chunks * LZ_SUMS, chunks, lane);
+        if (lane < LZ_SUMS) S_s[lane] = ps_finish_sum<LZ_SUMS>(sums + ((size_t)q * pass_seeds + h) * chunks * LZ_SUMS, chunks, lane);
     }
     __syncthreads();
     if (lane != 0) return;
@@ -553,21 +451,8 @@ __global__ __launch_bounds__(64) void lz_solve_kernel(const double* __restrict__
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------------
-static inline int lz_chunks(int n) { return (n + LZ_CHUNK - 1) / LZ_CHUNK; }
-static bool lz_shape_ok(int Q, int H, int n) {
-    return Q >= 0 && Q <= LZ_MAX_SCANS && H >= 1 && H <= LZ_MAX_SEEDS && n >= 32 && n <= LZ_MAX_N && n % 32 == 0;
-}
-// the workspace: sums (Q, H, chunks, 29) f64 | cur (Q, 12) f64 | state (Q, 4) i32 | run_a (Q, H) i32 | run_b (Q) i32, each rounded up to 16 bytes
-struct lz_ws { double *sums, *cur; int32_t *state, *run_a, *run_b; size_t bytes; };
-static lz_ws lz_layout(void* base, int Q, int H, int n) {
-    epc_carver c(base);
-    const size_t q = (size_t)Q;
-    return {c.take<double>(q * H * lz_chunks(n) * LZ_SUMS, 16), c.take<double>(q * 12, 16), c.take<int32_t>(q * LZ_STATE, 16),
-            c.take<int32_t>(q * H, 16), c.take<int32_t>(q, 16), c.bytes()};
-}
-
 extern "C" size_t epcnet_scan_localize_workspace_bytes(int Q, int H, int n) {
-    return lz_shape_ok(Q, H, n) ? lz_layout(nullptr, Q, H, n).bytes : 0;
+    return ps_shape_ok(Q, H, n) ? ps_layout<LZ_SUMS>(nullptr, Q, H, n).bytes : 0;
 }
 
 extern "C" int epcnet_scan_localize(const float* scans, int Q, int n, const double* seeds, int H, const void* index, size_t index_bytes,
@@ -576,7 +461,7 @@ extern "C" int epcnet_scan_localize(const float* scans, int Q, int n, const doub
                                     void* stream) {
     EPC_CHECK_ARG(scans && index && centroid && normal && params && pose && fit && hessian && info && status && workspace, "null pointer");
     EPC_CHECK_ARG(epc_aligned16(scans) && epc_aligned16(index), "scans and index must be 16-byte aligned");
-    EPC_CHECK_ARG(lz_shape_ok(Q, H, n), "need n a multiple of 32 in [32, 4096], 0 <= Q <= 2^20, 1 <= H <= 64");
+    EPC_CHECK_ARG(ps_shape_ok(Q, H, n), "need n a multiple of 32 in [32, 4096], 0 <= Q <= 2^20, 1 <= H <= 64");
     EPC_CHECK_ARG(seeds || H == 1, "seeds is NULL: H must be 1 (the identity)");
     EPC_CHECK_ARG(M >= 1 && M <= LZ_MAX_M, "need 1 <= M <= 2^28");
     const double voxel = params[0], max_dist = params[1], iters = params[2], pairs = params[3];
@@ -589,28 +474,20 @@ extern "C" int epcnet_scan_localize(const float* scans, int Q, int n, const doub
     EPC_CHECK_WORKSPACE_BYTES(index_bytes, epcnet_surfel_index_bytes(M));
     EPC_CHECK_WORKSPACE(workspace, workspace_bytes, epcnet_scan_localize_workspace_bytes(Q, H, n));
     const int iterations = (int)iters, min_pairs = (int)pairs;
-    const float g = (float)(max_dist * max_dist);
-    const float gate2 = g < FLT_MAX ? g : FLT_MAX;
-    const int chunks = lz_chunks(n);
+    const float gate2 = ps_gate2(max_dist);
+    const int chunks = ps_chunks(n);
     const lz_index ix = lz_index_layout(const_cast<void*>(index), M).ix;
-    const lz_ws w = lz_layout(workspace, Q, H, n);
+    const ps_ws w = ps_layout<LZ_SUMS>(workspace, Q, H, n);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 solve_grid(Q);
     hipLaunchKernelGGL(lz_prep_kernel, dim3(Q), dim3(LZ_THREADS), 0, st, scans, n, seeds, H, ix.head, M, voxel, w.state, w.run_a, w.cur);
-    // stage A: a pass per seed (under cur, the identity, where there are no seeds), the choice, and the first solve
-    hipLaunchKernelGGL(lz_corr_kernel, dim3(Q, H, chunks), dim3(LZ_CHUNK), 0, st, scans, n, seeds ? seeds : w.cur, w.run_a, ix.table, ix.mask,
-                       voxel, gate2, w.sums);
-    hipLaunchKernelGGL(lz_solve_kernel, solve_grid, dim3(64), 0, st, w.sums, H, chunks, seeds, w.run_a, min_pairs, 1, iterations > 0 ? 1 : 0,
-                       iterations > 0 ? 0 : 1, w.state, w.run_b, w.cur, pose, fit, hessian, info, status);
-    EPC_CHECK_LAUNCH();
-    // stage B's further passes, then the final pass: all under cur
-    for (int it = 1; it <= iterations; ++it) {
-        const int last = it == iterations;
-        hipLaunchKernelGGL(lz_corr_kernel, dim3(Q, 1, chunks), dim3(LZ_CHUNK), 0, st, scans, n, w.cur, w.run_b, ix.table, ix.mask, voxel, gate2,
-                           w.sums);
-        hipLaunchKernelGGL(lz_solve_kernel, solve_grid, dim3(64), 0, st, w.sums, 1, chunks, seeds, w.run_a, min_pairs, 0, last ? 0 : 1, last,
-                           w.state, w.run_b, w.cur, pose, fit, hessian, info, status);
-        EPC_CHECK_LAUNCH();
-    }
-    return EPC_OK;
+    return ps_drive(
+        __func__, seeds, H, iterations, w,
+        [&](int seed_count, const double* poses, const int32_t* run) {
+            hipLaunchKernelGGL(lz_corr_kernel, dim3(Q, seed_count, chunks), dim3(PS_CHUNK), 0, st, scans, n, poses, run, ix.table, ix.mask, voxel,
+                               gate2, w.sums);
+        },
+        [&](int pass_seeds, int select, int solve, int output) {
+            hipLaunchKernelGGL(lz_solve_kernel, dim3(Q), dim3(64), 0, st, w.sums, pass_seeds, chunks, seeds, w.run_a, min_pairs, select, solve,
+                               output, w.state, w.run_b, w.cur, pose, fit, hessian, info, status);
+        });
 }

@@ -6,7 +6,7 @@
 // pairs, seeds and the clouds are device data: every grid is sized from num_pairs, num_seeds and n alone, nothing is read back.
 //   rg_prep_kernel     one workgroup per pair: the indices' range, the rows of both clouds that are not absent, which seeds are finite
 //                      (or the identity where there are none); writes the pair's state and the run flags of stage A
-//   rg_corr_kernel     the hot path, one per pass.  Grid (pair, seed, chunk of RG_CHUNK source rows): the target in LDS as three float
+//   rg_corr_kernel     the hot path, one per pass.  Grid (pair, seed, chunk of PS_CHUNK source rows): the target in LDS as three float
 //                      arrays, +Inf in its absent rows (their d2 is +Inf and never wins: no mask in the loop); every lane keeps one
 //                      transformed source row and reads four targets per wave-uniform 16-byte LDS read; packed float32 sub / mul / add on
 //                      two targets at once (no FMA: the rounding of the definition), a compare and two selects per target; then the
@@ -14,36 +14,25 @@
 //   rg_solve_kernel    one thread per pair: finishes the tree over the chunks; after stage A chooses the seed; solves (Horn, cyclic
 //                      Jacobi) for the next pass's pose; after the final pass writes the four outputs
 // No atomics and no word read that an earlier kernel of the same call has not written: nothing to clear, no memset.
-#include "scan_common.h"
-#include "../../include/epcnet_pairs.h"
+// What this file shares with localize.hip -- the limits, the workspace, the seeds' half of the prep kernel, the correspondence kernel's
+// source row and chunk sums, the tree over the chunks, the host's launch sequence -- and the rotation of a quaternion are
+// pose_common.h's (ps_*).
+#include "pose_common.h"
 
-#include <float.h>
 #include <math.h>
 
-#define RG_CHUNK 256           // source rows per workgroup of the correspondence kernel: one per thread
-#define RG_MAX_N 4096          // the leaves of the summation tree; three float arrays of it are 48 KB of LDS
-#define RG_MAX_CHUNKS (RG_MAX_N / RG_CHUNK)
 #define RG_SUMS 17
 #define RG_SWEEPS 6            // the header's count, fixed on the CPU
-#define RG_MAX_PAIRS (1 << 20)
-#define RG_MAX_SEEDS 64
-#define RG_STATE 4             // int32 per pair: status (0 = still running), best seed, source rows, target rows
 
 typedef float rg_f32x2 __attribute__((ext_vector_type(2)));
-
-static inline int rg_chunks(int n) { return (n + RG_CHUNK - 1) / RG_CHUNK; }
 
 // ---- launch 1: the pairs -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rg_prep_kernel(const float* __restrict__ clouds, int num_clouds, int n, const int32_t* __restrict__ pairs,
                                                       const double* __restrict__ seeds, int num_seeds, int32_t* __restrict__ state,
                                                       int32_t* __restrict__ run_a, double* __restrict__ cur) {
-    __shared__ int part[2][4];
-    __shared__ int any_seed;
     const int p = blockIdx.x, tid = threadIdx.x;
     const int s = pairs[2 * p], t = pairs[2 * p + 1];
     const bool valid = s >= 0 && s < num_clouds && t >= 0 && t < num_clouds;
-    if (tid == 0) any_seed = 0;
-    __syncthreads();
     int ns = 0, nt = 0;
     if (valid) {
         const float* __restrict__ src = clouds + (size_t)s * n * 3;
@@ -53,28 +42,8 @@ __global__ __launch_bounds__(256) void rg_prep_kernel(const float* __restrict__ 
             nt += epc_finite3(tgt[3 * i], tgt[3 * i + 1], tgt[3 * i + 2]) ? 1 : 0;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) ns += __shfl_xor(ns, off), nt += __shfl_xor(nt, off);
-    if ((tid & 63) == 0) part[0][tid >> 6] = ns, part[1][tid >> 6] = nt;
-    if (tid < num_seeds) {
-        bool ok = valid;
-        if (seeds) {
-            const double* __restrict__ m = seeds + ((size_t)p * num_seeds + tid) * 12;
-#pragma unroll
-            for (int c = 0; c < 12; ++c) ok = ok && __builtin_isfinite(m[c]);
-        }
-        run_a[(size_t)p * num_seeds + tid] = ok ? 1 : 0;
-        if (ok) any_seed = 1;                          // every writer writes the same value
-    }
-    if (!seeds && tid < 12) cur[(size_t)p * 12 + tid] = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
-    __syncthreads();
-    if (tid == 0) {
-        int32_t* st = state + (size_t)p * RG_STATE;
-        st[0] = any_seed ? 0 : EPC_STATUS_NO_PAIR;
-        st[1] = -1;
-        st[2] = (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
-        st[3] = (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
-    }
+    int rows[2] = {ns, nt};
+    ps_prep_item(p, valid, rows, seeds, num_seeds, state, run_a, cur);
 }
 
 // ---- the correspondence pass -------------------------------------------------------------------------------------------------------------
@@ -95,31 +64,27 @@ __device__ __forceinline__ void rg_two_targets(rg_f32x2 px, rg_f32x2 py, rg_f32x
 }
 
 // poses (num_pairs, num_seeds, 12); run (num_pairs, num_seeds): 0 = this pass is not wanted, nothing is written; sums (num_pairs, num_seeds,
-// chunks, 17).  Grid (num_pairs, num_seeds, chunks).
-__global__ __launch_bounds__(RG_CHUNK) void rg_corr_kernel(const float* __restrict__ clouds, int n, const int32_t* __restrict__ pairs,
+// chunks, 17).  Grid (num_pairs, num_seeds, chunks), a chunk PS_CHUNK source rows.
+__global__ __launch_bounds__(PS_CHUNK) void rg_corr_kernel(const float* __restrict__ clouds, int n, const int32_t* __restrict__ pairs,
                                                            const double* __restrict__ poses, const int32_t* __restrict__ run, float gate2,
                                                            double* __restrict__ sums) {
-    __shared__ __attribute__((aligned(16))) float lx[RG_MAX_N];
-    __shared__ __attribute__((aligned(16))) float ly[RG_MAX_N];
-    __shared__ __attribute__((aligned(16))) float lz[RG_MAX_N];
-    __shared__ double part[RG_CHUNK / 64][RG_SUMS];
+    __shared__ __attribute__((aligned(16))) float lx[PS_MAX_N];       // (three float arrays of the tree's leaves: 48 KB of LDS)
+    __shared__ __attribute__((aligned(16))) float ly[PS_MAX_N];
+    __shared__ __attribute__((aligned(16))) float lz[PS_MAX_N];
+    __shared__ double part[PS_CHUNK / 64][RG_SUMS];
     const int p = blockIdx.x, h = blockIdx.y, chunk = blockIdx.z, tid = threadIdx.x;
     const size_t ph = (size_t)p * gridDim.y + h;
     if (!run[ph]) return;                              // (a run flag is only set for a pair whose indices are inside)
     const float* __restrict__ src = clouds + (size_t)pairs[2 * p] * n * 3;
     const float* __restrict__ tgt = clouds + (size_t)pairs[2 * p + 1] * n * 3;
-    for (int j = tid; j < n; j += RG_CHUNK) {
+    for (int j = tid; j < n; j += PS_CHUNK) {
         float x = tgt[3 * j], y = tgt[3 * j + 1], z = tgt[3 * j + 2];
         if (!epc_finite3(x, y, z)) x = y = z = INFINITY;
         lx[j] = x, ly[j] = y, lz[j] = z;
     }
-    const int i = chunk * RG_CHUNK + tid;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    bool present = false;
-    if (i < n) {
-        sx = src[3 * i], sy = src[3 * i + 1], sz = src[3 * i + 2];
-        present = epc_finite3(sx, sy, sz);
-    }
+    float sx, sy, sz;
+    bool present;
+    ps_corr_row(src, n, chunk, sx, sy, sz, present);
     const double* __restrict__ m = poses + ph * 12;
     const float nan = epc_nan_f32();
     const float px = present ? rg_transform_row(m, sx, sy, sz) : nan;
@@ -128,7 +93,7 @@ __global__ __launch_bounds__(RG_CHUNK) void rg_corr_kernel(const float* __restri
     __syncthreads();
     float best = INFINITY;
     int bj = 0;
-    if (chunk * RG_CHUNK + (tid & ~63) < n) {          // wave-uniform: a wave wholly behind the cloud has nothing to search
+    if (chunk * PS_CHUNK + (tid & ~63) < n) {          // wave-uniform: a wave wholly behind the cloud has nothing to search
         const rg_f32x2 vx = {px, px}, vy = {py, py}, vz = {pz, pz};
         const float4* __restrict__ lx4 = reinterpret_cast<const float4*>(lx);
         const float4* __restrict__ ly4 = reinterpret_cast<const float4*>(ly);
@@ -154,33 +119,10 @@ __global__ __launch_bounds__(RG_CHUNK) void rg_corr_kernel(const float* __restri
         v[13] = s2 * q0, v[14] = s2 * q1, v[15] = s2 * q2;
         v[16] = acc ? (double)best : 0.0;
     }
-#pragma unroll
-    for (int k = 0; k < RG_SUMS; ++k) {
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) v[k] += __shfl_xor(v[k], off);
-    }
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < RG_SUMS; ++k) part[tid >> 6][k] = v[k];
-    }
-    __syncthreads();
-    if (tid < RG_SUMS) sums[(ph * gridDim.z + chunk) * RG_SUMS + tid] = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+    ps_chunk_sums(v, part, sums + (ph * gridDim.z + chunk) * RG_SUMS);
 }
 
 // ---- the solve -----------------------------------------------------------------------------------------------------------------------------
-// sum k of one pass: the tree over the chunks, an absent chunk the leaf +0.0
-__device__ __forceinline__ double rg_finish_sum(const double* __restrict__ chunk_sums, int chunks, int k) {
-    double v[RG_MAX_CHUNKS];
-#pragma unroll
-    for (int c = 0; c < RG_MAX_CHUNKS; ++c) v[c] = c < chunks ? chunk_sums[c * RG_SUMS + k] : 0.0;
-#pragma unroll
-    for (int w = RG_MAX_CHUNKS; w > 1; w >>= 1) {
-#pragma unroll
-        for (int c = 0; c < w / 2; ++c) v[c] = v[2 * c] + v[2 * c + 1];
-    }
-    return v[0];
-}
-
 // one Jacobi rotation of the pair (P, Q) on the symmetric a, accumulated into the eigenvectors e
 template <int P, int Q>
 __device__ __forceinline__ void rg_rotate(double (&a)[4][4], double (&e)[4][4]) {
@@ -251,17 +193,7 @@ __device__ __forceinline__ bool rg_solve(const double (&S)[RG_SUMS], double (&po
     for (int k = 1; k < 4; ++k) {
         if (a[k][k] > top) top = a[k][k], w = e[0][k], x = e[1][k], y = e[2][k], z = e[3][k];
     }
-    const double nn = ((w * w + x * x) + y * y) + z * z;
-    const double u = 2.0 / nn;
-    pose[0] = 1.0 - u * (y * y + z * z);
-    pose[1] = u * (x * y - w * z);
-    pose[2] = u * (x * z + w * y);
-    pose[4] = u * (x * y + w * z);
-    pose[5] = 1.0 - u * (x * x + z * z);
-    pose[6] = u * (y * z - w * x);
-    pose[8] = u * (x * z - w * y);
-    pose[9] = u * (y * z + w * x);
-    pose[10] = 1.0 - u * (x * x + y * y);
+    ps_rotation<4>(w, x, y, z, pose);
     const double sm0 = S[1] / m, sm1 = S[2] / m, sm2 = S[3] / m;
     bool ok = true;
 #pragma unroll
@@ -285,7 +217,7 @@ __global__ __launch_bounds__(64) void rg_solve_kernel(const double* __restrict__
                                                       int32_t* __restrict__ status_out) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= num_pairs) return;
-    int32_t* st = state + (size_t)p * RG_STATE;
+    int32_t* st = state + (size_t)p * PS_STATE;
     int status = st[0], best = st[1];
     double S[RG_SUMS], pose[12];
     double* mine = cur + (size_t)p * 12;
@@ -297,7 +229,7 @@ __global__ __launch_bounds__(64) void rg_solve_kernel(const double* __restrict__
             for (int k = 0; k < pass_seeds; ++k) {
                 if (!run_a[(size_t)p * pass_seeds + k]) continue;
                 const double* cs = sums + ((size_t)p * pass_seeds + k) * chunks * RG_SUMS;
-                const double c = rg_finish_sum(cs, chunks, 0), d = rg_finish_sum(cs, chunks, 16);
+                const double c = ps_finish_sum<RG_SUMS>(cs, chunks, 0), d = ps_finish_sum<RG_SUMS>(cs, chunks, 16);
                 if (best < 0 || c > bc || (c == bc && d < bd)) best = k, bc = c, bd = d;
             }
             h = best;                                  // >= 0: status 0 says that a seed ran
@@ -309,7 +241,7 @@ __global__ __launch_bounds__(64) void rg_solve_kernel(const double* __restrict__
         }
         const double* cs = sums + ((size_t)p * pass_seeds + h) * chunks * RG_SUMS;
 #pragma unroll
-        for (int k = 0; k < RG_SUMS; ++k) S[k] = rg_finish_sum(cs, chunks, k);
+        for (int k = 0; k < RG_SUMS; ++k) S[k] = ps_finish_sum<RG_SUMS>(cs, chunks, k);
         if (S[0] < (double)min_pairs) {
             status = EPC_STATUS_NO_FIT;
         } else if (solve) {
@@ -340,21 +272,8 @@ __global__ __launch_bounds__(64) void rg_solve_kernel(const double* __restrict__
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------------
-static bool rg_shape_ok(int num_pairs, int num_seeds, int n) {
-    return num_pairs >= 0 && num_pairs <= RG_MAX_PAIRS && num_seeds >= 1 && num_seeds <= RG_MAX_SEEDS && n >= 32 && n <= RG_MAX_N &&
-           n % 32 == 0;
-}
-// the workspace: sums (P, H, chunks, 17) f64 | cur (P, 12) f64 | state (P, 4) i32 | run_a (P, H) i32 | run_b (P) i32, each rounded up to 16 bytes
-struct rg_ws { double *sums, *cur; int32_t *state, *run_a, *run_b; size_t bytes; };
-static rg_ws rg_layout(void* base, int num_pairs, int num_seeds, int n) {
-    epc_carver c(base);
-    const size_t P = (size_t)num_pairs;
-    return {c.take<double>(P * num_seeds * rg_chunks(n) * RG_SUMS, 16), c.take<double>(P * 12, 16), c.take<int32_t>(P * RG_STATE, 16),
-            c.take<int32_t>(P * num_seeds, 16), c.take<int32_t>(P, 16), c.bytes()};
-}
-
 extern "C" size_t epcnet_pair_register_workspace_bytes(int num_pairs, int num_seeds, int n) {
-    return rg_shape_ok(num_pairs, num_seeds, n) ? rg_layout(nullptr, num_pairs, num_seeds, n).bytes : 0;
+    return ps_shape_ok(num_pairs, num_seeds, n) ? ps_layout<RG_SUMS>(nullptr, num_pairs, num_seeds, n).bytes : 0;
 }
 
 extern "C" int epcnet_pair_register(const float* clouds, int num_clouds, int n, const int32_t* pairs, int num_pairs, const double* seeds,
@@ -362,7 +281,7 @@ extern "C" int epcnet_pair_register(const float* clouds, int num_clouds, int n, 
                                     int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     EPC_CHECK_ARG(clouds && pairs && pose && fit && info && status && workspace, "null pointer");
     EPC_CHECK_ARG(epc_aligned16(clouds), "clouds must be 16-byte aligned");
-    EPC_CHECK_ARG(rg_shape_ok(num_pairs, num_seeds, n) && num_clouds >= 1,
+    EPC_CHECK_ARG(ps_shape_ok(num_pairs, num_seeds, n) && num_clouds >= 1,
                   "need n a multiple of 32 in [32, 4096], num_clouds >= 1, 0 <= num_pairs <= 2^20, 1 <= num_seeds <= 64");
     EPC_CHECK_ARG(seeds || num_seeds == 1, "seeds is NULL: num_seeds must be 1 (the identity)");
     EPC_CHECK_ARG(isfinite(max_dist) && max_dist > 0.0, "max_dist must be finite and > 0");
@@ -370,26 +289,19 @@ extern "C" int epcnet_pair_register(const float* clouds, int num_clouds, int n, 
     EPC_CHECK_ARG(min_pairs >= 3 && min_pairs <= n, "need 3 <= min_pairs <= n");
     if (num_pairs == 0) return EPC_OK;
     EPC_CHECK_WORKSPACE(workspace, workspace_bytes, epcnet_pair_register_workspace_bytes(num_pairs, num_seeds, n));
-    const float g = (float)(max_dist * max_dist);
-    const float gate2 = g < FLT_MAX ? g : FLT_MAX;
-    const int chunks = rg_chunks(n);
-    const rg_ws w = rg_layout(workspace, num_pairs, num_seeds, n);
+    const float gate2 = ps_gate2(max_dist);
+    const int chunks = ps_chunks(n);
+    const ps_ws w = ps_layout<RG_SUMS>(workspace, num_pairs, num_seeds, n);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 solve_grid((num_pairs + 63) / 64);
     hipLaunchKernelGGL(rg_prep_kernel, dim3(num_pairs), dim3(256), 0, st, clouds, num_clouds, n, pairs, seeds, num_seeds, w.state, w.run_a, w.cur);
-    // stage A: a pass per seed (under cur, the identity, where there are no seeds), the choice, and the first solve
-    hipLaunchKernelGGL(rg_corr_kernel, dim3(num_pairs, num_seeds, chunks), dim3(RG_CHUNK), 0, st, clouds, n, pairs, seeds ? seeds : w.cur, w.run_a,
-                       gate2, w.sums);
-    hipLaunchKernelGGL(rg_solve_kernel, solve_grid, dim3(64), 0, st, w.sums, num_pairs, num_seeds, chunks, seeds, w.run_a, min_pairs, 1,
-                       iterations > 0 ? 1 : 0, iterations > 0 ? 0 : 1, w.state, w.run_b, w.cur, pose, fit, info, status);
-    EPC_CHECK_LAUNCH();
-    // stage B's further passes, then the final pass: all under cur
-    for (int it = 1; it <= iterations; ++it) {
-        const int last = it == iterations;
-        hipLaunchKernelGGL(rg_corr_kernel, dim3(num_pairs, 1, chunks), dim3(RG_CHUNK), 0, st, clouds, n, pairs, w.cur, w.run_b, gate2, w.sums);
-        hipLaunchKernelGGL(rg_solve_kernel, solve_grid, dim3(64), 0, st, w.sums, num_pairs, 1, chunks, seeds, w.run_a, min_pairs, 0, last ? 0 : 1,
-                           last, w.state, w.run_b, w.cur, pose, fit, info, status);
-        EPC_CHECK_LAUNCH();
-    }
-    return EPC_OK;
+    return ps_drive(
+        __func__, seeds, num_seeds, iterations, w,
+        [&](int seed_count, const double* poses, const int32_t* run) {
+            hipLaunchKernelGGL(rg_corr_kernel, dim3(num_pairs, seed_count, chunks), dim3(PS_CHUNK), 0, st, clouds, n, pairs, poses, run, gate2,
+                               w.sums);
+        },
+        [&](int pass_seeds, int select, int solve, int output) {
+            hipLaunchKernelGGL(rg_solve_kernel, dim3((num_pairs + 63) / 64), dim3(64), 0, st, w.sums, num_pairs, pass_seeds, chunks, seeds, w.run_a,
+                               min_pairs, select, solve, output, w.state, w.run_b, w.cur, pose, fit, info, status);
+        });
 }

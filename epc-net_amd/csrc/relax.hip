@@ -15,7 +15,9 @@
 //   step      rx_scan_kernel on x, rx_retract_kernel
 //   rx_finish_kernel writes poses_out, and everything where nothing was solved
 // No atomics, no flag one workgroup waits on, no grid barrier, no word read that an earlier kernel of the same call has not written.
-#include "scan_common.h"
+// The three-term dot, the 6 x 6 Cholesky, its substitutions and the rotation of a quaternion are pose_common.h's (ps_*), shared with
+// localize.hip and register.hip.
+#include "pose_common.h"
 #include "../../include/epcnet_trajectory.h"
 
 #include <math.h>
@@ -33,11 +35,6 @@ enum { RX_TE = 0, RX_ACTIVE = 1, RX_FAIL = 2, RX_USED = 3, RX_FLAGS = 4 };
 static inline int rx_blocks(int n) { return (n + RX_BLOCK - 1) / RX_BLOCK; }
 
 // ---- the arithmetic of the definition ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double rx_d3(double a0, double a1, double a2, double b0, double b1, double b2) {
-#pragma clang fp contract(off)
-    return (a0 * b0 + a1 * b1) + a2 * b2;
-}
-
 // An edge (a, b, Z, w_t, w_r) at the state (Ra, ca), (Rb, cb); R row-major 3 x 3, Z row-major [Z_R | z_t] 3 x 4.
 // J = [[A, B], [0, C]] as J[0..9) = A, J[9..18) = B, J[18..27) = C row-major; b = J^T W r; returns the edge's cost.
 __device__ __forceinline__ double rx_linearise(const double (&Ra)[9], const double (&Rb)[9], const double (&ca)[3], const double (&cb)[3],
@@ -47,16 +44,16 @@ __device__ __forceinline__ double rx_linearise(const double (&Ra)[9], const doub
 #pragma unroll
     for (int i = 0; i < 3; ++i) dc[i] = cb[i] - ca[i];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) rt[i] = rx_d3(Ra[i], Ra[3 + i], Ra[6 + i], dc[0], dc[1], dc[2]) - Z[4 * i + 3];
+    for (int i = 0; i < 3; ++i) rt[i] = ps_d3(Ra[i], Ra[3 + i], Ra[6 + i], dc[0], dc[1], dc[2]) - Z[4 * i + 3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
-        for (int j = 0; j < 3; ++j) M[3 * i + j] = rx_d3(Ra[i], Ra[3 + i], Ra[6 + i], Rb[j], Rb[3 + j], Rb[6 + j]);
+        for (int j = 0; j < 3; ++j) M[3 * i + j] = ps_d3(Ra[i], Ra[3 + i], Ra[6 + i], Rb[j], Rb[3 + j], Rb[6 + j]);
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
-        for (int j = 0; j < 3; ++j) E[3 * i + j] = rx_d3(Z[i], Z[4 + i], Z[8 + i], M[j], M[3 + j], M[6 + j]);
+        for (int j = 0; j < 3; ++j) E[3 * i + j] = ps_d3(Z[i], Z[4 + i], Z[8 + i], M[j], M[3 + j], M[6 + j]);
     }
     rR[0] = 0.5 * (E[7] - E[5]);
     rR[1] = 0.5 * (E[2] - E[6]);
@@ -83,14 +80,14 @@ __device__ __forceinline__ double rx_linearise(const double (&Ra)[9], const doub
 #pragma unroll
     for (int i = 0; i < 3; ++i) {                                                     // C = 1/2 G Rb^T
 #pragma unroll
-        for (int j = 0; j < 3; ++j) J[18 + 3 * i + j] = 0.5 * rx_d3(G[3 * i], G[3 * i + 1], G[3 * i + 2], Rb[3 * j], Rb[3 * j + 1], Rb[3 * j + 2]);
+        for (int j = 0; j < 3; ++j) J[18 + 3 * i + j] = 0.5 * ps_d3(G[3 * i], G[3 * i + 1], G[3 * i + 2], Rb[3 * j], Rb[3 * j + 1], Rb[3 * j + 2]);
     }
     const double t0 = wt * rt[0], t1 = wt * rt[1], t2 = wt * rt[2];
     const double r0 = wr * rR[0], r1 = wr * rR[1], r2 = wr * rR[2];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        b[j] = rx_d3(J[j], J[3 + j], J[6 + j], t0, t1, t2);
-        b[3 + j] = rx_d3(J[9 + j], J[12 + j], J[15 + j], t0, t1, t2) + rx_d3(J[18 + j], J[21 + j], J[24 + j], r0, r1, r2);
+        b[j] = ps_d3(J[j], J[3 + j], J[6 + j], t0, t1, t2);
+        b[3 + j] = ps_d3(J[9 + j], J[12 + j], J[15 + j], t0, t1, t2) + ps_d3(J[18 + j], J[21 + j], J[24 + j], r0, r1, r2);
     }
     return wt * ((rt[0] * rt[0] + rt[1] * rt[1]) + rt[2] * rt[2]) + wr * ((rR[0] * rR[0] + rR[1] * rR[1]) + rR[2] * rR[2]);
 }
@@ -101,20 +98,20 @@ __device__ __forceinline__ void rx_apply(const double (&J)[27], double wt, doubl
     double yt[3], yr[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        yt[i] = wt * (rx_d3(J[3 * i], J[3 * i + 1], J[3 * i + 2], d[0], d[1], d[2]) + rx_d3(J[9 + 3 * i], J[9 + 3 * i + 1], J[9 + 3 * i + 2], d[3], d[4], d[5]));
-        yr[i] = wr * rx_d3(J[18 + 3 * i], J[18 + 3 * i + 1], J[18 + 3 * i + 2], d[3], d[4], d[5]);
+        yt[i] = wt * (ps_d3(J[3 * i], J[3 * i + 1], J[3 * i + 2], d[0], d[1], d[2]) + ps_d3(J[9 + 3 * i], J[9 + 3 * i + 1], J[9 + 3 * i + 2], d[3], d[4], d[5]));
+        yr[i] = wr * ps_d3(J[18 + 3 * i], J[18 + 3 * i + 1], J[18 + 3 * i + 2], d[3], d[4], d[5]);
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        u[j] = rx_d3(J[j], J[3 + j], J[6 + j], yt[0], yt[1], yt[2]);
-        u[3 + j] = rx_d3(J[9 + j], J[12 + j], J[15 + j], yt[0], yt[1], yt[2]) + rx_d3(J[18 + j], J[21 + j], J[24 + j], yr[0], yr[1], yr[2]);
+        u[j] = ps_d3(J[j], J[3 + j], J[6 + j], yt[0], yt[1], yt[2]);
+        u[3 + j] = ps_d3(J[9 + j], J[12 + j], J[15 + j], yt[0], yt[1], yt[2]) + ps_d3(J[18 + j], J[21 + j], J[24 + j], yr[0], yr[1], yr[2]);
     }
 }
 
 // The lower Cholesky factor of D = J^T W J, packed by rows (Lc[i (i + 1) / 2 + j]); false where a pivot is not > 0.
 __device__ __forceinline__ bool rx_factor(const double (&J)[27], double wt, double wr, double (&Lc)[21]) {
 #pragma clang fp contract(off)
-    double D[6][6];
+    double U[21];                                      // D's upper triangle by rows
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
 #pragma unroll
@@ -122,53 +119,16 @@ __device__ __forceinline__ bool rx_factor(const double (&J)[27], double wt, doub
             double v;
             if (i < 3) {
                 const int o = j < 3 ? j : 9 + (j - 3);
-                v = wt * rx_d3(J[i], J[3 + i], J[6 + i], J[o], J[o + 3], J[o + 6]);
+                v = wt * ps_d3(J[i], J[3 + i], J[6 + i], J[o], J[o + 3], J[o + 6]);
             } else {
                 const int bi = 9 + (i - 3), bj = 9 + (j - 3), ci = 18 + (i - 3), cj = 18 + (j - 3);
-                v = wt * rx_d3(J[bi], J[bi + 3], J[bi + 6], J[bj], J[bj + 3], J[bj + 6]) +
-                    wr * rx_d3(J[ci], J[ci + 3], J[ci + 6], J[cj], J[cj + 3], J[cj + 6]);
+                v = wt * ps_d3(J[bi], J[bi + 3], J[bi + 6], J[bj], J[bj + 3], J[bj + 6]) +
+                    wr * ps_d3(J[ci], J[ci + 3], J[ci + 6], J[cj], J[cj + 3], J[cj + 6]);
             }
-            D[i][j] = D[j][i] = v;
+            U[i * (13 - i) / 2 + (j - i)] = v;
         }
     }
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double s = D[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s = s - Lc[j * (j + 1) / 2 + k] * Lc[j * (j + 1) / 2 + k];
-        ok = ok && s > 0.0;
-        const double piv = __dsqrt_rn(s);
-        Lc[j * (j + 1) / 2 + j] = piv;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double q = D[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) q = q - Lc[i * (i + 1) / 2 + k] * Lc[j * (j + 1) / 2 + k];
-            Lc[i * (i + 1) / 2 + j] = q / piv;
-        }
-    }
-    return ok;
-}
-
-// z = D^-1 r from the factor
-__device__ __forceinline__ void rx_solve(const double (&Lc)[21], const double (&r)[6], double (&z)[6]) {
-#pragma clang fp contract(off)
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double s = r[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s = s - Lc[i * (i + 1) / 2 + k] * y[k];
-        y[i] = s / Lc[i * (i + 1) / 2 + i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) s = s - Lc[k * (k + 1) / 2 + i] * z[k];
-        z[i] = s / Lc[i * (i + 1) / 2 + i];
-    }
+    return ps_chol6(U, Lc);
 }
 
 __device__ __forceinline__ double rx_leaf(const double (&x)[6], const double (&y)[6]) {
@@ -179,25 +139,13 @@ __device__ __forceinline__ double rx_leaf(const double (&x)[6], const double (&y
 // R <- C(w) R, c <- C(w) c + rho
 __device__ __forceinline__ void rx_retract(const double (&eta)[6], double (&R)[9], double (&c)[3]) {
 #pragma clang fp contract(off)
-    const double w = 1.0, x = 0.5 * eta[3], y = 0.5 * eta[4], z = 0.5 * eta[5];
-    const double nn = ((w * w + x * x) + y * y) + z * z;
-    const double u = 2.0 / nn;
-    double C[9];
-    C[0] = 1.0 - u * (y * y + z * z);
-    C[1] = u * (x * y - w * z);
-    C[2] = u * (x * z + w * y);
-    C[3] = u * (x * y + w * z);
-    C[4] = 1.0 - u * (x * x + z * z);
-    C[5] = u * (y * z - w * x);
-    C[6] = u * (x * z - w * y);
-    C[7] = u * (y * z + w * x);
-    C[8] = 1.0 - u * (x * x + y * y);
-    double Rn[9], cn[3];
+    double C[9], Rn[9], cn[3];
+    ps_rotation<3>(1.0, 0.5 * eta[3], 0.5 * eta[4], 0.5 * eta[5], C);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
-        for (int j = 0; j < 3; ++j) Rn[3 * i + j] = rx_d3(C[3 * i], C[3 * i + 1], C[3 * i + 2], R[j], R[3 + j], R[6 + j]);
-        cn[i] = rx_d3(C[3 * i], C[3 * i + 1], C[3 * i + 2], c[0], c[1], c[2]) + eta[i];
+        for (int j = 0; j < 3; ++j) Rn[3 * i + j] = ps_d3(C[3 * i], C[3 * i + 1], C[3 * i + 2], R[j], R[3 + j], R[6 + j]);
+        cn[i] = ps_d3(C[3 * i], C[3 * i + 1], C[3 * i + 2], c[0], c[1], c[2]) + eta[i];
     }
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = Rn[k];
@@ -384,8 +332,8 @@ __global__ __launch_bounds__(RX_BLOCK) void rx_fill_kernel(const double* __restr
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
-        for (int j = 0; j < 3; ++j) Zn[4 * i + j] = rx_d3(Ra[i], Ra[3 + i], Ra[6 + i], Rb[j], Rb[3 + j], Rb[6 + j]);
-        Zn[4 * i + 3] = rx_d3(Ra[i], Ra[3 + i], Ra[6 + i], dc[0], dc[1], dc[2]);
+        for (int j = 0; j < 3; ++j) Zn[4 * i + j] = ps_d3(Ra[i], Ra[3 + i], Ra[6 + i], Rb[j], Rb[3 + j], Rb[6 + j]);
+        Zn[4 * i + 3] = ps_d3(Ra[i], Ra[3 + i], Ra[6 + i], dc[0], dc[1], dc[2]);
     }
     rx_store<12>(Zn, Z, n, T);
 }
@@ -569,7 +517,7 @@ __global__ __launch_bounds__(RX_BLOCK) void rx_start_kernel(const double* __rest
         rx_load<21>(Lc, cL, n, T);
 #pragma unroll
         for (int k = 0; k < 6; ++k) rn[k] = -(RX_AT(cb, k, n, T) + (before[k] + RX_AT(sg, k, n, T)));
-        rx_solve(Lc, rn, zn);
+        ps_chol6_solve(Lc, rn, zn);
     }
     if (n < T) {
         const double zero[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -653,7 +601,7 @@ __global__ __launch_bounds__(RX_BLOCK) void rx_update_kernel(int T, const int32_
         if (n >= 1) {
             double Lc[21];
             rx_load<21>(Lc, cL, n, T);
-            rx_solve(Lc, rn, zn);
+            ps_chol6_solve(Lc, rn, zn);
         }
         rx_store<6>(xn, x, n, T);
         rx_store<6>(rn, r, n, T);
