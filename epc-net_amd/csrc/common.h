@@ -198,22 +198,25 @@ int epc_partial_sum_wide_launch(const float* partials, int P, int E, float* out,
 int epc_sort_launch(const float* xyz, int num_clouds, int n, float* xyz_sorted, int32_t* perm, int32_t* status_zero,
                     void* stream);
 
-#define EPC_CHECK_ARG(cond, msg)                                  \
+// the refusals of an entry: under its own name, or (_AS) under the name `who` of the entry that a shared host function serves
+#define EPC_CHECK_ARG_AS(who, cond, msg)                          \
     do {                                                          \
         if (!(cond)) {                                            \
-            epc_set_error("%s: %s", __func__, msg);               \
+            epc_set_error("%s: %s", who, msg);                    \
             return EPC_EINVAL;                                    \
         }                                                         \
     } while (0)
+#define EPC_CHECK_ARG(cond, msg) EPC_CHECK_ARG_AS(__func__, cond, msg)
 
-#define EPC_CHECK_LAUNCH()                                                        \
+#define EPC_CHECK_LAUNCH_AS(who)                                                  \
     do {                                                                          \
         hipError_t e__ = hipGetLastError();                                       \
         if (e__ != hipSuccess) {                                                  \
-            epc_set_error("%s: launch failed: %s", __func__, hipGetErrorString(e__)); \
+            epc_set_error("%s: launch failed: %s", who, hipGetErrorString(e__));  \
             return EPC_EHIP;                                                      \
         }                                                                         \
     } while (0)
+#define EPC_CHECK_LAUNCH() EPC_CHECK_LAUNCH_AS(__func__)
 
 // ---- host helpers that serve every launcher of the library ------------------------------------------------
 static inline bool epc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

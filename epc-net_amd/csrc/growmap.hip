@@ -1,10 +1,10 @@
 // The surfel map that grows across calls (include/epcnet_growmap.h: epcnet_surfel_map_init, epcnet_surfel_map_add; numpy restatement in
-// tests/growmap_ref.py).  The definition is epcnet_map_surfels' on the concatenation of the calls' clouds, and so is the code: the slot, a
-// tile's rows, the claim loop, the sixteen-lane adds, the lookup and the pool-and-solve are surfel_common.h's, here on a table that
-// persists in the caller's state.  What an add has to do beyond the sums follows from three facts: a voxel's number is its first source
-// row's rank, so numbers handed out never move; the sums are integers, free of how rows were split over calls; a surfel depends on the
-// cells within `ring` of its voxel only.  So a call numbers the slots it claimed behind the V it found, and solves again the voxels within
-// `ring` of a slot that received a row -- the DIRTY ones -- and no other.
+// tests/growmap_ref.py).  The definition is epcnet_map_surfels' on the concatenation of the calls' clouds, and so is the code: the claim
+// loop, the lookup and the scan's levels are map_common.h's, the slot, a tile's rows, the sixteen-lane adds and the pool-and-solve
+// surfel_common.h's, here on a table that persists in the caller's state.  What an add has to do beyond the sums follows from three
+// facts: a voxel's number is its first source row's rank, so numbers handed out never move; the sums are integers, free of how rows were
+// split over calls; a surfel depends on the cells within `ring` of its voxel only.  So a call numbers the slots it claimed behind the V
+// it found, and solves again the voxels within `ring` of a slot that received a row -- the DIRTY ones -- and no other.
 //
 // The state: a head (gm_head, 256 bytes) | the table (mp_cap(max_voxels) slots of 128 bytes).  A slot's last two words carry its leader (a
 // row of the call that claimed it), its number + 1 (0: not numbered yet) and two epochs: the call in which it last received a row, the call
@@ -22,7 +22,7 @@
 //                           its slot (out of range: skipped, never wrapped) and exchanges the epoch into `dirty` of each that is a voxel;
 //                           whoever flips one appends the slot to the dirty list through an integer counter.  The list's order varies
 //                           from run to run; the outputs are written by voxel number, so it does not reach them
-//   growmap_group_kernel, growmap_top_kernel     the scan's upper levels (surfel_common.h); V, num_out, num_call, the epoch's increment,
+//   growmap_group_kernel, growmap_top_kernel     the scan's upper levels (map_common.h); V, num_out, num_call, the epoch's increment,
 //                           and whether this call has to fill the outputs after an overflow (the first such call does, once)
 //   growmap_number_kernel   tiles over the rows: every leader writes V_before + its rank + 1 into its slot
 //   growmap_emit_kernel     lanes over the dirty list, the grid sized from min(num_rows (2 ring + 1)^3, max_voxels); lanes behind the
@@ -115,10 +115,7 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_init_kernel(const double* 
                                                                   int32_t* __restrict__ num_out) {
     const unsigned long long stride = (unsigned long long)gridDim.x * MP_THREADS;
     const unsigned long long first = (unsigned long long)blockIdx.x * MP_THREADS + threadIdx.x;
-    // sixteen lanes per slot, one word each: a wave-instruction stores four whole slots
-    const unsigned long long words = (st.mask + 1) * 16;
-    unsigned long long* const base = reinterpret_cast<unsigned long long*>(st.table);
-    for (unsigned long long i = first; i < words; i += stride) base[i] = sf_cleared_word((unsigned)(i & 15));
+    sf_clear_table(st.table, st.mask, first, stride);
     for (unsigned long long j = first; j < (unsigned long long)max_voxels; j += stride)
         sf_write_none((long long)j, map_points, count, centroid, normal, eigen, support);
     if (first < 4) num_out[first] = 0;
@@ -148,6 +145,19 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_check_kernel(const int32_t
 }
 
 // ---- launch 3: the rows ----------------------------------------------------------------------------------------------------------------
+// the epoch into a slot's `touched` -> this row is the slot's first of the call
+__device__ __forceinline__ bool gm_touch(uint32_t* touched, uint32_t epoch) {
+    return __atomic_load_n(touched, __ATOMIC_RELAXED) != epoch && atomicExch(touched, epoch) != epoch;
+}
+// row r enters slot t: its position for the tile's adds; its claim to lead, unless the slot has a number (claimed in an earlier call: it
+// keeps its number, whatever its stale leader says); the epoch -> won
+__device__ __forceinline__ bool gm_enter(sf_tile_lds& lds, int tid, sf_slot* table, int slot, long long r, const long long* w, uint32_t epoch) {
+    sf_stage_pos(lds, tid, w);
+    sf_slot* t = table + slot;
+    if (mp_load(&t->number) == 0) sf_lead(t, r);
+    return gm_touch(&t->touched, epoch);
+}
+
 __global__ __launch_bounds__(MP_THREADS) void growmap_insert_kernel(const float* __restrict__ points, const int32_t* __restrict__ offsets,
                                                                     long long num_rows, int num_clouds, const double* __restrict__ poses,
                                                                     sf_params pr, long long max_voxels, gm_state st, gm_ws ws) {
@@ -161,17 +171,8 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_insert_kernel(const float*
     int slot = -kind;                                  // -1 absent, -2 out of range, -4 no row of any cloud
     bool won = false;
     if (kind == 0) {
-        slot = sf_claim(st.table, st.mask, mp_key(w[0] >> 12, w[1] >> 12, w[2] >> 12), &st.head->claimed, max_voxels);      // -3: gave up
-        if (slot >= 0) {
-            lds.pos[tid][0] = (unsigned short)(w[0] & 4095), lds.pos[tid][1] = (unsigned short)(w[1] & 4095);
-            lds.pos[tid][2] = (unsigned short)(w[2] & 4095);
-            sf_slot* t = st.table + slot;
-            if (mp_load(&t->number) == 0) {            // claimed in this call: it has a leader to find.  A numbered slot keeps its number
-                int32_t* lead = &t->leader;
-                if (mp_load(lead) > (int)r) atomicMin(lead, (int)r);    // (it only falls: a stale read costs an atomic)
-            }
-            if (__atomic_load_n(&t->touched, __ATOMIC_RELAXED) != epoch) won = atomicExch(&t->touched, epoch) != epoch;
-        }
+        slot = mp_claim(st.table, st.mask, mp_key(w[0] >> 12, w[1] >> 12, w[2] >> 12), &st.head->claimed, max_voxels);      // -3: gave up
+        if (slot >= 0) won = gm_enter(lds, tid, st.table, slot, r, w, epoch);
     }
     if (r < num_rows) ws.row_slot[r] = won ? slot | GM_WON : slot;
     lds.slot[tid] = slot;
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_move_kernel(const float* _
     if (ko != 4 && !unmoved) {
         bool matched = true;
         if (ko == 0) {                                 // found AND numbered: a slot claimed in this call has no number yet
-            const long long at = sf_find(st.table, st.mask, mp_key(wo[0] >> 12, wo[1] >> 12, wo[2] >> 12));
+            const long long at = mp_find(st.table, st.mask, mp_key(wo[0] >> 12, wo[1] >> 12, wo[2] >> 12));
             matched = at >= 0 && mp_load(&st.table[at].number) != 0;
             if (matched) so = (int)at;
         }
@@ -217,24 +218,13 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_move_kernel(const float* _
             if (kn < 3) atomicAdd(&moved[kn], 1);
             if (kn == 0) {
                 atomicAdd(&moved[3], 1);
-                sn = sf_claim(st.table, st.mask, mp_key(wn[0] >> 12, wn[1] >> 12, wn[2] >> 12), &st.head->claimed, max_voxels);   // -3: gave up
+                sn = mp_claim(st.table, st.mask, mp_key(wn[0] >> 12, wn[1] >> 12, wn[2] >> 12), &st.head->claimed, max_voxels);   // -3: gave up
             }
-            if (so >= 0) {
-                out.pos[tid][0] = (unsigned short)(wo[0] & 4095), out.pos[tid][1] = (unsigned short)(wo[1] & 4095);
-                out.pos[tid][2] = (unsigned short)(wo[2] & 4095);
-                uint32_t* tp = &st.table[so].touched;
-                if (__atomic_load_n(tp, __ATOMIC_RELAXED) != epoch) won_o = atomicExch(tp, epoch) != epoch;
+            if (so >= 0) {                             // (numbered: it has no leader to find)
+                sf_stage_pos(out, tid, wo);
+                won_o = gm_touch(&st.table[so].touched, epoch);
             }
-            if (sn >= 0) {
-                in.pos[tid][0] = (unsigned short)(wn[0] & 4095), in.pos[tid][1] = (unsigned short)(wn[1] & 4095);
-                in.pos[tid][2] = (unsigned short)(wn[2] & 4095);
-                sf_slot* t = st.table + sn;
-                if (mp_load(&t->number) == 0) {        // claimed in this call: it has a leader to find
-                    int32_t* lead = &t->leader;
-                    if (mp_load(lead) > (int)r) atomicMin(lead, (int)r);
-                }
-                if (__atomic_load_n(&t->touched, __ATOMIC_RELAXED) != epoch) won_n = atomicExch(&t->touched, epoch) != epoch;
-            }
+            if (sn >= 0) won_n = gm_enter(in, tid, st.table, sn, r, wn, epoch);
         }
     }
     if (r < num_rows) {
@@ -282,14 +272,14 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_mark_kernel(long long num_
         const int s = ws.row_slot[r * ws.per_row + word];
         if (s < 0 || !(s & GM_WON)) continue;
         long long g0, g1, g2;
-        sf_cell(st.table[s & (GM_WON - 1)].key, g0, g1, g2);
+        mp_cell(st.table[s & (GM_WON - 1)].key, g0, g1, g2);
         for (int o2 = -ring; o2 <= ring; ++o2) {
-            if (!sf_in_range(g2 + o2)) continue;
+            if (!mp_in_range(g2 + o2)) continue;
             for (int o1 = -ring; o1 <= ring; ++o1) {
-                if (!sf_in_range(g1 + o1)) continue;
+                if (!mp_in_range(g1 + o1)) continue;
                 for (int o0 = -ring; o0 <= ring; ++o0) {
-                    if (!sf_in_range(g0 + o0)) continue;
-                    const long long at = sf_find(st.table, st.mask, mp_key(g0 + o0, g1 + o1, g2 + o2));
+                    if (!mp_in_range(g0 + o0)) continue;
+                    const long long at = mp_find(st.table, st.mask, mp_key(g0 + o0, g1 + o1, g2 + o2));
                     if (at < 0) continue;
                     uint32_t* dp = &st.table[at].dirty;
                     // (one atomic add per flipped slot.  Lanes of a wave that flip in the same step sharing ONE add -- a ballot -- measured
@@ -308,7 +298,7 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_mark_kernel(long long num_
 __global__ __launch_bounds__(MP_GROUP) void growmap_group_kernel(long long tiles, long long max_voxels, gm_state st, gm_ws ws) {
     __shared__ int part[MP_GROUP / 64];
     if (gm_no_map(st, ws, max_voxels)) return;
-    sf_scan_group(tiles, ws.tile, ws.group, part);
+    mp_scan_group(tiles, ws.tile, ws.group, part);
 }
 
 __global__ __launch_bounds__(MP_THREADS) void growmap_top_kernel(long long groups, long long max_voxels, gm_state st, gm_ws ws,
@@ -316,7 +306,7 @@ __global__ __launch_bounds__(MP_THREADS) void growmap_top_kernel(long long group
     __shared__ int part[MP_THREADS / 64];
     const bool bad = ws.head[MP_BAD] != 0, over = (long long)st.head->claimed > max_voxels;
     int fresh = 0;
-    if (!bad && !over) fresh = sf_scan_top(groups, ws.group, part);
+    if (!bad && !over) fresh = mp_scan_top(groups, ws.group, part);
     if (threadIdx.x != 0) return;
     if (bad) {                                         // the state and the outputs stay as they were
         num_call[0] = -1, num_call[1] = 0, num_call[2] = 0, num_call[3] = 0;
@@ -378,66 +368,45 @@ static gm_bits gm_bits_of(const double* params) {
     return b;
 }
 
+// the size queries answer 0 where the entries refuse: mp_shape_refusal's bounds, with a value in range for what a query does not take
 extern "C" size_t epcnet_surfel_map_state_bytes(long long max_voxels) {
-    if (!sf_voxels_supported(max_voxels)) return 0;
+    if (!mp_supported(0, 0, max_voxels)) return 0;
     return gm_state_layout(nullptr, max_voxels).bytes;
 }
 
+static size_t gm_workspace_bytes(long long num_rows, int num_clouds, int ring, int per_row) {
+    if (!mp_supported(num_rows, num_clouds, 1) || ring < 0 || ring > EPC_SURFEL_MAX_RING) return 0;
+    return gm_layout(nullptr, num_rows, ring, per_row).bytes;
+}
 extern "C" size_t epcnet_surfel_map_add_workspace_bytes(long long num_rows, int num_clouds, int ring) {
-    if (!sf_rows_supported(num_rows, num_clouds) || ring < 0 || ring > EPC_SURFEL_MAX_RING) return 0;
-    return gm_layout(nullptr, num_rows, ring).bytes;
+    return gm_workspace_bytes(num_rows, num_clouds, ring, 1);
+}
+extern "C" size_t epcnet_surfel_map_move_workspace_bytes(long long num_rows, int num_clouds, int ring) {
+    return gm_workspace_bytes(num_rows, num_clouds, ring, 2);
 }
 
-// the refusals of an entry `who` (init checks under its own name; add and move share gm_call, which is told the entry's)
-#define GM_CHECK_ARG(who, cond, msg)                                                                                           \
-    do {                                                                                                                       \
-        if (!(cond)) {                                                                                                         \
-            epc_set_error("%s: %s", who, msg);                                                                                 \
-            return EPC_EINVAL;                                                                                                 \
-        }                                                                                                                      \
-    } while (0)
-#define GM_CHECK_BYTES(who, what, bytes, need)                                                                                 \
-    do {                                                                                                                       \
-        if ((bytes) < (need)) {                                                                                                \
-            epc_set_error("%s: %s of %zu bytes, %zu needed", who, what, (size_t)(bytes), (size_t)(need));                      \
-            return EPC_ENOMEM;                                                                                                 \
-        }                                                                                                                      \
-    } while (0)
-#define GM_CHECK_STATE(who, state, state_bytes, max_voxels)                                                                    \
-    do {                                                                                                                       \
-        GM_CHECK_ARG(who, epc_aligned16(state), "state must be 16-byte aligned");                                              \
-        GM_CHECK_BYTES(who, "state", state_bytes, epcnet_surfel_map_state_bytes(max_voxels));                                  \
-    } while (0)
-#define GM_CHECK_LAUNCH(who)                                                                                                   \
-    do {                                                                                                                       \
-        hipError_t e__ = hipGetLastError();                                                                                    \
-        if (e__ != hipSuccess) {                                                                                               \
-            epc_set_error("%s: launch failed: %s", who, hipGetErrorString(e__));                                               \
-            return EPC_EHIP;                                                                                                   \
-        }                                                                                                                      \
+// the refusals of a state under the name of the entry `who` (init checks under its own; add and move share gm_call, which is told
+// the entry's)
+#define GM_STATE_REFUSALS(who, state, state_bytes, max_voxels)                                                \
+    do {                                                                                                      \
+        EPC_CHECK_ARG_AS(who, epc_aligned16(state), "state must be 16-byte aligned");                         \
+        EPC_CHECK_BYTES_AS(who, "state", state_bytes, epcnet_surfel_map_state_bytes(max_voxels));             \
     } while (0)
 
 extern "C" int epcnet_surfel_map_init(const double* origin, const double* params, long long max_voxels, void* state, size_t state_bytes,
                                       float* map_points, int32_t* count, float* centroid, float* normal, float* eigen, int32_t* support,
                                       int32_t* num_out, void* stream) {
     EPC_CHECK_ARG(origin && params && state && map_points && count && centroid && normal && eigen && support && num_out, "null pointer");
-    EPC_CHECK_ARG(max_voxels >= 1 && max_voxels <= (1ll << 28), "need 1 <= max_voxels <= 2^28");
+    const char* const shape = mp_shape_refusal(0, 0, max_voxels);
+    EPC_CHECK_ARG(!shape, shape);
     const char* const refusal = sf_params_refusal(params);
     EPC_CHECK_ARG(!refusal, refusal);
-    GM_CHECK_STATE(__func__, state, state_bytes, max_voxels);
+    GM_STATE_REFUSALS(__func__, state, state_bytes, max_voxels);
     const gm_state st = gm_state_layout(state, max_voxels).st;
-    const unsigned long long blocks = ((st.mask + 1) * 16 + MP_THREADS - 1) / MP_THREADS;
-    hipLaunchKernelGGL(growmap_init_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(MP_THREADS), 0, (hipStream_t)stream, origin,
-                       gm_bits_of(params), max_voxels, st, map_points, count, centroid, normal, eigen, support, num_out);
+    hipLaunchKernelGGL(growmap_init_kernel, dim3(sf_clear_blocks(st.mask)), dim3(MP_THREADS), 0, (hipStream_t)stream, origin, gm_bits_of(params),
+                       max_voxels, st, map_points, count, centroid, normal, eigen, support, num_out);
     EPC_CHECK_LAUNCH();
     return EPC_OK;
-}
-
-
-
-extern "C" size_t epcnet_surfel_map_move_workspace_bytes(long long num_rows, int num_clouds, int ring) {
-    if (!sf_rows_supported(num_rows, num_clouds) || ring < 0 || ring > EPC_SURFEL_MAX_RING) return 0;
-    return gm_layout(nullptr, num_rows, ring, 2).bytes;
 }
 
 // add and move: the same refusals and the same launches around ONE tile kernel of their own -- the insert, or the move (then row_slot
@@ -446,19 +415,17 @@ static int gm_call(const char* who, bool move, const float* points, const int32_
                    const double* poses, const double* new_poses, const double* params, long long max_voxels, void* state, size_t state_bytes,
                    float* map_points, int32_t* count, float* centroid, float* normal, float* eigen, int32_t* support, int32_t* num_out,
                    int32_t* num_call, void* workspace, size_t workspace_bytes, void* stream) {
-    GM_CHECK_ARG(who, points && offsets && poses && params && state && map_points && count && centroid && normal && eigen && support &&
-                          num_out && num_call && workspace,
-                 "null pointer");
-    GM_CHECK_ARG(who, num_rows >= 0 && num_rows < 2147483648ll, "need 0 <= num_rows < 2^31");
-    GM_CHECK_ARG(who, num_clouds >= 0 && num_clouds <= (1 << 24), "need 0 <= num_clouds <= 2^24");
-    GM_CHECK_ARG(who, max_voxels >= 1 && max_voxels <= (1ll << 28), "need 1 <= max_voxels <= 2^28");
+    EPC_CHECK_ARG_AS(who, points && offsets && poses && params && state && map_points && count && centroid && normal && eigen && support &&
+                              num_out && num_call && workspace,
+                     "null pointer");
+    const char* const shape = mp_shape_refusal(num_rows, num_clouds, max_voxels);
+    EPC_CHECK_ARG_AS(who, !shape, shape);
     const char* const refusal = sf_params_refusal(params);
-    GM_CHECK_ARG(who, !refusal, refusal);
-    GM_CHECK_STATE(who, state, state_bytes, max_voxels);
+    EPC_CHECK_ARG_AS(who, !refusal, refusal);
+    GM_STATE_REFUSALS(who, state, state_bytes, max_voxels);
     const sf_params pr = sf_params_of(params);
-    GM_CHECK_ARG(who, epc_aligned16(workspace), "workspace must be 16-byte aligned");
     const gm_layout_t layout = gm_layout(workspace, num_rows, pr.ring, move ? 2 : 1);
-    GM_CHECK_BYTES(who, "workspace", workspace_bytes, layout.bytes);
+    EPC_CHECK_WORKSPACE_AS(who, workspace, workspace_bytes, layout.bytes);
     hipStream_t s = (hipStream_t)stream;
     const gm_state st = gm_state_layout(state, max_voxels).st;
     const gm_ws ws = layout.ws;
@@ -467,7 +434,7 @@ static int gm_call(const char* who, bool move, const float* points, const int32_
     const long long checks = num_clouds > 0 ? ((long long)num_clouds + MP_THREADS - 1) / MP_THREADS : 1;
     hipLaunchKernelGGL(growmap_check_kernel, dim3((unsigned)checks), dim3(MP_THREADS), 0, s, offsets, num_rows, num_clouds, gm_bits_of(params),
                        max_voxels, st, ws);
-    GM_CHECK_LAUNCH(who);
+    EPC_CHECK_LAUNCH_AS(who);
     if (tiles > 0) {
         if (move)
             hipLaunchKernelGGL(growmap_move_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, points, offsets, num_rows, num_clouds, poses,
@@ -475,22 +442,22 @@ static int gm_call(const char* who, bool move, const float* points, const int32_
         else
             hipLaunchKernelGGL(growmap_insert_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, points, offsets, num_rows, num_clouds, poses,
                                pr, max_voxels, st, ws);
-        GM_CHECK_LAUNCH(who);
+        EPC_CHECK_LAUNCH_AS(who);
         hipLaunchKernelGGL(growmap_mark_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, num_rows, pr.ring, max_voxels, st, ws);
-        GM_CHECK_LAUNCH(who);
+        EPC_CHECK_LAUNCH_AS(who);
         hipLaunchKernelGGL(growmap_group_kernel, dim3((unsigned)groups), dim3(MP_GROUP), 0, s, tiles, max_voxels, st, ws);
-        GM_CHECK_LAUNCH(who);
+        EPC_CHECK_LAUNCH_AS(who);
     }
     hipLaunchKernelGGL(growmap_top_kernel, dim3(1), dim3(MP_THREADS), 0, s, groups, max_voxels, st, ws, num_out, num_call);
-    GM_CHECK_LAUNCH(who);
+    EPC_CHECK_LAUNCH_AS(who);
     if (tiles > 0) {
         hipLaunchKernelGGL(growmap_number_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, s, num_rows, max_voxels, st, ws);
-        GM_CHECK_LAUNCH(who);
+        EPC_CHECK_LAUNCH_AS(who);
         // a call's dirty voxels: at most (2 ring + 1)^3 per slot that a row left or entered, and never more than the map holds
         const long long bound = ws.dirty_cap < max_voxels ? ws.dirty_cap : max_voxels;
         hipLaunchKernelGGL(growmap_emit_kernel, dim3((unsigned)((bound + MP_THREADS - 1) / MP_THREADS)), dim3(MP_THREADS), 0, s, max_voxels, pr,
                            st, ws, map_points, count, centroid, normal, eigen, support);
-        GM_CHECK_LAUNCH(who);
+        EPC_CHECK_LAUNCH_AS(who);
     }
     return EPC_OK;
 }

@@ -7,17 +7,18 @@
 //   scan_clear_words       clears the workspace's head (scan_common.h: a launch, not a memset)
 //   map_clear_kernel       every slot of the table to (empty key, no leader, zero sums); the offsets' rule, an integer OR into the head
 //   map_insert_kernel      the hot path.  One thread per row, MP_TILE rows per workgroup: the tile finds the clouds of its first and last
-//                          row by binary search ONCE, the pose of the first comes through LDS; transform, classify, key; a 64-bit
-//                          atomicCAS claims a slot of the open-addressing table (linear probing), then integer atomics on the slot: three
-//                          sums, the count, atomicMin on the leader.  The slot a row landed in goes to row_slot (negative: no kept row).
-//                          The claimed slots are counted: more than max_voxels is the overflow, and a probe gives up once it sees that.
-//   map_count_kernel       per tile, the number of rows that are their slot's leader
-//   map_group_kernel       the exclusive scan of MP_TILE tile counts per workgroup, the group's total
-//   map_top_kernel         ONE workgroup: the exclusive scan of the group totals in chunks of its width with a running carry; num_out
+//                          row by binary search ONCE, the pose of the first comes through LDS; transform, classify, key; the claim of a
+//                          slot of the open-addressing table (mp_claim), then this file's own integer atomics on the slot, one lane per
+//                          row: three sums, the count, atomicMin on the leader.  The slot a row landed in goes to row_slot (negative:
+//                          no kept row).  The claimed slots are counted: more than max_voxels is the overflow, and a probe gives up
+//                          once it sees that.  (The prologue is surfel_common.h's sf_tile_row written out: as a call it leaves w live
+//                          across the helper's end, ten more instructions; DESIGN.md, "What the voxel maps share".)
+//   map_count_kernel, map_group_kernel, map_top_kernel      every leader's number: mp_is_leader counted per tile, mp_scan_group, mp_top; num_out
 //   map_emit_kernel        tiles over the rows: a leader's j = group + tile + its place in the tile; it writes row j and count j from its
 //                          slot.  Behind them tiles over the voxels: NaN rows and zero counts for j >= V, or everywhere after an overflow
 //                          or a failed call.
-// No float atomics, no inline assembly.
+// No float atomics, no inline assembly.  What does not follow the 40-byte slot -- the shape's refusals, key and cell, the claim loop, the
+// scan -- is map_common.h's, shared with the surfel files; the slot, its adds and the mean written from it are this file's.
 #include "map_common.h"
 
 // one slot of the table: 40 bytes
@@ -108,29 +109,11 @@ __global__ __launch_bounds__(MP_THREADS) void map_insert_kernel(const float* __r
             atomicAdd(&kinds[kind], 1);
             slot = -kind;                              // -1 absent, -2 out of range
             if (kind == 0) {
+                // (mp_key(w >> 12) written out: as a call its eight instructions come in another order -- DESIGN.md)
                 const unsigned long long key = ((unsigned long long)((w[2] >> 12) + EPC_MAP_MAX_CELL) << 42) |
                                                ((unsigned long long)((w[1] >> 12) + EPC_MAP_MAX_CELL) << 21) |
                                                (unsigned long long)((w[0] >> 12) + EPC_MAP_MAX_CELL);
-                unsigned long long s = mp_hash(key) & ws.mask;
-                slot = -3;                             // gave up: the table overflowed
-                for (unsigned probes = 0;; ++probes) {
-                    // (a full table holds no empty slot: the count of claimed slots is what ends the walk)
-                    if ((probes & 7) == 0 && (long long)mp_load(&ws.head[MP_CLAIMED]) > max_voxels) break;
-                    unsigned long long* kp = &ws.table[s].key;
-                    unsigned long long k = __atomic_load_n(kp, __ATOMIC_RELAXED);
-                    if (k == MP_EMPTY) {
-                        k = atomicCAS(kp, MP_EMPTY, key);
-                        if (k == MP_EMPTY) {
-                            atomicAdd(&ws.head[MP_CLAIMED], 1);
-                            k = key;
-                        }
-                    }
-                    if (k == key) {
-                        slot = (int)s;
-                        break;
-                    }
-                    s = (s + 1) & ws.mask;
-                }
+                slot = mp_claim(ws.table, ws.mask, key, &ws.head[MP_CLAIMED], max_voxels);   // -3: gave up
                 if (slot >= 0) {
                     mp_slot* t = ws.table + slot;
                     atomicAdd(&t->sum[0], (unsigned long long)(w[0] & 4095));
@@ -147,65 +130,31 @@ __global__ __launch_bounds__(MP_THREADS) void map_insert_kernel(const float* __r
     if (tid < 3 && kinds[tid]) atomicAdd(&ws.head[MP_KEPT + tid], kinds[tid]);
 }
 
-// the call has no map: the offsets were not valid, or more voxels than max_voxels were claimed (row_slot and the table may not be followed)
-__device__ __forceinline__ bool mp_no_map(const mp_ws& ws, long long max_voxels) {
-    return ws.head[MP_BAD] != 0 || (long long)ws.head[MP_CLAIMED] > max_voxels;
-}
-
-__device__ __forceinline__ int mp_is_leader(const mp_ws& ws, long long r, long long num_rows, int* slot) {
-    if (r >= num_rows) return 0;
-    const int s = ws.row_slot[r];
-    *slot = s;
-    return s >= 0 && ws.table[s].leader == (int)r ? 1 : 0;
-}
-
-// ---- launches 4 to 6: every leader's number ----------------------------------------------------------------------------------------------
+// ---- launches 4 to 6: every leader's number (map_common.h) -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(MP_THREADS) void map_count_kernel(long long num_rows, long long max_voxels, mp_ws ws) {
     __shared__ int part[MP_THREADS / 64];
-    if (mp_no_map(ws, max_voxels)) return;
+    if (mp_no_map(ws.head, max_voxels)) return;
     int slot, total;
-    block_scan<MP_THREADS / 64, int>(mp_is_leader(ws, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot), part, total);
+    block_scan<MP_THREADS / 64, int>(mp_is_leader(ws.table, ws.row_slot, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot), part, total);
     if (threadIdx.x == 0) ws.tile[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(MP_GROUP) void map_group_kernel(long long tiles, long long max_voxels, mp_ws ws) {
     __shared__ int part[MP_GROUP / 64];
-    if (mp_no_map(ws, max_voxels)) return;
-    const long long t = (long long)blockIdx.x * MP_GROUP + threadIdx.x;
-    const int v = t < tiles ? ws.tile[t] : 0;
-    int total;
-    const int excl = block_scan<MP_GROUP / 64, int>(v, part, total);
-    if (t < tiles) ws.tile[t] = excl;
-    if (threadIdx.x == 0) ws.group[blockIdx.x] = total;
+    if (mp_no_map(ws.head, max_voxels)) return;
+    mp_scan_group(tiles, ws.tile, ws.group, part);
 }
 
 __global__ __launch_bounds__(MP_THREADS) void map_top_kernel(long long groups, long long max_voxels, mp_ws ws, int32_t* __restrict__ num_out) {
     __shared__ int part[MP_THREADS / 64];
-    const bool bad = ws.head[MP_BAD] != 0, none = mp_no_map(ws, max_voxels);
-    if (!none) {
-        int carry = 0;
-        for (long long base = 0; base < groups; base += MP_THREADS) {
-            const long long g = base + threadIdx.x;
-            const int v = g < groups ? ws.group[g] : 0;
-            int total;
-            const int excl = carry + block_scan<MP_THREADS / 64, int>(v, part, total);
-            if (g < groups) ws.group[g] = excl;
-            carry += total;
-        }
-    }
-    if (threadIdx.x == 0) {
-        num_out[0] = none ? -1 : ws.head[MP_CLAIMED];                       // V: every claimed slot has a leader
-        num_out[1] = bad ? 0 : ws.head[MP_KEPT];
-        num_out[2] = bad ? 0 : ws.head[MP_KEPT + 1];
-        num_out[3] = bad ? 0 : ws.head[MP_KEPT + 2];
-    }
+    mp_top(ws.head, groups, ws.group, max_voxels, num_out, part);
 }
 
 // ---- launch 7: the outputs -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MP_THREADS) void map_emit_kernel(long long num_rows, long long row_tiles, long long max_voxels, mp_params pr,
                                                               mp_ws ws, float* __restrict__ map_points, int32_t* __restrict__ count) {
     __shared__ int part[MP_THREADS / 64];
-    const bool none = mp_no_map(ws, max_voxels);       // (uniform)
+    const bool none = mp_no_map(ws.head, max_voxels);  // (uniform)
     const float nan = epc_nan_f32();
     if ((long long)blockIdx.x >= row_tiles) {          // the voxels no leader writes
         const long long j = ((long long)blockIdx.x - row_tiles) * MP_THREADS + threadIdx.x;
@@ -217,27 +166,23 @@ __global__ __launch_bounds__(MP_THREADS) void map_emit_kernel(long long num_rows
     }
     if (none) return;
     int slot = -1, total;
-    const int lead = mp_is_leader(ws, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot);
+    const int lead = mp_is_leader(ws.table, ws.row_slot, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot);
     const long long j = (long long)ws.group[blockIdx.x / MP_GROUP] + ws.tile[blockIdx.x] + block_scan<MP_THREADS / 64, int>(lead, part, total);
     if (!lead || j >= max_voxels) return;              // (j < V <= max_voxels here: the bound only keeps a wrong number inside the buffers)
     const mp_slot* t = ws.table + slot;
     const long long cnt = t->cnt;
-    const unsigned long long key = t->key;
+    long long cell[3];
+    mp_cell(t->key, cell[0], cell[1], cell[2]);
     float o[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
 #pragma clang fp contract(off)
-        const long long g = (long long)((key >> (21 * a)) & 0x1fffff) - EPC_MAP_MAX_CELL;
+        const long long g = cell[a];
         const long long mean = (long long)(t->sum[a] / (unsigned long long)cnt);
         o[a] = cnt >= pr.min_count ? (float)((double)(g * 4096 + mean) * pr.step) : nan;
     }
     map_points[(size_t)j * 3] = o[0], map_points[(size_t)j * 3 + 1] = o[1], map_points[(size_t)j * 3 + 2] = o[2];
     count[j] = (int32_t)cnt;
-}
-
-static bool mp_supported(long long num_rows, int num_clouds, long long max_voxels) {
-    return num_rows >= 0 && num_rows < 2147483648ll && num_clouds >= 0 && num_clouds <= (1 << 24) && max_voxels >= 1 &&
-           max_voxels <= (1ll << 28);
 }
 
 extern "C" size_t epcnet_map_fuse_workspace_bytes(long long num_rows, int num_clouds, long long max_voxels) {
@@ -249,9 +194,8 @@ extern "C" int epcnet_map_fuse(const float* points, const int32_t* offsets, long
                                const double* origin, const double* params, long long max_voxels, float* map_points, int32_t* count,
                                int32_t* num_out, void* workspace, size_t workspace_bytes, void* stream) {
     EPC_CHECK_ARG(points && offsets && poses && origin && params && map_points && count && num_out && workspace, "null pointer");
-    EPC_CHECK_ARG(num_rows >= 0 && num_rows < 2147483648ll, "need 0 <= num_rows < 2^31");
-    EPC_CHECK_ARG(num_clouds >= 0 && num_clouds <= (1 << 24), "need 0 <= num_clouds <= 2^24");
-    EPC_CHECK_ARG(max_voxels >= 1 && max_voxels <= (1ll << 28), "need 1 <= max_voxels <= 2^28");
+    const char* const shape = mp_shape_refusal(num_rows, num_clouds, max_voxels);
+    EPC_CHECK_ARG(!shape, shape);
     const double voxel = params[0], min_count = params[1];
     EPC_CHECK_ARG(__builtin_isfinite(voxel) && voxel >= 1.0 / 1048576.0 && voxel <= 1048576.0, "voxel must be finite and in [2^-20, 2^20]");
     EPC_CHECK_ARG(min_count >= 1.0 && min_count < 2147483648.0 && min_count == __builtin_floor(min_count),

@@ -104,15 +104,18 @@ static inline int scan_clear_words_launch(int32_t* words, int count, void* strea
 }
 
 // the refusal of a workspace that is too small, and, in front of it, of one that is not 16-byte aligned
-#define EPC_CHECK_WORKSPACE_BYTES(workspace_bytes, need)                                                             \
+// (_AS: under the name `who`, and of a buffer called `what`, a string literal -- growmap.hip's state is refused in the same words)
+#define EPC_CHECK_BYTES_AS(who, what, bytes, need)                                                                    \
     do {                                                                                                             \
-        if ((workspace_bytes) < (need)) {                                                                            \
-            epc_set_error("%s: workspace of %zu bytes, %zu needed", __func__, (size_t)(workspace_bytes), (size_t)(need)); \
+        if ((bytes) < (need)) {                                                                                      \
+            epc_set_error("%s: " what " of %zu bytes, %zu needed", who, (size_t)(bytes), (size_t)(need));            \
             return EPC_ENOMEM;                                                                                       \
         }                                                                                                            \
     } while (0)
-#define EPC_CHECK_WORKSPACE(workspace, workspace_bytes, need)                           \
-    do {                                                                                \
-        EPC_CHECK_ARG(epc_aligned16(workspace), "workspace must be 16-byte aligned");   \
-        EPC_CHECK_WORKSPACE_BYTES(workspace_bytes, need);                               \
+#define EPC_CHECK_WORKSPACE_BYTES(workspace_bytes, need) EPC_CHECK_BYTES_AS(__func__, "workspace", workspace_bytes, need)
+#define EPC_CHECK_WORKSPACE_AS(who, workspace, workspace_bytes, need)                            \
+    do {                                                                                         \
+        EPC_CHECK_ARG_AS(who, epc_aligned16(workspace), "workspace must be 16-byte aligned");    \
+        EPC_CHECK_BYTES_AS(who, "workspace", workspace_bytes, need);                             \
     } while (0)
+#define EPC_CHECK_WORKSPACE(workspace, workspace_bytes, need) EPC_CHECK_WORKSPACE_AS(__func__, workspace, workspace_bytes, need)

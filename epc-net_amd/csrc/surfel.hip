@@ -20,8 +20,9 @@
 //                          key or an empty slot -- cap >= 2 max_voxels + 1 leaves one), pools their moments in int64 and solves in float64
 //                          registers.  Behind them tiles over the voxels: NaN / 0 for j >= V, or everywhere after an overflow or a failed
 //                          call.
-// No float atomics, no inline assembly, no scratch.  The slot, a tile's rows, the claim loop, the sixteen-lane adds, the lookup and the
-// pool-and-solve are surfel_common.h's: growmap.hip (the map that grows across calls) runs the same definitions on a persistent table.
+// No float atomics, no inline assembly, no scratch.  The claim loop, the lookup and the scan are map_common.h's (map.hip runs them
+// too); the slot, a tile's rows, the sixteen-lane adds and the pool-and-solve are surfel_common.h's: growmap.hip (the map that grows
+// across calls) runs the same definitions on a persistent table.
 #include "surfel_common.h"
 
 // the workspace: head (16 int32, padded to 128 bytes: a slot is one 128-byte line of an aligned workspace) | table (cap slots) | row_slot (num_rows int32) | tile counts (int32) | group totals (int32)
@@ -47,10 +48,7 @@ __global__ __launch_bounds__(MP_THREADS) void surfel_clear_kernel(const int32_t*
                                                                   sf_ws ws) {
     const unsigned long long stride = (unsigned long long)gridDim.x * MP_THREADS;
     const unsigned long long first = (unsigned long long)blockIdx.x * MP_THREADS + threadIdx.x;
-    // sixteen lanes per slot, one word each: a wave-instruction stores four whole slots
-    const unsigned long long words = (ws.mask + 1) * 16;
-    unsigned long long* const base = reinterpret_cast<unsigned long long*>(ws.table);
-    for (unsigned long long i = first; i < words; i += stride) base[i] = sf_cleared_word((unsigned)(i & 15));
+    sf_clear_table(ws.table, ws.mask, first, stride);
     bool bad = false;
     const long long checks = num_clouds > 0 ? num_clouds : 1;
     for (long long i = (long long)first; i < checks; i += (long long)stride) bad |= offsets_rule_bad(offsets, num_clouds, num_rows, i);
@@ -70,12 +68,10 @@ __global__ __launch_bounds__(MP_THREADS) void surfel_insert_kernel(const float* 
     const int kind = sf_tile_row(points, offsets, num_rows, num_clouds, poses, origin, pr.voxel, lds, r0, w);
     int slot = -kind;                                  // -1 absent, -2 out of range, -4 no row of any cloud
     if (kind == 0) {
-        slot = sf_claim(ws.table, ws.mask, mp_key(w[0] >> 12, w[1] >> 12, w[2] >> 12), &ws.head[MP_CLAIMED], max_voxels);   // -3: gave up
+        slot = mp_claim(ws.table, ws.mask, mp_key(w[0] >> 12, w[1] >> 12, w[2] >> 12), &ws.head[MP_CLAIMED], max_voxels);   // -3: gave up
         if (slot >= 0) {
-            lds.pos[tid][0] = (unsigned short)(w[0] & 4095), lds.pos[tid][1] = (unsigned short)(w[1] & 4095);
-            lds.pos[tid][2] = (unsigned short)(w[2] & 4095);
-            int32_t* lead = &ws.table[slot].leader;
-            if (mp_load(lead) > (int)r) atomicMin(lead, (int)r);        // (it only falls: a stale read costs an atomic)
+            sf_stage_pos(lds, tid, w);
+            sf_lead(ws.table + slot, r);
         }
     }
     if (r < num_rows) ws.row_slot[r] = slot;
@@ -86,43 +82,24 @@ __global__ __launch_bounds__(MP_THREADS) void surfel_insert_kernel(const float* 
     if (tid < 3 && lds.kinds[tid]) atomicAdd(&ws.head[MP_KEPT + tid], lds.kinds[tid]);
 }
 
-// the call has no map: the offsets were not valid, or more voxels than max_voxels were claimed (row_slot and the table may not be followed)
-__device__ __forceinline__ bool sf_no_map(const sf_ws& ws, long long max_voxels) {
-    return ws.head[MP_BAD] != 0 || (long long)ws.head[MP_CLAIMED] > max_voxels;
-}
-
-__device__ __forceinline__ int sf_is_leader(const sf_ws& ws, long long r, long long num_rows, int* slot) {
-    if (r >= num_rows) return 0;
-    const int s = ws.row_slot[r];
-    *slot = s;
-    return s >= 0 && ws.table[s].leader == (int)r ? 1 : 0;
-}
-
-// ---- launches 4 to 6: every leader's number ----------------------------------------------------------------------------------------------
+// ---- launches 4 to 6: every leader's number (map_common.h) -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(MP_THREADS) void surfel_count_kernel(long long num_rows, long long max_voxels, sf_ws ws) {
     __shared__ int part[MP_THREADS / 64];
-    if (sf_no_map(ws, max_voxels)) return;
+    if (mp_no_map(ws.head, max_voxels)) return;
     int slot, total;
-    block_scan<MP_THREADS / 64, int>(sf_is_leader(ws, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot), part, total);
+    block_scan<MP_THREADS / 64, int>(mp_is_leader(ws.table, ws.row_slot, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot), part, total);
     if (threadIdx.x == 0) ws.tile[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(MP_GROUP) void surfel_group_kernel(long long tiles, long long max_voxels, sf_ws ws) {
     __shared__ int part[MP_GROUP / 64];
-    if (sf_no_map(ws, max_voxels)) return;
-    sf_scan_group(tiles, ws.tile, ws.group, part);
+    if (mp_no_map(ws.head, max_voxels)) return;
+    mp_scan_group(tiles, ws.tile, ws.group, part);
 }
 
 __global__ __launch_bounds__(MP_THREADS) void surfel_top_kernel(long long groups, long long max_voxels, sf_ws ws, int32_t* __restrict__ num_out) {
     __shared__ int part[MP_THREADS / 64];
-    const bool bad = ws.head[MP_BAD] != 0, none = sf_no_map(ws, max_voxels);
-    if (!none) sf_scan_top(groups, ws.group, part);
-    if (threadIdx.x == 0) {
-        num_out[0] = none ? -1 : ws.head[MP_CLAIMED];                       // V: every claimed slot has a leader
-        num_out[1] = bad ? 0 : ws.head[MP_KEPT];
-        num_out[2] = bad ? 0 : ws.head[MP_KEPT + 1];
-        num_out[3] = bad ? 0 : ws.head[MP_KEPT + 2];
-    }
+    mp_top(ws.head, groups, ws.group, max_voxels, num_out, part);
 }
 
 // ---- launch 7: the outputs -----------------------------------------------------------------------------------------------------------------
@@ -132,7 +109,7 @@ __global__ __launch_bounds__(MP_THREADS) void surfel_emit_kernel(long long num_r
                                                                  float* __restrict__ eigen, int32_t* __restrict__ support) {
     __shared__ int part[MP_THREADS / 64];
     __shared__ int lead_slot[MP_TILE];
-    const bool none = sf_no_map(ws, max_voxels);       // (uniform)
+    const bool none = mp_no_map(ws.head, max_voxels);  // (uniform)
     if ((long long)blockIdx.x >= row_tiles) {          // the voxels no leader writes
         const long long j = ((long long)blockIdx.x - row_tiles) * MP_THREADS + threadIdx.x;
         if (j < max_voxels && (none || j >= (long long)ws.head[MP_CLAIMED])) sf_write_none(j, map_points, count, centroid, normal, eigen, support);
@@ -140,7 +117,7 @@ __global__ __launch_bounds__(MP_THREADS) void surfel_emit_kernel(long long num_r
     }
     if (none) return;
     int slot = -1, total;
-    const int lead = sf_is_leader(ws, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot);
+    const int lead = mp_is_leader(ws.table, ws.row_slot, (long long)blockIdx.x * MP_TILE + threadIdx.x, num_rows, &slot);
     const int place = block_scan<MP_THREADS / 64, int>(lead, part, total);
     if (lead) lead_slot[place] = slot;                 // the tile's leaders in row order, packed to the first lanes
     __syncthreads();
@@ -153,7 +130,7 @@ __global__ __launch_bounds__(MP_THREADS) void surfel_emit_kernel(long long num_r
 }
 
 extern "C" size_t epcnet_map_surfels_workspace_bytes(long long num_rows, int num_clouds, long long max_voxels) {
-    if (!sf_rows_supported(num_rows, num_clouds) || !sf_voxels_supported(max_voxels)) return 0;
+    if (!mp_supported(num_rows, num_clouds, max_voxels)) return 0;
     return sf_layout(nullptr, num_rows, max_voxels).bytes;
 }
 
@@ -164,9 +141,8 @@ extern "C" int epcnet_map_surfels(const float* points, const int32_t* offsets, l
     EPC_CHECK_ARG(points && offsets && poses && origin && params && map_points && count && centroid && normal && eigen && support &&
                       num_out && workspace,
                   "null pointer");
-    EPC_CHECK_ARG(num_rows >= 0 && num_rows < 2147483648ll, "need 0 <= num_rows < 2^31");
-    EPC_CHECK_ARG(num_clouds >= 0 && num_clouds <= (1 << 24), "need 0 <= num_clouds <= 2^24");
-    EPC_CHECK_ARG(max_voxels >= 1 && max_voxels <= (1ll << 28), "need 1 <= max_voxels <= 2^28");
+    const char* const shape = mp_shape_refusal(num_rows, num_clouds, max_voxels);
+    EPC_CHECK_ARG(!shape, shape);
     const char* const refusal = sf_params_refusal(params);
     EPC_CHECK_ARG(!refusal, refusal);
     EPC_CHECK_WORKSPACE(workspace, workspace_bytes, epcnet_map_surfels_workspace_bytes(num_rows, num_clouds, max_voxels));
@@ -175,9 +151,7 @@ extern "C" int epcnet_map_surfels(const float* points, const int32_t* offsets, l
     const sf_ws ws = sf_layout(workspace, num_rows, max_voxels).ws;
     const long long tiles = mp_tiles(num_rows), groups = mp_groups(num_rows);
     if (int rc = scan_clear_words_launch(ws.head, MP_HEAD, st, __func__)) return rc;
-    const unsigned long long clear_blocks = ((ws.mask + 1) * 16 + MP_THREADS - 1) / MP_THREADS;
-    hipLaunchKernelGGL(surfel_clear_kernel, dim3((unsigned)(clear_blocks < 65536 ? clear_blocks : 65536)), dim3(MP_THREADS), 0, st, offsets,
-                       num_rows, num_clouds, ws);
+    hipLaunchKernelGGL(surfel_clear_kernel, dim3(sf_clear_blocks(ws.mask)), dim3(MP_THREADS), 0, st, offsets, num_rows, num_clouds, ws);
     EPC_CHECK_LAUNCH();
     if (tiles > 0) {
         hipLaunchKernelGGL(surfel_insert_kernel, dim3((unsigned)tiles), dim3(MP_THREADS), 0, st, points, offsets, num_rows, num_clouds, poses,

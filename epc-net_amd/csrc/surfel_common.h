@@ -1,9 +1,10 @@
 // ONE definition of what the two surfel files share (surfel.hip: epcnet_map_surfels, the map built in one call; growmap.hip:
-// epcnet_surfel_map_add, the map that grows across calls): the slot of the open-addressing table, the parameters and their refusals, a
-// tile's rows -> kinds and lattice positions, the claim loop, the sixteen-lane adds, the read-only lookup, the Jacobi rotation and the
-// pool-and-solve behind them, and the two upper levels of the leaders' scan.  The bit contract of include/epcnet_surfels.h forbids a second
-// copy of the float64 sequence: both files' outputs come out of sf_pool_solve.  Device helpers are __forceinline__: a kernel's code is
-// what it was with the piece written out.
+// epcnet_surfel_map_add, the map that grows across calls) and that follows the 128-byte slot: the slot and its cleared state, the
+// parameters and their refusals, a tile's rows -> kinds and lattice positions, a row's position and its claim to lead on the way into
+// a slot, the sixteen-lane adds, the Jacobi rotation and the pool-and-solve.  What does not depend on the slot's layout -- key and
+// cell, the claim loop, the lookup, the leaders' scan -- is map_common.h's, shared with map.hip.  The bit contract of
+// include/epcnet_surfels.h forbids a second copy of the float64 sequence: both files' outputs come out of sf_pool_solve.  Device
+// helpers are __forceinline__: a kernel's code is what it was with the piece written out.
 #ifndef EPC_SURFEL_COMMON_H
 #define EPC_SURFEL_COMMON_H
 #include "map_common.h"
@@ -28,6 +29,18 @@ static_assert(sizeof(sf_slot) == 128, "a slot is sixteen 64-bit words");
 __device__ __forceinline__ unsigned long long sf_cleared_word(unsigned e) {
     return e == 0 ? MP_EMPTY : e == 14 ? (unsigned long long)MP_NO_LEADER : 0ull;
 }
+// every slot of the table cleared by the threads first, first + stride, ...: sixteen lanes per slot, one word each -- a wave-instruction
+// stores four whole slots
+__device__ __forceinline__ void sf_clear_table(sf_slot* table, unsigned long long mask, unsigned long long first, unsigned long long stride) {
+    const unsigned long long words = (mask + 1) * 16;
+    unsigned long long* const base = reinterpret_cast<unsigned long long*>(table);
+    for (unsigned long long i = first; i < words; i += stride) base[i] = sf_cleared_word((unsigned)(i & 15));
+}
+// the workgroups of MP_THREADS that a clearing launch takes: a thread per word, at most 65536 of them
+static inline unsigned sf_clear_blocks(unsigned long long mask) {
+    const unsigned long long blocks = ((mask + 1) * 16 + MP_THREADS - 1) / MP_THREADS;
+    return (unsigned)(blocks < 65536 ? blocks : 65536);
+}
 
 struct sf_params {
     double voxel, step, step8;     // step = fl(voxel / 4096), step8 = fl(voxel / 256)
@@ -35,7 +48,7 @@ struct sf_params {
     int ring;
 };
 
-// ---- host: the rules of the eight doubles and of the three counts -----------------------------------------------------------------------
+// ---- host: the rules of the eight doubles (those of the three counts: mp_shape_refusal) ---------------------------------------------------
 // why `params` (EPC_SURFEL_PARAMS doubles in host memory) are refused, or NULL
 static inline const char* sf_params_refusal(const double* params) {
     const double voxel = params[0], min_count = params[1], ring = params[2], min_support = params[3];
@@ -60,10 +73,6 @@ static inline sf_params sf_params_of(const double* params) {
     pr.ring = (int)params[2];
     return pr;
 }
-static inline bool sf_rows_supported(long long num_rows, int num_clouds) {
-    return num_rows >= 0 && num_rows < 2147483648ll && num_clouds >= 0 && num_clouds <= (1 << 24);
-}
-static inline bool sf_voxels_supported(long long max_voxels) { return max_voxels >= 1 && max_voxels <= (1ll << 28); }
 
 // ---- the rows of a tile -----------------------------------------------------------------------------------------------------------------
 // what an insert kernel keeps in LDS
@@ -110,25 +119,15 @@ __device__ __forceinline__ int sf_tile_row(const float* __restrict__ points, con
     return kind;
 }
 
-// The slot of `key`, claimed by a 64-bit atomicCAS where the table does not hold it yet (linear probing; *claimed counts the claims), or
-// -3: the table overflowed -- a full table holds no empty slot: the count of claimed slots is what ends the walk.
-__device__ __forceinline__ int sf_claim(sf_slot* __restrict__ table, unsigned long long mask, unsigned long long key, int32_t* claimed,
-                                        long long max_voxels) {
-    unsigned long long s = mp_hash(key) & mask;
-    for (unsigned probes = 0;; ++probes) {
-        if ((probes & 7) == 0 && (long long)mp_load(claimed) > max_voxels) return -3;
-        unsigned long long* kp = &table[s].key;
-        unsigned long long k = __atomic_load_n(kp, __ATOMIC_RELAXED);
-        if (k == MP_EMPTY) {
-            k = atomicCAS(kp, MP_EMPTY, key);
-            if (k == MP_EMPTY) {
-                atomicAdd(claimed, 1);
-                k = key;
-            }
-        }
-        if (k == key) return (int)s;
-        s = (s + 1) & mask;
-    }
+// on the way into a slot: the row's position in its cell, for the tile's adds
+__device__ __forceinline__ void sf_stage_pos(sf_tile_lds& lds, int tid, const long long* w) {
+    lds.pos[tid][0] = (unsigned short)(w[0] & 4095), lds.pos[tid][1] = (unsigned short)(w[1] & 4095);
+    lds.pos[tid][2] = (unsigned short)(w[2] & 4095);
+}
+// and row r's claim to lead slot t (the leader only falls: a stale read costs an atomic)
+__device__ __forceinline__ void sf_lead(sf_slot* t, long long r) {
+    int32_t* lead = &t->leader;
+    if (mp_load(lead) > (int)r) atomicMin(lead, (int)r);
 }
 
 // The tile's adds, behind a barrier that follows the last write of lds.slot / lds.pos: sixteen lanes per row, one per word of its slot
@@ -152,49 +151,7 @@ __device__ __forceinline__ void sf_add_rows(sf_slot* __restrict__ table, const s
     }
 }
 
-// ---- the leaders' scan above the tiles ------------------------------------------------------------------------------------------------------
-// one workgroup of MP_GROUP threads: the tiles' counts of its group to exclusive prefixes, the group's total to group[blockIdx.x]
-__device__ __forceinline__ void sf_scan_group(long long tiles, int32_t* __restrict__ tile, int32_t* __restrict__ group, int* part) {
-    const long long t = (long long)blockIdx.x * MP_GROUP + threadIdx.x;
-    const int v = t < tiles ? tile[t] : 0;
-    int total;
-    const int excl = block_scan<MP_GROUP / 64, int>(v, part, total);
-    if (t < tiles) tile[t] = excl;
-    if (threadIdx.x == 0) group[blockIdx.x] = total;
-}
-// one workgroup of MP_THREADS threads: the groups' totals to exclusive prefixes -> the sum of all
-__device__ __forceinline__ int sf_scan_top(long long groups, int32_t* __restrict__ group, int* part) {
-    int carry = 0;
-    for (long long base = 0; base < groups; base += MP_THREADS) {
-        const long long g = base + threadIdx.x;
-        const int v = g < groups ? group[g] : 0;
-        int total;
-        const int excl = carry + block_scan<MP_THREADS / 64, int>(v, part, total);
-        if (g < groups) group[g] = excl;
-        carry += total;
-    }
-    return carry;
-}
-
 // ---- a voxel's outputs ------------------------------------------------------------------------------------------------------------------
-// the slot of `key`, or -1: the walk ends at the key or at an empty slot (the table is at most half full)
-__device__ __forceinline__ long long sf_find(const sf_slot* __restrict__ table, unsigned long long mask, unsigned long long key) {
-    unsigned long long s = mp_hash(key) & mask;
-    for (;;) {
-        const unsigned long long k = table[s].key;
-        if (k == key) return (long long)s;
-        if (k == MP_EMPTY) return -1;
-        s = (s + 1) & mask;
-    }
-}
-
-// the cell of a key
-__device__ __forceinline__ void sf_cell(unsigned long long key, long long& g0, long long& g1, long long& g2) {
-    g0 = (long long)(key & 0x1fffff) - EPC_MAP_MAX_CELL, g1 = (long long)((key >> 21) & 0x1fffff) - EPC_MAP_MAX_CELL;
-    g2 = (long long)((key >> 42) & 0x1fffff) - EPC_MAP_MAX_CELL;
-}
-__device__ __forceinline__ bool sf_in_range(long long c) { return c >= -EPC_MAP_MAX_CELL && c < EPC_MAP_MAX_CELL; }
-
 // one Jacobi rotation of the pair (p, q), r the third index: epcnet_surfels.h
 __device__ __forceinline__ void sf_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
                                           double& v1p, double& v1q, double& v2p, double& v2q) {
@@ -228,7 +185,7 @@ __device__ __forceinline__ void sf_write_mean(const sf_slot* __restrict__ t, con
     const float nan = epc_nan_f32();
     const long long cnt = (long long)t->cnt;
     long long g0, g1, g2;
-    sf_cell(t->key, g0, g1, g2);
+    mp_cell(t->key, g0, g1, g2);
     const unsigned long long by = cnt != 0 ? (unsigned long long)cnt : 1ull;
     const long long m0 = (long long)(t->sum[0] / by), m1 = (long long)(t->sum[1] / by), m2 = (long long)(t->sum[2] / by);
     const bool keep = cnt >= pr.min_count;
@@ -246,20 +203,20 @@ __device__ __forceinline__ int32_t sf_pool_solve(const sf_slot* __restrict__ tab
     const float nan = epc_nan_f32();
     const long long cnt = (long long)t->cnt;
     long long g0, g1, g2;
-    sf_cell(t->key, g0, g1, g2);
+    mp_cell(t->key, g0, g1, g2);
     // the pool, in the frame of cell g: int64
     long long N = 0, S1x = 0, S1y = 0, S1z = 0, Sxx = 0, Sxy = 0, Sxz = 0, Syy = 0, Syz = 0, Szz = 0;
     const int ring = pr.ring;
     for (int o2 = -ring; o2 <= ring; ++o2) {
         const long long c2 = g2 + o2;
-        if (!sf_in_range(c2)) continue;
+        if (!mp_in_range(c2)) continue;
         for (int o1 = -ring; o1 <= ring; ++o1) {
             const long long c1 = g1 + o1;
-            if (!sf_in_range(c1)) continue;
+            if (!mp_in_range(c1)) continue;
             for (int o0 = -ring; o0 <= ring; ++o0) {
                 const long long c0 = g0 + o0;
-                if (!sf_in_range(c0)) continue;
-                const long long at = sf_find(table, mask, mp_key(c0, c1, c2));
+                if (!mp_in_range(c0)) continue;
+                const long long at = mp_find(table, mask, mp_key(c0, c1, c2));
                 if (at < 0) continue;
                 const sf_slot* q = table + at;
                 const long long n = (long long)q->cnt;
